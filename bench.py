@@ -25,6 +25,10 @@ views/s and the denoise MFMA fraction.  Random-initialised SD1.5-shaped networks
 
 Extra objects: "roofline" (dominant kernel, live hipEvent durations on the launch stream) and "cpu_baseline" (the CPU
 oracle = "port" of the reference algorithm, timed on this box's host cores on a bounded sample: 1 view fwd+bwd).
+
+--dump-outputs DIR: what the last timed step of the headline windows returned — color, radii, depth, alpha and the gradients of
+means3D / shs / opacities / scales / rotations / means2D — as DIR/<name>.npy (float32, a fixed seeded sample of the larger
+arrays: dump_outputs).  Every input is seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -172,6 +176,26 @@ def measure_config4(dev, P=1000000, H=1024, W=1024, V=12, iters=5):
             "sum_stage_ms": {"forward": round(fwd_stage_ms, 4), "forward_backward": round(all_stage_ms, 4)}}
 
 
+DUMP_MAX_ELEMENTS = 1 << 20    # per array (4 MiB of float32): the ten arrays of a step stay under 64 MB at any size
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every tensor of `arrays` as out_dir/<name>.npy in float32 (radii are small integers: exact).  An array of
+    more than DUMP_MAX_ELEMENTS elements is replaced by a fixed sample of its flattened entries, the sorted indices
+    np.random.default_rng(0).choice(numel, DUMP_MAX_ELEMENTS, replace=False): the same entries in every run of the same shape,
+    so two builds compare output for output.  Returns {name: {"shape": full shape, "written": elements written}}."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    info = {}
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.size > DUMP_MAX_ELEMENTS:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_ELEMENTS, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        info[name] = {"shape": list(t.shape), "written": int(a.size)}
+    return info
+
+
 def _free_port():
     import socket
     s = socket.socket()
@@ -280,7 +304,7 @@ def spawn_ranks(n, cmd, env=None, out=None, err=None, timeout=None):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=100)
+    ap.add_argument("--steps", type=int, default=100, help="steps in each timed window (every window times exactly this many)")
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--gaussians", type=int, default=100000)
     ap.add_argument("--size", type=int, default=1024)
@@ -298,7 +322,11 @@ def main():
     ap.add_argument("--no-refine", action="store_true", help="skip configs[4]'s refine-pass / stage-3 measurement (config4.refine, config4.stage3)")
     ap.add_argument("--launch-timeout", type=float, default=float(os.environ.get("GIP_BENCH_LAUNCH_TIMEOUT", "3600")),
                     help="--gpus N launcher: seconds after which still-running ranks are stopped and the run fails (0 = never)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed windows, write what the last timed step returned (rank 0) as DIR/<name>.npy, float32")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` as the driver types it, outside torch.distributed.run: THIS process becomes the
@@ -389,22 +417,27 @@ def main():
                     p_.grad = g_
                 parallel.exchange_sum(plist, viewspace_grads=grads[-1], group=group)
                 pending.wait()
-            return color
+            # what a caller of the path receives: the images, the radii and the gradients (all-reduced in place when exchanged)
+            return color, radii, depth, alpha, grads
         return step
 
     def timed_windows(step_fn, repeats, steps, warmup):
         """W warmup steps, then `repeats` windows of exactly `steps` steps, each between barrier + synchronize pairs and
-        MAX-reduced over the ranks.  Returns the per-window seconds."""
+        MAX-reduced over the ranks.  Returns the per-window seconds and what the last timed step returned."""
         for _ in range(warmup):
             step_fn()
-        out_ = []
+        out_, last = [], None
         for _ in range(repeats):
+            # only a window's final step keeps what it returned: a step that runs while the previous step's outputs (and through
+            # them its autograd graph) are still alive measured 1-2 % slower
+            last = None
             if world > 1:
                 dist.barrier()
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            for _ in range(steps):
+            for _ in range(steps - 1):
                 step_fn()
+            last = step_fn()
             if world > 1:
                 dist.barrier()
             torch.cuda.synchronize()
@@ -414,12 +447,19 @@ def main():
                 dist.all_reduce(et, op=dist.ReduceOp.MAX)
                 el = float(et.item())
             out_.append(el)
-        return out_
+        return out_, last
 
     step = make_step(sts, shard.group if shard is not None else None, world > 1)
     for _ in range(args.prewarm):
         step()
-    windows = timed_windows(step, max(args.repeats, 1), args.steps, args.warmup)
+    windows, last = timed_windows(step, max(args.repeats, 1), args.steps, args.warmup)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        color, radii, depth, alpha, grads = last
+        arrays = {"color": color, "radii": radii, "depth": depth, "alpha": alpha}
+        arrays.update(("grad_" + n, g_) for n, g_ in zip(names + ["means2D"], grads))
+        dumped = dump_outputs(args.dump_outputs, arrays)
+    del last
     elapsed = sorted(windows)[len(windows) // 2]                     # the median window
     n_groups = shard.n_seed_groups if shard is not None else 1
     ms_per_step = elapsed / args.steps * 1e3
@@ -496,7 +536,7 @@ def main():
     replicas = None
     if world > 1:
         sts_r = settings(scenes.train_cameras(V, seed=42 + rank, H=H, W=W))
-        wr_ = timed_windows(make_step(sts_r, None, True), 3, args.steps, args.warmup)
+        wr_, _ = timed_windows(make_step(sts_r, None, True), 3, args.steps, args.warmup)
         dtr = sorted(wr_)[1] / args.steps
         replicas = {"layout": "replicas: %d ranks x %d cameras, one averaged optimizer step" % (world, V),
                     "ms_per_step": round(dtr * 1e3, 4), "views_per_s": round(world * V / dtr, 2),
@@ -508,7 +548,7 @@ def main():
     if world == 1 and not args.no_exact:
         os.environ["GIP_RASTER_EXACT_LISTS"] = "1"
         try:
-            we_ = timed_windows(step, 5, args.steps, max(args.warmup, 3))
+            we_, _ = timed_windows(step, 5, args.steps, max(args.warmup, 3))
             dte = sorted(we_)[2] / args.steps
             stages_e, nr_e = R.profile_stages(t["means3D"].detach(), t["opacities"].detach(), sts, gC[:Vl], gD[:Vl], None, shs=t["shs"].detach(),
                                               scales=t["scales"].detach(), rotations=t["rotations"].detach(), iters=3)
@@ -746,7 +786,8 @@ def main():
                "config4": config4,
                "exact_lists": exact,
                "replicas_layout": replicas,
-               "roofline": roofline, "roofline_valu": valu, "cpu_baseline": cpu}
+               "roofline": roofline, "roofline_valu": valu, "cpu_baseline": cpu,
+               "dump_outputs": None if dumped is None else {"dir": args.dump_outputs, "arrays": dumped}}
     if rank == 0:
         out["ahds"] = ahds
         # BASELINE.json's metric names the AHDS training-step rate first: first-class beside the raster rate
