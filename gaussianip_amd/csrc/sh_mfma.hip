@@ -77,8 +77,10 @@ gip_sh_forward_mfma_kernel(GipKernelParams kp, const float* __restrict__ means3D
     const float* campos = camposs + 3 * v;
     const float d0 = p0 - campos[0], d1 = p1 - campos[1], d2 = p2 - campos[2];
     const float len = sqrtf(d0 * d0 + d1 * d1 + d2 * d2);
+    // a mean at this camera's position (len = 0: the near plane culls it there) takes the zero direction: finite colours
+    const bool dir = len > 0.f;
     float b[N];
-    shm_basis<DEG>(d0 / len, d1 / len, d2 / len, b);
+    shm_basis<DEG>(dir ? d0 / len : 0.f, dir ? d1 / len : 0.f, dir ? d2 / len : 0.f, b);
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int k = 0; k < N; k++) acc = __builtin_amdgcn_mfma_f32_4x4x1f32(b[k], shv[k], acc, 0, 0, 0);
@@ -122,7 +124,11 @@ gip_sh_backward_mfma_kernel(GipKernelParams kp, const float* __restrict__ means3
     for (int vv = 0; vv < 4; vv++) {
       const int view = v0 + vv;
       if (view >= kp.V) break;                                   // uniform
-      const float ga = (valid && sub < 3) ? sh_gcol[((size_t)view * kp.P + gi) * 4 + sub] : 0.f;
+      // a view that culled the Gaussian has dL/dcolour = 0 (gather_backward.hip) and contributes nothing, as in the scalar chain:
+      // its basis operand is zeroed too, since its direction may be 0 / 0 (a mean at that camera's position)
+      const float4 gv = valid ? gc4[(size_t)view * kp.P + gi] : make_float4(0.f, 0.f, 0.f, 0.f);
+      const bool live = gv.x != 0.f || gv.y != 0.f || gv.z != 0.f;
+      const float ga = sub == 0 ? gv.x : sub == 1 ? gv.y : sub == 2 ? gv.z : 0.f;
       const float* campos = camposs + 3 * view;                  // uniform: scalar loads
       const float d0 = p0 - campos[0], d1 = p1 - campos[1], d2 = p2 - campos[2];
       const float len = sqrtf(d0 * d0 + d1 * d1 + d2 * d2);
@@ -132,7 +138,7 @@ gip_sh_backward_mfma_kernel(GipKernelParams kp, const float* __restrict__ means3
       shm_basis<DEG>(d0 / len, d1 / len, d2 / len, b);
 #pragma unroll
       for (int q = 0; q < NQ; q++) {
-        const float bs = sub == 0 ? b[4 * q] : sub == 1 ? b[4 * q + 1] : sub == 2 ? b[4 * q + 2] : b[4 * q + 3];
+        const float bs = !live ? 0.f : sub == 0 ? b[4 * q] : sub == 1 ? b[4 * q + 1] : sub == 2 ? b[4 * q + 2] : b[4 * q + 3];
         dsh[q] = __builtin_amdgcn_mfma_f32_4x4x1f32(ga, bs, dsh[q], 0, 0, 0);
       }
     }
@@ -174,7 +180,7 @@ gip_sh_backward_mfma_kernel(GipKernelParams kp, const float* __restrict__ means3
       }
     }
 #undef W
-    if (vok) {                                                   // through the normalisation of the direction
+    if (vok && (gb.x != 0.f || gb.y != 0.f || gb.z != 0.f)) {    // through the normalisation of the direction (culled view: none)
       const float invsum32 = 1.0f / sqrtf(sum2 * sum2 * sum2);
       dm0 += ((sum2 - d0 * d0) * dx - d1 * d0 * dy - d2 * d0 * dz) * invsum32;
       dm1 += (-d0 * d1 * dx + (sum2 - d1 * d1) * dy - d2 * d1 * dz) * invsum32;
