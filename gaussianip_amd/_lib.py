@@ -23,7 +23,7 @@ class GipRasterConfig(ctypes.Structure):
                 ("debug", ctypes.c_int32), ("scale_modifier", ctypes.c_float),
                 ("tanfovx", ctypes.c_float * GIP_MAX_VIEWS), ("tanfovy", ctypes.c_float * GIP_MAX_VIEWS),
                 ("capacity", ctypes.c_uint64), ("exact_lists", ctypes.c_int32), ("forward_only", ctypes.c_int32),
-                ("sh_scalar", ctypes.c_int32)]
+                ("sh_scalar", ctypes.c_int32), ("antialiasing", ctypes.c_int32)]
 
 
 class GipRasterInputs(ctypes.Structure):

@@ -33,7 +33,8 @@ class _Group:
 
 
 class PipelineParams(_Group):
-    _defaults = dict(convert_SHs_python=False, compute_cov3D_python=False, debug=False)
+    # antialiasing: the upstream package's opacity-compensated 2-D filter (GaussianRasterizationSettings.antialiasing)
+    _defaults = dict(convert_SHs_python=False, compute_cov3D_python=False, debug=False, antialiasing=False)
 
     def __init__(self, parser=None, **kw):
         super().__init__(parser, "Pipeline Parameters", **kw)

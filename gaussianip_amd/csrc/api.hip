@@ -5,6 +5,9 @@
 
 static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
+// `antialiasing` took the config's tail padding: ABI 4 callers (ctypes zero-fills) see the same layout
+static_assert(offsetof(GipRasterConfig, antialiasing) == 188 && sizeof(GipRasterConfig) == 192, "GipRasterConfig layout");
+
 // matrix-core SH path (sh_mfma.hip): SH coefficients given (sh_coeffs > 0; 0 = colors_precomp), something to contract
 // (degree >= 1), views to batch (V >= 2), not switched off
 static bool sh_mfma_path(const GipRasterConfig* c) { return c->sh_coeffs > 0 && c->sh_degree >= 1 && c->V >= 2 && !c->sh_scalar; }
@@ -87,6 +90,7 @@ static void fill_params(const GipRasterConfig* c, const GipRasterStateLayout& L,
   kp->exact_lists = c->exact_lists ? 1 : 0;
   kp->forward_only = c->forward_only ? 1 : 0;
   kp->sh_mfma = sh_mfma_path(c) ? 1 : 0;
+  kp->antialiasing = c->antialiasing ? 1 : 0;
   kp->ckpt_capacity = (uint32_t)(c->capacity / GIP_SEGMENT + 1);
   kp->seg_capacity = kp->ckpt_capacity + (uint32_t)(kp->V * kp->T);
   for (int v = 0; v < c->V; v++) {

@@ -16,10 +16,14 @@ __device__ static const float GSH_C3[7] = {-0.5900435899266435f, 2.8906114426405
                                            0.3731763325901154f, -0.4570457994644658f, 1.445305721320277f,
                                            -0.5900435899266435f};
 
-template <int MAXM>
+// AA: GipKernelParams::antialiasing, a template parameter so that the fork's model compiles to exactly the code it had
+// without the mode (a scalar branch lets the compiler share the mode's products with the conic chain and re-decide FMA
+// contraction there)
+template <int MAXM, bool AA>
 __global__ void __launch_bounds__(GIP_BLOCK)
 gip_gather_backward_kernel(GipKernelParams kp, const float* __restrict__ means3D, const float* __restrict__ shs,
-                           const float* __restrict__ colors_precomp, const float* __restrict__ scales,
+                           const float* __restrict__ colors_precomp, const float* __restrict__ opacities,
+                           const float* __restrict__ scales,
                            const float* __restrict__ rotations, const float* __restrict__ cov3D_precomp,
                            const float* __restrict__ viewmatrix, const float* __restrict__ projmatrix,
                            const float* __restrict__ camposs, const GipRecord* __restrict__ records,
@@ -113,7 +117,7 @@ gip_gather_backward_kernel(GipKernelParams kp, const float* __restrict__ means3D
     const float g2y = -(con_c * a[1] + con_b * a[0]) * (0.5f * kp.H);
     const float gcx = -0.5f * a[2], gcy = -0.5f * a[3], gcw = -0.5f * a[4];
     if (d2) { d2[0] = g2x; d2[1] = g2y; d2[2] = 0.f; }
-    dopac += opac != 0.f ? a[5] / opac : 0.f;
+    const float gop = opac != 0.f ? a[5] / opac : 0.f;           // dL/d(the record's opacity)
 
     const float* view = viewmatrix + 16 * v;
     const float* proj = projmatrix + 16 * v;
@@ -136,16 +140,34 @@ gip_gather_backward_kernel(GipKernelParams kp, const float* __restrict__ means3D
     const float M10 = J11 * view[1] + J12 * view[2], M11 = J11 * view[5] + J12 * view[6], M12 = J11 * view[9] + J12 * view[10];
     const float v00 = c0 * M00 + c1 * M01 + c2 * M02, v01 = c1 * M00 + c3 * M01 + c4 * M02, v02 = c2 * M00 + c4 * M01 + c5 * M02;
     const float v10 = c0 * M10 + c1 * M11 + c2 * M12, v11 = c1 * M10 + c3 * M11 + c4 * M12, v12 = c2 * M10 + c4 * M11 + c5 * M12;
-    const float ca = (M00 * v00 + M01 * v01 + M02 * v02) + 0.3f;
+    const float cau = M00 * v00 + M01 * v01 + M02 * v02;          // undilated cov2D: cau, cb, ccu
     const float cb = M00 * v10 + M01 * v11 + M02 * v12;
-    const float cc = (M10 * v10 + M11 * v11 + M12 * v12) + 0.3f;
+    const float ccu = M10 * v10 + M11 * v11 + M12 * v12;
+    const float ca = cau + 0.3f, cc = ccu + 0.3f;
     const float denom = ca * cc - cb * cb;
     const float denom2inv = 1.0f / ((denom * denom) + 0.0000001f);
+    // antialiasing: the record's opacity is o comp, comp = sqrt(max(0.000025, r)), r = (cau ccu - cb^2) / denom (preprocess.hip)
+    float comp = 1.f, aa_r = 0.f;
+    if (AA) {
+      aa_r = (cau * ccu - cb * cb) / denom;
+      comp = sqrtf(fmaxf(0.000025f, aa_r));
+      dopac += comp * gop;
+    } else {
+      dopac += gop;
+    }
     float dL_da = 0.f, dL_db = 0.f, dL_dc = 0.f;
     if (denom2inv != 0.f) {
       dL_da = denom2inv * (-cc * cc * gcx + 2 * cb * cc * gcy + (denom - ca * cc) * gcw);
       dL_dc = denom2inv * (-ca * ca * gcw + 2 * ca * cb * gcy + (denom - ca * cc) * gcx);
       dL_db = denom2inv * 2 * (cb * cc * gcx - (denom + 2 * cb * cb) * gcy + ca * cb * gcw);
+      if (AA && aa_r > 0.000025f) {
+        // dL/dcomp = gop o; dcomp/dr = 0.5 / comp; with h = 0.3: dr/da = h (ccu cc + cb^2) / denom^2,
+        // dr/dc = h (cau ca + cb^2) / denom^2, dr/db = -2 cb h (cau + ccu + h) / denom^2 (zero on the clamped branch)
+        const float k = gop * opacities[idx] * 0.3f * 0.5f / (comp * denom * denom);
+        dL_da += k * (ccu * cc + cb * cb);
+        dL_dc += k * (cau * ca + cb * cb);
+        dL_db -= k * 2.f * cb * (cau + ccu + 0.3f);
+      }
       dcov[0] += M00 * M00 * dL_da + M00 * M10 * dL_db + M10 * M10 * dL_dc;
       dcov[3] += M01 * M01 * dL_da + M01 * M11 * dL_db + M11 * M11 * dL_dc;
       dcov[5] += M02 * M02 * dL_da + M02 * M12 * dL_db + M12 * M12 * dL_dc;
@@ -298,13 +320,15 @@ gip_gather_backward_kernel(GipKernelParams kp, const float* __restrict__ means3D
 void gip_launch_gather_backward(const GipKernelParams& kp, const GipRasterInputs& in, GipStatePtrs st, const float* partial,
                                 const GipRasterGradsOut& gout, hipStream_t s) {
   const dim3 grid(kp.nblk), block(GIP_BLOCK);
-#define LAUNCH(MM) hipLaunchKernelGGL((gip_gather_backward_kernel<MM>), grid, block, 0, s, kp, in.means3D, in.shs, \
-    in.colors_precomp, in.scales, in.rotations, in.cov3D_precomp, in.viewmatrix, in.projmatrix, in.campos, st.records, \
+#define LAUNCH_AA(MM, AA) hipLaunchKernelGGL((gip_gather_backward_kernel<MM, AA>), grid, block, 0, s, kp, in.means3D, in.shs, \
+    in.colors_precomp, in.opacities, in.scales, in.rotations, in.cov3D_precomp, in.viewmatrix, in.projmatrix, in.campos, st.records, \
     st.inst_offset, partial, gout, st.header, kp.sh_mfma ? st.sh_colors : nullptr)
+#define LAUNCH(MM) do { if (kp.antialiasing) LAUNCH_AA(MM, true); else LAUNCH_AA(MM, false); } while (0)
   const int needed = (in.shs && !kp.sh_mfma) ? (kp.D + 1) * (kp.D + 1) : 1;      // matrix-core SH path: no dsh registers here
   if (needed <= 1) LAUNCH(1);
   else if (needed <= 4) LAUNCH(4);
   else if (needed <= 9) LAUNCH(9);
   else LAUNCH(16);
 #undef LAUNCH
+#undef LAUNCH_AA
 }

@@ -48,6 +48,7 @@ struct GipKernelParams {
   int exact_lists;          // GipRasterConfig::exact_lists
   int forward_only;         // GipRasterConfig::forward_only: nothing is kept for a backward
   int sh_mfma;              // SH colours / their backward on the matrix cores (sh_mfma.hip): shs given, degree >= 1, V >= 2, !sh_scalar
+  int antialiasing;         // GipRasterConfig::antialiasing: opacity-compensated 2-D filter (preprocess.hip, gather_backward.hip)
   GipViewConst view[GIP_MAX_VIEWS];
 };
 

@@ -124,11 +124,17 @@ gip_preprocess_kernel(GipKernelParams kp, const float* __restrict__ means3D, con
       const float v10 = c0 * M10 + c1 * M11 + c2 * M12;
       const float v11 = c1 * M10 + c3 * M11 + c4 * M12;
       const float v12 = c2 * M10 + c4 * M11 + c5 * M12;
-      const float a = (M00 * v00 + M01 * v01 + M02 * v02) + 0.3f;
+      const float au = M00 * v00 + M01 * v01 + M02 * v02;
       const float b = M00 * v10 + M01 * v11 + M02 * v12;
-      const float c = (M10 * v10 + M11 * v11 + M12 * v12) + 0.3f;
+      const float cu = M10 * v10 + M11 * v11 + M12 * v12;
+      const float a = au + 0.3f, c = cu + 0.3f;                   // undilated: au, b, cu
       const float det = a * c - b * b;
       if (det != 0.0f) {
+        // antialiasing (Mip-Splatting's 2-D filter): the dilation's added energy is taken back out of the opacity,
+        // o sqrt(max(0.000025, det_undilated / det)); conic, radius and rectangle stay the dilated covariance's.  Everything downstream (the 1/255 pruning
+        // below, the tile masks, both render kernels) reads this opacity from the record.
+        float opac = opacities[idx];
+        if (kp.antialiasing) opac *= sqrtf(fmaxf(0.000025f, (au * cu - b * b) / det));
         const float det_inv = 1.f / det;
         const float mid = 0.5f * (a + c);
         const float lambda1 = mid + sqrtf(fmaxf(0.1f, mid * mid - det));
@@ -148,7 +154,7 @@ gip_preprocess_kernel(GipKernelParams kp, const float* __restrict__ means3D, con
         // output; radii / visibility keep the fork's 3-sigma definition.  (Bench scene: 14 % fewer instances.)
         int ntiles = ntiles_ref;
         if (ntiles_ref != 0 && !kp.exact_lists) {
-          const float t2 = 2.0f * logf(255.0f * opacities[idx]) + 0.02f;
+          const float t2 = 2.0f * logf(255.0f * opac) + 0.02f;
           if (t2 <= 0.f) {
             ntiles = 0;
           } else {
@@ -182,7 +188,7 @@ gip_preprocess_kernel(GipKernelParams kp, const float* __restrict__ means3D, con
             clamped = (cr < 0.f ? 1u : 0u) | (cg < 0.f ? 2u : 0u) | (cb < 0.f ? 4u : 0u);
             cr = fmaxf(cr, 0.f); cg = fmaxf(cg, 0.f); cb = fmaxf(cb, 0.f);
           }
-          rec.x = pixx; rec.y = pixy; rec.depth = pvz; rec.opacity = opacities[idx];
+          rec.x = pixx; rec.y = pixy; rec.depth = pvz; rec.opacity = opac;
           rec.ca = c * det_inv; rec.cb = -b * det_inv; rec.cc = a * det_inv; rec.tiles = (uint32_t)ntiles;
           rec.r = cr; rec.g = cg; rec.b = cb; rec.radius = rad;
           rec.rmin = (uint32_t)rminx | ((uint32_t)rminy << 16);

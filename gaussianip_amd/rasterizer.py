@@ -3,6 +3,7 @@
 Reference interface reproduced (the package is an un-vendored dependency; the contract is its call sites):
   * GaussianRasterizationSettings(image_height, image_width, tanfovx, tanfovy, bg, scale_modifier, viewmatrix,
     projmatrix, sh_degree, campos, prefiltered, debug)          gaussian_renderer/__init__.py:36-49
+    plus the upstream package's optional 13th field `antialiasing` (default False = the fork's model)
   * GaussianRasterizer(raster_settings)(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
     cov3D_precomp) -> (color [3,H,W], radii [P] int32, depth [1,H,W], alpha [1,H,W])      :51, :85-93
   * GaussianRasterizer.markVisible(positions)
@@ -42,6 +43,8 @@ class GaussianRasterizationSettings(NamedTuple):
     campos: torch.Tensor
     prefiltered: bool
     debug: bool
+    # upstream diff_gaussian_rasterization's switch: Mip-Splatting's 2-D filter with opacity compensation (GipRasterConfig::antialiasing)
+    antialiasing: bool = False
 
 
 # ---------------------------------------------------------------------------------------------
@@ -116,7 +119,8 @@ class _Plan:
     pass
 
 
-def _make_config(P, V, H, W, sh_degree, M, scale_modifier, tanfovx, tanfovy, capacity, prefiltered, debug, forward_only=False):
+def _make_config(P, V, H, W, sh_degree, M, scale_modifier, tanfovx, tanfovy, capacity, prefiltered, debug, forward_only=False,
+                 antialiasing=False):
     cfg = _lib.GipRasterConfig()
     cfg.P, cfg.V, cfg.H, cfg.W = int(P), int(V), int(H), int(W)
     cfg.sh_degree, cfg.sh_coeffs = int(sh_degree), int(M)
@@ -129,6 +133,7 @@ def _make_config(P, V, H, W, sh_degree, M, scale_modifier, tanfovx, tanfovy, cap
     cfg.exact_lists = 1 if _exact_lists() else 0
     cfg.forward_only = 1 if forward_only else 0
     cfg.sh_scalar = 1 if _sh_scalar() else 0
+    cfg.antialiasing = 1 if antialiasing else 0
     return cfg
 
 
@@ -144,7 +149,7 @@ def _run_forward(plan, capacity, forward_only=False):
     lib = _lib.raster_lib()
     dev = plan.means3D.device
     cfg = _make_config(plan.P, plan.V, plan.H, plan.W, plan.sh_degree, plan.M, plan.scale_modifier, plan.tanfovx,
-                       plan.tanfovy, capacity, plan.prefiltered, plan.debug, forward_only)
+                       plan.tanfovy, capacity, plan.prefiltered, plan.debug, forward_only, plan.antialiasing)
     nbytes = lib.gip_raster_state_bytes(ctypes.byref(cfg))
     if nbytes == 0:
         raise ValueError("invalid rasterizer configuration (P=%d V=%d H=%d W=%d sh_degree=%d)" %
@@ -336,10 +341,14 @@ def _build_plan(means3D, shs, colors_precomp, opacities, scales, rotations, cov3
     plan.M = 0 if plan.shs is None else int(plan.shs.shape[1])
     plan.scale_modifier = float(s0.scale_modifier)
     plan.prefiltered, plan.debug = bool(s0.prefiltered), bool(s0.debug)
+    # no capacity-hint key of its own: the compensation only lowers opacities, so a launch set has at most the instances
+    # of the same call without it, and a hint learnt either way covers it
+    plan.antialiasing = bool(getattr(s0, "antialiasing", False))
     for s in settings_list[1:]:
-        if (int(s.image_height), int(s.image_width), int(s.sh_degree), float(s.scale_modifier)) != \
-                (plan.H, plan.W, plan.sh_degree, plan.scale_modifier):
-            raise ValueError("all views of one call must share image size, sh_degree and scale_modifier")
+        if (int(s.image_height), int(s.image_width), int(s.sh_degree), float(s.scale_modifier),
+                bool(getattr(s, "antialiasing", False))) != \
+                (plan.H, plan.W, plan.sh_degree, plan.scale_modifier, plan.antialiasing):
+            raise ValueError("all views of one call must share image size, sh_degree, scale_modifier and antialiasing")
     plan.tanfovx = [float(s.tanfovx) for s in settings_list]
     plan.tanfovy = [float(s.tanfovy) for s in settings_list]
     if V == 1:

@@ -9,7 +9,9 @@ Deviations, all documented in DESIGN.md:
   * the reference casts the `None` placeholders with `.float()` (:88,:91,:92), so its convert_SHs_python /
     compute_cov3D_python switches can only work through gs_renderer.Renderer.render (gs_renderer.py:969-1001);
     here both switches work (None inputs are passed through un-cast, as gs_renderer does);
-  * `render_views` renders all cameras of a batch in ONE launch set (the reference loops, GaussianIP.py:154-173).
+  * `render_views` renders all cameras of a batch in ONE launch set (the reference loops, GaussianIP.py:154-173);
+  * `pipe.antialiasing` (upstream's PipelineParams field; absent = False) selects the rasterizer's opacity-compensated
+    2-D filter; `render_deformed`, which has no `pipe`, takes it as a keyword.
 """
 import math
 
@@ -19,12 +21,17 @@ from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer, raste
 from .utils.sh import eval_sh
 
 
-def _settings(cam, pc, bg_color, scaling_modifier):
+def _settings(cam, pc, bg_color, scaling_modifier, antialiasing=False):
     return GaussianRasterizationSettings(
         image_height=int(cam.image_height), image_width=int(cam.image_width),
         tanfovx=math.tan(cam.FoVx * 0.5), tanfovy=math.tan(cam.FoVy * 0.5), bg=bg_color,
         scale_modifier=scaling_modifier, viewmatrix=cam.world_view_transform, projmatrix=cam.full_proj_transform,
-        sh_degree=pc.active_sh_degree, campos=cam.camera_center, prefiltered=False, debug=False)
+        sh_degree=pc.active_sh_degree, campos=cam.camera_center, prefiltered=False, debug=False,
+        antialiasing=bool(antialiasing))
+
+
+def _antialiasing(pipe):
+    return bool(getattr(pipe, "antialiasing", False))     # a reference-side PipelineParams has no such field
 
 
 def _select_inputs(cam, pc, pipe, scaling_modifier, override_color, activated=False):
@@ -65,7 +72,8 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
         screenspace_points.retain_grad()
     except Exception:
         pass
-    rasterizer = GaussianRasterizer(raster_settings=_settings(viewpoint_camera, pc, bg_color, scaling_modifier))
+    rasterizer = GaussianRasterizer(raster_settings=_settings(viewpoint_camera, pc, bg_color, scaling_modifier,
+                                                              _antialiasing(pipe)))
     scales, rotations, cov3D, shs, colors = _select_inputs(viewpoint_camera, pc, pipe, scaling_modifier, override_color)
     image, radii, depth, alpha = rasterizer(
         means3D=xyz.float(), means2D=screenspace_points.float(), shs=_f(shs), colors_precomp=colors,
@@ -81,7 +89,7 @@ def render_with_smaller_scale(viewpoint_camera, pc, pipe, bg_color: torch.Tensor
 
 
 def render_deformed(viewpoint_camera, means3D, opacity, scales, rotations, shs, active_sh_degree, bg_color,
-                    scaling_modifier=1.0):
+                    scaling_modifier=1.0, antialiasing=False):
     """Explicit-tensor variant (:195-265): returns no depth / alpha entries."""
     screenspace_points = torch.zeros_like(means3D, dtype=means3D.dtype, requires_grad=True, device=means3D.device) + 0
     try:
@@ -93,7 +101,7 @@ def render_deformed(viewpoint_camera, means3D, opacity, scales, rotations, shs, 
         image_height=int(cam.image_height), image_width=int(cam.image_width), tanfovx=math.tan(cam.FoVx * 0.5),
         tanfovy=math.tan(cam.FoVy * 0.5), bg=bg_color, scale_modifier=scaling_modifier,
         viewmatrix=cam.world_view_transform, projmatrix=cam.full_proj_transform, sh_degree=active_sh_degree,
-        campos=cam.camera_center, prefiltered=False, debug=False)
+        campos=cam.camera_center, prefiltered=False, debug=False, antialiasing=bool(antialiasing))
     image, radii, _depth, _alpha = GaussianRasterizer(raster_settings=st)(
         means3D=means3D.float(), means2D=screenspace_points.float(), shs=shs.float(), colors_precomp=None,
         opacities=opacity.float(), scales=scales.float(), rotations=rotations.float())
@@ -145,7 +153,7 @@ def render_views(cameras, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0
     scales, rotations, cov3D, shs, colors = _select_inputs(cameras[0], pc, pipe, scaling_modifier, override_color, activated=True)
     act = pc.__dict__.pop("_act_cache", None)
     opacity = act[0] if act is not None else pc.get_opacity
-    sts = [_settings(c, pc, bg_color, scaling_modifier) for c in cameras]
+    sts = [_settings(c, pc, bg_color, scaling_modifier, _antialiasing(pipe)) for c in cameras]
     image, radii, depth, alpha = rasterize_views(
         xyz.float(), screenspace_points.float(), opacity.float(), sts, shs=_f(shs), colors_precomp=colors,
         scales=_f(scales), rotations=_f(rotations), cov3D_precomp=cov3D)

@@ -89,6 +89,12 @@ typedef struct GipRasterConfig {
                              Gaussian's [4 views x K] . [K x 3] product per 4 x 4 block); colours then agree with the scalar sum
                              to a few ulp — no integer buffer depends on them.  1: always the scalar chain of eval_sh
                              (sh_utils.py:57-112), bit-exact against the oracle's colours.  V = 1 and degree 0 are always scalar. */
+  int32_t antialiasing;   /* 0 (default) = the fork's model: the +0.3 px^2 screen-space dilation at full opacity.  1: the 2-D filter of
+                             Mip-Splatting with opacity compensation (settings.antialiasing of the upstream package): every
+                             (view, Gaussian) blends with opacity * sqrt(max(0.000025, det(cov2D) / det(cov2D + 0.3 I))) — the
+                             record's opacity slot holds that product; conic, radius, rectangle (radii, visibility) stay the
+                             dilated covariance's.  The field sits in what was tail padding: layout and GIP_ABI_VERSION unchanged,
+                             and a caller that zero-fills the struct gets the fork's model. */
 } GipRasterConfig;
 
 /* Device inputs.  Exactly one of (shs, colors_precomp) and one of (scales+rotations, cov3D_precomp)
@@ -189,7 +195,7 @@ typedef struct GipRasterStateLayout {
 /* Per-(view,Gaussian) record (GIP_RECORD_BYTES = 64), written by preprocess:
  *   float  x, y        pixel-space centre (points_xy_image)
  *   float  depth       view-space z
- *   float  opacity
+ *   float  opacity     settings.antialiasing: opacity x the compensation factor (GipRasterConfig::antialiasing)
  *   float  conic_a, conic_b, conic_c
  *   uint32 tiles_touched   instances made for this Gaussian = tiles of the rectangle below that are set in tile_mask.  NOT the fork's count: the
  *                          fork's 3-sigma rectangle is intersected with the extent of the alpha >= 1/255 region
