@@ -27,7 +27,6 @@
 #include <hip/hip_runtime.h>
 #include <type_traits>
 #include <stdint.h>
-#include <stdlib.h>
 
 #include "../../include/gip_nn.h"
 
@@ -38,6 +37,12 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define CV_BM 128
 #define CV_BK 64
 #define CV_THREADS 256
+constexpr int CV_STAGES = 2;              // LDS stages of the K loop (one pipeline depth is built: see the loop)
+
+// geom = stride | pad_top << 8 | pad_left << 16 | the flags below
+constexpr int CV_NMAJOR = 1 << 24;        // tile order inside an XCD's chunk: n-major (tiles sharing a weight block together)
+constexpr int CV_LDS_EPI = 1 << 25;       // epilogue through an LDS tile image (16-byte row stores, statistics)
+constexpr int CV_GN_IN = 1 << 30;         // halo kernel: GroupNorm (+ SiLU) of gnb applied to the input in LDS
 
 #define CV_OOB 0xFFFF0000u                // voffset beyond any num_records: the buffer load returns 0
 #define CV_RSRC_FLAGS 0x00020000         // raw buffer, 32-bit data format (gfx9 family)
@@ -130,7 +135,8 @@ __device__ __forceinline__ void gnb_accumulate(const GnBwdArgs& a, const GnBwdLa
 // the nine taps then read their fragments from that one image at shifted rows.  The K loop only streams the weights: 16 KB of
 // LDS-DMA per K step instead of 32, plus 46 KB once instead of 9 x 32 KB of pixels.  Why: at Cin = 128 (the VAE encoder's first
 // level, 4 x 512^2: 8 of its convolutions, 4.1 ms of the training step at 675 TFLOP/s) the K loop is only 18 steps and the
-// kernel is bound by its L2 -> LDS traffic (tools/exp_conv_ablate.py: the DMA stream alone = 70 % of the kernel).
+// kernel is bound by its L2 -> LDS traffic (the DMA stream alone = 70 % of the kernel: timing ablations,
+// tools/experiments/conv3x3_timing_ablations.diff.txt).
 #define CVH_ROWS 184                      // halo rows held per channel block (180 used: 10 x 18; waves 0-2 of the sixth round)
 #define CVH_KC_BYTES (CVH_ROWS * 128)
 // KG = 2 (round 6, TAPS = 1 GEMMs on grids of at most one workgroup per CU): TWO K groups of four waves inside one workgroup.  A lone
@@ -142,7 +148,7 @@ __device__ __forceinline__ void gnb_accumulate(const GnBwdArgs& a, const GnBwdLa
 // bit-identical to KG = 1.  (Extended to whole-K 3x3 convolutions of 171..256 tiles — the shared prefix at batch 4, a shard's
 // 64 x 64 level — in place of split-K = 2, it measured SLOWER in the step: full step 33.25 -> 33.38 ms, and it gave back 0.09 of the
 // shard's 0.22 ms: eight waves holding 147 KB of LDS keep the OTHER stream's workgroups off the CU in the two-stream denoise.)
-template <int BN, int STAGES, int TAPS, bool GEGLU, bool HALO = false, int KG = 1>
+template <int BN, int TAPS, bool GEGLU, bool HALO = false, int KG = 1>
 __global__ void __launch_bounds__(CV_THREADS * KG, 2)
 conv3x3_kernel(const _Float16* __restrict__ x, const _Float16* __restrict__ w, const _Float16* __restrict__ bias,
                const _Float16* __restrict__ residual, _Float16* __restrict__ out, int N, int H, int W, int Cin, int Cout,
@@ -153,7 +159,7 @@ conv3x3_kernel(const _Float16* __restrict__ x, const _Float16* __restrict__ w, c
   if constexpr (TAPS == 1) {
     x += (size_t)blockIdx.y * bs_x; w += (size_t)blockIdx.y * bs_w; out += (size_t)blockIdx.y * bs_o;
   }
-  // geom = stride | pad_top << 8 | pad_left << 16; H, W are the OUTPUT dims, Hin, Win the input dims (equal at stride 1)
+  // geom = stride, pads and CV_* flags (see above); H, W are the OUTPUT dims, Hin, Win the input dims (equal at stride 1)
   // tapsel (TAPS = 9): bits 0-8 = the taps the K loop visits (0x1ff: all nine); bit 11 = scatter: output pixel (n, a, b) is
   // written to row (n, 2 a + pi, 2 b + pj) of a [N, 2 H, 2 W, Cout] tensor, pi = bit 9, pj = bit 10 — one parity class of
   // the DATA GRADIENT of a stride-2 convolution (gip_conv3x3s2_dgrad_nhwc_f16 below).  Bit 12 = all four parity classes in
@@ -181,9 +187,9 @@ conv3x3_kernel(const _Float16* __restrict__ x, const _Float16* __restrict__ w, c
   static_assert(KG == 1 || (KG == 2 && TAPS == 1 && !HALO && !GEGLU), "two K groups: plain GEMMs only");
   constexpr int B_ROUNDS = BN / 32;
   constexpr int NI = BN / 32;                   // 16-channel MFMA tiles per wave (its half of BN)
-  const int kg = KG > 1 ? (int)threadIdx.x / CV_THREADS : 0;           // K group of this wave (wave-uniform)
+  const int kg = KG > 1 ? __builtin_amdgcn_readfirstlane((int)threadIdx.x / CV_THREADS) : 0;   // K group of this wave (an SGPR)
   const int tid = KG > 1 ? (int)threadIdx.x % CV_THREADS : (int)threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  unsigned char* const gsm = smem + (KG > 1 ? kg * (STAGES * STAGE) : 0);      // this group's stage buffers
+  unsigned char* const gsm = smem + (KG > 1 ? kg * (CV_STAGES * STAGE) : 0);      // this group's stage buffers
   const int wm = wave & 1, wn = wave >> 1;
 
   // tile of this workgroup (bijective XCD remap: ids congruent mod 8 share an XCD)
@@ -192,11 +198,11 @@ conv3x3_kernel(const _Float16* __restrict__ x, const _Float16* __restrict__ w, c
   const int total = m_tiles * n_tiles, id = (int)(bid % (unsigned)total), split = (int)(bid / (unsigned)total);
   const int q = total >> 3, r = total & 7, xcd = id & 7;
   const int t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (id >> 3);
-  // tile order inside an XCD's contiguous chunk (geom bit 24): m-major keeps the tiles that share a PIXEL block together
+  // tile order inside an XCD's contiguous chunk (CV_NMAJOR): m-major keeps the tiles that share a PIXEL block together
   // (the activations are the big operand: VAE, 64^2 / 32^2 levels), n-major the tiles that share a WEIGHT block (16^2 /
   // 8^2 levels: 30-60 MB of weights against a few MB of activations) — whichever operand is larger is then fetched into
   // each XCD's L2 once instead of eight times
-  const bool nmajor = (geom >> 24) & 1;
+  const bool nmajor = geom & CV_NMAJOR;
   const int mt = nmajor ? t % m_tiles : t / n_tiles, nt = nmajor ? t / m_tiles : t - (t / n_tiles) * n_tiles;
   const unsigned M = (unsigned)N * H * W;          // < 2^31 (checked on the host): 32-bit index arithmetic throughout
   const unsigned m0 = (unsigned)mt * CV_BM;
@@ -284,16 +290,12 @@ conv3x3_kernel(const _Float16* __restrict__ x, const _Float16* __restrict__ w, c
     const unsigned wtap_off = (unsigned)(tap * Cin + cb * CV_BK) * 2u;
     if constexpr (!HALO) {
       unsigned char* sa = gsm + buf * STAGE + wave * 1024;
-      if (!((geom >> 26) & 1)) {
 #pragma unroll
-        for (int i = 0; i < 4; i++) dma16(xr, ((a_mask[i] >> tap) & 1u) ? a_off[i] : CV_OOB, tap_off, sa + i * 4096);
-      }
+      for (int i = 0; i < 4; i++) dma16(xr, ((a_mask[i] >> tap) & 1u) ? a_off[i] : CV_OOB, tap_off, sa + i * 4096);
     }
     unsigned char* sb = gsm + HALO_BYTES + buf * STAGE + A_BYTES + wave * 1024;
-    if (!((geom >> 27) & 1)) {
 #pragma unroll
-      for (int i = 0; i < B_ROUNDS; i++) dma16(wr, b_off[i], wtap_off, sb + i * 4096);
-    }
+    for (int i = 0; i < B_ROUNDS; i++) dma16(wr, b_off[i], wtap_off, sb + i * 4096);
   };
 
   f32x4 acc[NI][4];
@@ -354,7 +356,6 @@ conv3x3_kernel(const _Float16* __restrict__ x, const _Float16* __restrict__ w, c
   // two LDS stages: the DMA of step t + 1 is in flight while the MFMAs of step t run; one wait + barrier per step.  (A
   // three-stage single-workgroup-per-CU variant and BK = 32 variants with 3 / 4 stages and counted vmcnt were measured
   // slower: tools/experiments/conv3x3_bk32_multistage.hip.txt holds both.)
-  static_assert(STAGES == 2, "one pipeline depth is built");
   if constexpr (HALO) {
     // the halo image, once: 6 rounds of 32 rows per channel block (round 5: waves 0-2 only, rows 160..183; rows >= 180 and
     // pixels outside the image read zeros from an out-of-range offset).  Row r = halo pixel (r / 18, r % 18) = image pixel
@@ -392,7 +393,7 @@ conv3x3_kernel(const _Float16* __restrict__ x, const _Float16* __restrict__ w, c
   [[maybe_unused]] const int gn_cbk = (tid >> 3) & 1, gn_lch = tid & 7;
   [[maybe_unused]] float sc8[8], sh8[8];
   if constexpr (HALO) {
-    if ((geom >> 30) & 1) {
+    if (geom & CV_GN_IN) {
 #pragma unroll
       for (int j = 0; j < 8; j++) {
         const int c = gn_cbk * 64 + gn_lch * 8 + j, g = c / (128 / gnb.G);
@@ -405,7 +406,7 @@ conv3x3_kernel(const _Float16* __restrict__ x, const _Float16* __restrict__ w, c
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   if constexpr (HALO) {
-    if ((geom >> 30) & 1) {
+    if (geom & CV_GN_IN) {
       // GN-IN (round 5): the convolution's input is y = silu?(GroupNorm(x + addend)) and y is never materialised — the halo image
       // holds RAW x and is normalised in place here, once per tile (gnb = that GroupNorm: gamma, beta, mean, rstd, addend over
       // the Cin = 128 input channels).  Same arithmetic as csrc/groupnorm.hip's apply pass (sc = rstd gamma, sh = beta - (mean -
@@ -444,13 +445,20 @@ conv3x3_kernel(const _Float16* __restrict__ x, const _Float16* __restrict__ w, c
     const int buf = kt & 1;
     const int tap_n = tap, cb_n = cb;
     if (kt + 1 < KT) { stage(tap, cb, buf ^ 1); advance(); }
-    if (!((geom >> 28) & 1) && (KG == 1 || kt < KT)) compute(gsm + HALO_BYTES + buf * STAGE, tap_c, cb_c);
+    if (KG == 1 || kt < KT) compute(gsm + HALO_BYTES + buf * STAGE, tap_c, cb_c);
     tap_c = tap_n; cb_c = cb_n;
+    // every MFMA of step t issues before the wait for step t + 1's DMA: hipcc otherwise moves the last ones (register-only) past
+    // the wait and the barrier, and the DMA latency overlaps fewer of them
+    __builtin_amdgcn_sched_barrier(0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
   }
+  // KG = 2: group 1 hands its partial products over and group 0 runs the epilogue on the sum.  No wave leaves the kernel before
+  // the last barrier: group 1 stays resident and passes every barrier below with its work predicated off (`active`), and every
+  // branch around a barrier tests a workgroup-uniform value, so both groups run the same barrier sequence.
+  const bool active = KG == 1 || kg == 0;
   if constexpr (KG == 2) {
-    // group 1's partial products -> LDS (every lane its own f32x4 slots: conflict-free), group 0 adds them and goes on alone
+    // every lane its own f32x4 slots: conflict-free
     f32x4* red = (f32x4*)smem;                     // NI * 4 * 256 x 16 B <= the two groups' stage buffers (checked at the launch)
     if (kg == 1) {
 #pragma unroll
@@ -459,23 +467,24 @@ conv3x3_kernel(const _Float16* __restrict__ x, const _Float16* __restrict__ w, c
         for (int mi = 0; mi < 4; mi++) red[(ni * 4 + mi) * CV_THREADS + tid] = acc[ni][mi];
     }
     __syncthreads();
-    if (kg == 1) return;
+    if (kg == 0) {
 #pragma unroll
-    for (int ni = 0; ni < NI; ni++)
+      for (int ni = 0; ni < NI; ni++)
 #pragma unroll
-      for (int mi = 0; mi < 4; mi++) {
-        const f32x4 o = red[(ni * 4 + mi) * CV_THREADS + tid];
-        acc[ni][mi][0] += o[0]; acc[ni][mi][1] += o[1]; acc[ni][mi][2] += o[2]; acc[ni][mi][3] += o[3];
-      }
-    asm volatile("s_barrier" ::: "memory");        // group 0's four waves: `red` is about to be reused by the epilogue's tile image
+        for (int mi = 0; mi < 4; mi++) {
+          const f32x4 o = red[(ni * 4 + mi) * CV_THREADS + tid];
+          acc[ni][mi][0] += o[0]; acc[ni][mi][1] += o[1]; acc[ni][mi][2] += o[2]; acc[ni][mi][3] += o[3];
+        }
+    }
+    __syncthreads();                               // `red` is about to be reused by the epilogue's tile image
   }
 
   // ---- LayerNorm fold: (rstd, -rstd * mu) of the tile's 128 rows from the producer's per-row partial sums, kept in the last KB
   //      of the (now free) stage buffers — behind everything the epilogues below stage there
   const bool ln_fold = TAPS == 1 && gnb.ln_rows != nullptr;
-  float* lnbuf = (float*)(smem + HALO_BYTES + STAGES * STAGE - 1024);
+  float* lnbuf = (float*)(smem + HALO_BYTES + CV_STAGES * STAGE - 1024);
   if (ln_fold) {
-    if (tid < CV_BM) {
+    if (active && tid < CV_BM) {
       const unsigned m = row_m(tid);
       float rs = 0.f, a = 0.f;
       if (m < M) {
@@ -509,7 +518,7 @@ conv3x3_kernel(const _Float16* __restrict__ x, const _Float16* __restrict__ w, c
 #pragma unroll
       for (int mi = 0; mi < 4; mi++) {
         const unsigned m = m0 + wm * 64 + mi * 16 + (lane & 15);
-        if (m >= M) continue;
+        if (!active || m >= M) continue;
 #pragma unroll
         for (int ni = 0; ni < NI; ni++) {
           const int co = co0 + wn * (BN / 2) + ni * 16 + (lane >> 4) * 4;
@@ -520,7 +529,7 @@ conv3x3_kernel(const _Float16* __restrict__ x, const _Float16* __restrict__ w, c
     return;
   }
   if constexpr (!GEGLU) {
-    if (((geom >> 25) & 1) && !(Cout & 7)) {
+    if ((geom & CV_LDS_EPI) && !(Cout & 7)) {
       // ---- coalesced epilogue through LDS (the stage buffers are free: every wave has passed the loop's last barrier).
       // The accumulator layout gives a lane 4 channels of one pixel = 8-byte stores 32 contiguous bytes apiece (and the
       // same shape for the residual loads): the memory pipe sees eight times the instructions a full-row access needs.
@@ -533,12 +542,13 @@ conv3x3_kernel(const _Float16* __restrict__ x, const _Float16* __restrict__ w, c
       constexpr int RPT = (CV_BM + RPP - 1) / RPP;          // rows per thread
       const int chunk = tid % CH, r0 = tid / CH;
       const int co = co0 + chunk * 8;
-      const bool mine = tid < RPP * CH && co < Cout;
-      // the residual rows this thread will add are requested FIRST (geom bit 29): their HBM latency then overlaps the
-      // accumulator -> LDS staging and its barrier instead of starting after them
+      const bool staged = active && tid < RPP * CH;         // a thread of the row-chunk grid (KG = 2: of group 0)
+      const bool mine = staged && co < Cout;
+      // the residual rows this thread will add are requested FIRST: their HBM latency then overlaps the accumulator -> LDS
+      // staging and its barrier instead of starting after them
       // (the data-gradient + GroupNorm-backward mode has no residual: its early rows are the GroupNorm input it reads instead)
       const _Float16* early_src = residual ? residual : ((chan_stats && gnb.x) ? gnb.x : nullptr);
-      const bool res_early = early_src && ((geom >> 29) & 1);
+      const bool res_early = early_src != nullptr;
       f16x8 rres[RPT];
       if (res_early && mine) {
 #pragma unroll
@@ -548,25 +558,27 @@ conv3x3_kernel(const _Float16* __restrict__ x, const _Float16* __restrict__ w, c
           rres[k] = (row < CV_BM && m < M) ? *(const f16x8*)(early_src + (size_t)m * Cout + co) : (f16x8){0, 0, 0, 0, 0, 0, 0, 0};
         }
       }
+      if (active) {
 #pragma unroll
-      for (int ni = 0; ni < NI; ni++) {
-        const int cl = wn * (BN / 2) + ni * 16 + (lane >> 4) * 4;
-        const f32x4 b4 = (f32x4){(float)bias4[ni][0], (float)bias4[ni][1], (float)bias4[ni][2], (float)bias4[ni][3]};
-        f32x4 s4 = (f32x4){0.f, 0.f, 0.f, 0.f}, t4 = s4;
-        if (ln_fold && co0 + cl < Cout) { s4 = *(const f32x4*)(gnb.ln_s + co0 + cl); t4 = *(const f32x4*)(gnb.ln_t + co0 + cl); }
+        for (int ni = 0; ni < NI; ni++) {
+          const int cl = wn * (BN / 2) + ni * 16 + (lane >> 4) * 4;
+          const f32x4 b4 = (f32x4){(float)bias4[ni][0], (float)bias4[ni][1], (float)bias4[ni][2], (float)bias4[ni][3]};
+          f32x4 s4 = (f32x4){0.f, 0.f, 0.f, 0.f}, t4 = s4;
+          if (ln_fold && co0 + cl < Cout) { s4 = *(const f32x4*)(gnb.ln_s + co0 + cl); t4 = *(const f32x4*)(gnb.ln_t + co0 + cl); }
 #pragma unroll
-        for (int mi = 0; mi < 4; mi++) {
-          const int p = wm * 64 + mi * 16 + (lane & 15);
-          const f32x4 v = acc[ni][mi];
-          f16x4 o;
-          if (ln_fold) {       // rstd (x . W') - rstd mu s + t  (uniform branch; the plain path below is unchanged bit for bit)
-            const float rs = lnbuf[2 * p], a = lnbuf[2 * p + 1];
+          for (int mi = 0; mi < 4; mi++) {
+            const int p = wm * 64 + mi * 16 + (lane & 15);
+            const f32x4 v = acc[ni][mi];
+            f16x4 o;
+            if (ln_fold) {       // rstd (x . W') - rstd mu s + t  (uniform branch; the plain path below is unchanged bit for bit)
+              const float rs = lnbuf[2 * p], a = lnbuf[2 * p + 1];
 #pragma unroll
-            for (int j = 0; j < 4; j++) o[j] = (_Float16)fmaf(rs, v[j], fmaf(a, s4[j], t4[j]));
-          } else {
-            o[0] = (_Float16)(v[0] + b4[0]); o[1] = (_Float16)(v[1] + b4[1]); o[2] = (_Float16)(v[2] + b4[2]); o[3] = (_Float16)(v[3] + b4[3]);
+              for (int j = 0; j < 4; j++) o[j] = (_Float16)fmaf(rs, v[j], fmaf(a, s4[j], t4[j]));
+            } else {
+              o[0] = (_Float16)(v[0] + b4[0]); o[1] = (_Float16)(v[1] + b4[1]); o[2] = (_Float16)(v[2] + b4[2]); o[3] = (_Float16)(v[3] + b4[3]);
+            }
+            *(f16x4*)(smem + p * ROWB + cl * 2) = o;
           }
-          *(f16x4*)(smem + p * ROWB + cl * 2) = o;
         }
       }
       __syncthreads();
@@ -580,7 +592,7 @@ conv3x3_kernel(const _Float16* __restrict__ x, const _Float16* __restrict__ w, c
       // per-channel statistics would use: the two are never requested together), 128 threads then add a row's chunks in order
       float* rowpart = (float*)(smem + CV_BM * ROWB);
       const bool rows_wanted = gnb.rows_out != nullptr && !chan_stats;
-      if (rows_wanted && tid < RPP * CH && !mine) {
+      if (rows_wanted && staged && !mine) {
 #pragma unroll
         for (int k = 0; k < RPT; k++) {
           const int row = r0 + k * RPP;
@@ -627,7 +639,7 @@ conv3x3_kernel(const _Float16* __restrict__ x, const _Float16* __restrict__ w, c
           }
         }
         __syncthreads();
-        if (tid < CV_BM) {
+        if (active && tid < CV_BM) {
           const unsigned m = row_m(tid);
           if (m < M) {
             float S = 0.f, Q = 0.f;
@@ -640,7 +652,7 @@ conv3x3_kernel(const _Float16* __restrict__ x, const _Float16* __restrict__ w, c
       }
       if (chan_stats) {                                      // kernel argument: uniform over the workgroup
         float* part = (float*)(smem + CV_BM * ROWB);         // [RPP][BN][2] behind the tile image (fits: see launch())
-        if (tid < RPP * CH) {
+        if (staged) {
 #pragma unroll
           for (int j = 0; j < 8; j++) {
             part[((r0 * BN) + chunk * 8 + j) * 2] = s8[j];
@@ -648,7 +660,7 @@ conv3x3_kernel(const _Float16* __restrict__ x, const _Float16* __restrict__ w, c
           }
         }
         __syncthreads();
-        if (tid < BN && co0 + tid < Cout) {
+        if (active && tid < BN && co0 + tid < Cout) {
           float S = 0.f, Q = 0.f;
 #pragma unroll
           for (int r = 0; r < RPP; r++) { S += part[(r * BN + tid) * 2]; Q += part[(r * BN + tid) * 2 + 1]; }   // fixed order
@@ -662,7 +674,7 @@ conv3x3_kernel(const _Float16* __restrict__ x, const _Float16* __restrict__ w, c
 #pragma unroll
   for (int mi = 0; mi < 4; mi++) {
     const unsigned m = m0 + wm * 64 + mi * 16 + (lane & 15);
-    if (m >= M) continue;
+    if (!active || m >= M) continue;
     if constexpr (GEGLU) {
 #pragma unroll
       for (int ni = 0; ni < NI / 2; ni++) {
@@ -706,9 +718,9 @@ conv3x3_kernel(const _Float16* __restrict__ x, const _Float16* __restrict__ w, c
 // conv_big_kernel — the same implicit GEMM with a 256-pixel x BN-channel tile (BN = 256 or 128) owned by ONE 8-wave
 // workgroup per CU instead of two (four) independent 128 x 128 workgroups.
 //
-// Why (tools/exp_conv_ablate.py, round 3): in the 128 x 128 kernel the LDS-DMA stream alone takes as long as the LDS-read +
-// MFMA stream alone (each ~70 % of the full kernel; 23 TB/s of L2 -> LDS traffic at 512 -> 512 @ 128^2, two thirds of the
-// aggregate L2 peak), so the two overlap imperfectly and neither can shrink.  A 256 x 256 tile moves HALF the operand
+// Why (timing ablations, round 3: tools/experiments/conv3x3_timing_ablations.diff.txt): in the 128 x 128 kernel the LDS-DMA
+// stream alone takes as long as the LDS-read + MFMA stream alone (each ~70 % of the full kernel; 23 TB/s of L2 -> LDS traffic
+// at 512 -> 512 @ 128^2, two thirds of the aggregate L2 peak), so the two overlap imperfectly and neither can shrink.  A 256 x 256 tile moves HALF the operand
 // bytes per MFMA (64 KB per K step for 64 MFMAs per wave instead of 2 x 32 KB for 2 x 32), and a wave's 128 x 64 output
 // needs 24 fragment reads per 64 MFMAs instead of 16 per 32.  Structure otherwise as above: two LDS stages of a full K
 // step (2 x 64 KB), the DMA of step t + 1 issued before the MFMAs of step t, ONE barrier per K step (64 MFMAs per wave
@@ -927,7 +939,7 @@ conv_big_kernel(const _Float16* __restrict__ x, const _Float16* __restrict__ w, 
   const int co = co0 + chunk * 8;
   const bool mine = r0 < RPP && co < Cout;
   const _Float16* early_src = residual ? residual : ((chan_stats && gnb.x) ? gnb.x : nullptr);
-  const bool res_early = early_src && ((geom >> 29) & 1);
+  const bool res_early = early_src != nullptr;
   float s8[SB][8], q8[SB][8];                             // statistics of the tile's 128-row blocks
 #pragma unroll
   for (int b = 0; b < SB; b++)
@@ -937,7 +949,7 @@ conv_big_kernel(const _Float16* __restrict__ x, const _Float16* __restrict__ w, 
   if (chan_stats && gnb.x && mine) gnb_load(gnb, (int)(m0 / (unsigned)gnb.HW), co, Cout, gl);
 #pragma unroll
   for (int pass = 0; pass < PASSES; pass++) {
-    // the residual rows of this pass are requested before the image is staged (geom bit 29, see conv3x3_kernel)
+    // the residual rows of this pass are requested before the image is staged (see conv3x3_kernel)
     constexpr int RPT = (PROWS + RPP - 1) / RPP;
     constexpr int RPF = RPT / 2;                          // half of them: the register file is full (229 of 256 in the main loop)
     f16x8 rres[RPF];
@@ -1105,23 +1117,42 @@ conv_splitk_reduce_stats_kernel(const float* __restrict__ partial, const _Float1
   }
 }
 
-// Debug / A-B knobs (tools/exp_conv*.py set them through ctypes; -1 = the shape heuristic below decides)
-extern "C" { int gip_dbg_conv_order = -1; int gip_dbg_conv_epilogue = -1; int gip_dbg_conv_ksplit = 0; int gip_dbg_conv_ablate = 0;
-             int gip_dbg_conv_big = -1; int gip_dbg_linear_narrow = -1; int gip_dbg_linear_kg = -1; }
-// same-box A/B of a whole training step (tools/ab_ahds.sh); read once.  (Rounds 3-5 also had GIP_CONV_EPILOGUE / _RES_EARLY / _BIG /
-// _KSPLIT_R2: the per-lane 8-byte epilogue, residual rows requested late, no 256-row tile, the round-2 split-K factor — each measured
-// slower in DESIGN §4c and retired in round 6; the gip_dbg_* knobs above still reach them from tools/exp_conv*.py.)
-static int env_int(const char* name, int dflt) {
-  const char* v = getenv(name);
-  return v && *v ? atoi(v) : dflt;
+// Debug knobs, set through ctypes (the GPU tests force the reference paths with them, tools/exp_*.py compare the paths); -1 = the
+// shape heuristic below decides.  (Rounds 3-5 also had GIP_CONV_EPILOGUE / _RES_EARLY / _BIG / _KSPLIT_R2: the per-lane 8-byte
+// epilogue, residual rows requested late, no 256-row tile, the round-2 split-K factor — each measured slower in DESIGN §4c and retired.)
+extern "C" { int gip_dbg_conv_epilogue = -1; int gip_dbg_conv_big = -1; int gip_dbg_linear_narrow = -1; int gip_dbg_linear_kg = -1; }
+
+// One launch of the implicit GEMM.  The extern "C" entries set the fields they use; a field left at its default is off.
+struct ConvCall {
+  const void* x = nullptr; const void* w = nullptr; const void* bias = nullptr; const void* residual = nullptr; void* out = nullptr;
+  int N = 1, H = 1, W = 1, Cin = 0, Cout = 0;     // H, W: the OUTPUT dims (a GEMM: N = H = 1, W = M)
+  int Hin = 0, Win = 0;                           // the input dims; 0 = the output dims
+  int stride = 1, pad_t = 1, pad_l = 1;
+  int tapsel = 0x1ff;                             // TAPS = 9: taps visited, parity scatter (see conv3x3_kernel)
+  void* workspace = nullptr; size_t workspace_bytes = 0;    // split-K slabs; none = whole-K tiles
+  float* chan_stats = nullptr; int stats_rows = 128;         // per-(row block, channel) statistics of the output
+  GnBwdArgs gnb = {};                             // GroupNorm-backward sums, LayerNorm fold, per-row statistics
+  bool gn_in = false;                             // gnb is the GroupNorm (+ SiLU) of the INPUT (halo kernel only: else returns 1)
+  int batch = 1; long long bs_x = 0, bs_w = 0, bs_o = 0;    // batched GEMM: entries and their strides in elements
+
+  int geom() const { return stride | pad_t << 8 | pad_l << 16; }
+  int hin() const { return Hin ? Hin : H; }
+  int win() const { return Hin ? Win : W; }
+};
+
+// the operands and dimensions, which every entry sets
+static ConvCall conv_call(const void* x, const void* w, const void* bias, const void* residual, void* out, int N, int H, int W, int Cin,
+                          int Cout) {
+  ConvCall c;
+  c.x = x; c.w = w; c.bias = bias; c.residual = residual; c.out = out;
+  c.N = N; c.H = H; c.W = W; c.Cin = Cin; c.Cout = Cout;
+  return c;
 }
 
 template <int BM, int BN, int TAPS>
-static int launch_big(const void* x, const void* w, const void* bias, const void* residual, void* out, int N, int H, int W, int Cin,
-                      int Cout, hipStream_t s, int Hin, int Win, int geom, float* chan_stats, const GnBwdArgs& gnb, int batch = 1,
-                      long long bs_x = 0, long long bs_w = 0, long long bs_o = 0) {
-  const long long M = (long long)N * H * W;
-  const int m_tiles = (int)((M + BM - 1) / BM), n_tiles = (Cout + BN - 1) / BN;
+static int launch_big(const ConvCall& c, hipStream_t s) {
+  const long long M = (long long)c.N * c.H * c.W;
+  const int m_tiles = (int)((M + BM - 1) / BM), n_tiles = (c.Cout + BN - 1) / BN;
   const size_t lds = 2 * ((size_t)BM + (size_t)((BN + 63) / 64) * 64) * 128;
   static bool attr_set = false;
   if (!attr_set) {
@@ -1129,10 +1160,9 @@ static int launch_big(const void* x, const void* w, const void* bias, const void
       return 3;
     attr_set = true;
   }
-  geom |= 1 << 29;                                  // residual rows requested before the epilogue staging
-  hipLaunchKernelGGL((conv_big_kernel<BM, BN, TAPS>), dim3(m_tiles * n_tiles, batch), dim3(CVB_THREADS), lds, s, (const _Float16*)x,
-                     (const _Float16*)w, (const _Float16*)bias, (const _Float16*)residual, (_Float16*)out, N, H, W, Cin, Cout,
-                     m_tiles, n_tiles, Hin, Win, geom, chan_stats, gnb, bs_x, bs_w, bs_o);
+  hipLaunchKernelGGL((conv_big_kernel<BM, BN, TAPS>), dim3(m_tiles * n_tiles, c.batch), dim3(CVB_THREADS), lds, s, (const _Float16*)c.x,
+                     (const _Float16*)c.w, (const _Float16*)c.bias, (const _Float16*)c.residual, (_Float16*)c.out, c.N, c.H, c.W, c.Cin,
+                     c.Cout, m_tiles, n_tiles, c.hin(), c.win(), c.geom(), c.chan_stats, c.gnb, c.bs_x, c.bs_w, c.bs_o);
   return hipGetLastError() == hipSuccess ? 0 : 3;
 }
 
@@ -1156,161 +1186,146 @@ static int big_tile_width(long long M, int Cout) {
   return 0;
 }
 
-static inline bool workspace_is_forced_splitk() { return gip_dbg_conv_ksplit > 0; }      // tools/exp_conv5.py forces a split-K factor
-
-template <int BN, int STAGES, int TAPS, bool GEGLU>
-static int launch(const void* x, const void* w, const void* bias, const void* residual, void* out, int N, int H, int W,
-                  int Cin, int Cout, hipStream_t s, void* workspace = nullptr, size_t workspace_bytes = 0, int Hin = 0, int Win = 0,
-                  int geom = 1 | (1 << 8) | (1 << 16), float* chan_stats = nullptr, const GnBwdArgs* gnb_in = nullptr,
-                  int tapsel = 0x1ff, int stats_rows = 128, int batch = 1, long long bs_x = 0, long long bs_w = 0, long long bs_o = 0,
-                  bool gn_in = false) {
-  // gn_in: *gnb_in describes the GroupNorm (+ SiLU) applied to this convolution's INPUT (halo-resident kernel only: anything else
-  // returns 1 and the caller runs the separate apply pass)
-  GnBwdArgs gnb = {};
-  if (gnb_in) gnb = *gnb_in;
-  if (Hin == 0) { Hin = H; Win = W; }
+template <int BN, int TAPS, bool GEGLU>
+static int launch(const ConvCall& c, hipStream_t s) {
+  const GnBwdArgs& gnb = c.gnb;
+  const int N = c.N, H = c.H, W = c.W, Cin = c.Cin, Cout = c.Cout, Hin = c.hin(), Win = c.win(), tapsel = c.tapsel;
   const long long M = (long long)N * H * W;
-  if (batch > 1 && (TAPS != 1 || GEGLU || workspace || chan_stats || gnb_in)) return 1;
+  if (c.batch > 1 && (TAPS != 1 || GEGLU || c.workspace || c.chan_stats || c.gn_in || gnb.x || gnb.ln_rows || gnb.rows_out)) return 1;
   if constexpr (!GEGLU) {
-    if (!(Cout & 7) && batch == 1 && !gn_in) {
+    if (!(Cout & 7) && c.batch == 1 && !c.gn_in) {
       const int bw = big_tile_width(M, Cout);
-      if (bw == 256 && !(gnb.x && gnb.HW % CVB_BM) && tapsel == 0x1ff && !gnb.ln_rows && !gnb.rows_out)
-        return launch_big<256, 256, TAPS>(x, w, bias, residual, out, N, H, W, Cin, Cout, s, Hin, Win, geom, chan_stats, gnb);
-      {
-        // a 384-row tile straddles samples (HW % 384 != 0): fine for the implicit GEMM and for the 128-row statistics blocks, not for
-        // the per-sample constants of the GroupNorm-backward sums (gnb.x) — those layers keep the 128-row kernel.  As a GEMM
-        // (TAPS = 1) only with a K loop long enough to amortise the one-workgroup-per-CU prologue / epilogue (K >= 1280: ff_out).
-        // Same-box A/B of the whole step, four runs per setting (round 6): 33.55 -> 33.48 ms with the 3x3 layers, -> 33.35 with ff_out too
-        if (bw == 160 && !gnb.x && tapsel == 0x1ff && !gnb.ln_rows && !gnb.rows_out && !workspace_is_forced_splitk() &&
-            (TAPS == 9 || Cin >= 1280))
-          return launch_big<384, 160, TAPS>(x, w, bias, residual, out, N, H, W, Cin, Cout, s, Hin, Win, geom, chan_stats, gnb);
-      }
+      if (bw == 256 && !(gnb.x && gnb.HW % CVB_BM) && tapsel == 0x1ff && !gnb.ln_rows && !gnb.rows_out) return launch_big<256, 256, TAPS>(c, s);
+      // a 384-row tile straddles samples (HW % 384 != 0): fine for the implicit GEMM and for the 128-row statistics blocks, not for
+      // the per-sample constants of the GroupNorm-backward sums (gnb.x) — those layers keep the 128-row kernel.  As a GEMM
+      // (TAPS = 1) only with a K loop long enough to amortise the one-workgroup-per-CU prologue / epilogue (K >= 1280: ff_out).
+      // Same-box A/B of the whole step, four runs per setting (round 6): 33.55 -> 33.48 ms with the 3x3 layers, -> 33.35 with ff_out too
+      if (bw == 160 && !gnb.x && tapsel == 0x1ff && !gnb.ln_rows && !gnb.rows_out && (TAPS == 9 || Cin >= 1280))
+        return launch_big<384, 160, TAPS>(c, s);
     }
   }
   const int m_tiles = (int)((M + CV_BM - 1) / CV_BM), n_tiles = (Cout + (GEGLU ? BN / 2 : BN) - 1) / (GEGLU ? BN / 2 : BN);
   if constexpr (BN == 128 && TAPS == 9 && !GEGLU) {
     // halo-resident pixel tile (see conv3x3_kernel): Cin = 128, plain 3x3 / stride 1 / pad 1, whole-K tiles that fill the chip
-    static const int env_halo = env_int("GIP_CONV_HALO", 1);
-    if (env_halo && gip_dbg_conv_epilogue != 0 && gip_dbg_conv_ksplit <= 0 && Cin == 128 && (geom & 0xffffff) == (1 | (1 << 8) | (1 << 16)) &&
-        tapsel == 0x1ff && !(H & 7) && !(W & 15) && Hin == H && Win == W && !(Cout & 7) && stats_rows == 128 &&
-        (long long)m_tiles * n_tiles >= 256 && !(gnb.x && gnb.HW != H * W)) {
-      constexpr size_t lds_h = 2 * (size_t)CVH_KC_BYTES + STAGES * (size_t)BN * 128;
+    if (gip_dbg_conv_epilogue != 0 && Cin == 128 && c.stride == 1 && c.pad_t == 1 && c.pad_l == 1 && tapsel == 0x1ff && !(H & 7) &&
+        !(W & 15) && Hin == H && Win == W && !(Cout & 7) && c.stats_rows == 128 && (long long)m_tiles * n_tiles >= 256 &&
+        !(gnb.x && gnb.HW != H * W)) {
+      constexpr size_t lds_h = 2 * (size_t)CVH_KC_BYTES + CV_STAGES * (size_t)BN * 128;
       static_assert((size_t)CV_BM * (BN * 2 + 16) + (size_t)(CV_THREADS / (BN / 8)) * BN * 8 <= lds_h, "epilogue image must fit");
       static bool attr_h = false;
       if (!attr_h) {
-        if (hipFuncSetAttribute((const void*)conv3x3_kernel<BN, STAGES, TAPS, GEGLU, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+        if (hipFuncSetAttribute((const void*)conv3x3_kernel<BN, TAPS, GEGLU, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)lds_h) != hipSuccess)
           return 3;
         attr_h = true;
       }
-      const int geom_h = geom | (1 << 25) | ((gip_dbg_conv_ablate & 7) << 26) | (1 << 29) | ((gn_in ? 1 : 0) << 30);
-      hipLaunchKernelGGL((conv3x3_kernel<BN, STAGES, TAPS, GEGLU, true>), dim3(m_tiles * n_tiles), dim3(CV_THREADS), lds_h, s,
-                         (const _Float16*)x, (const _Float16*)w, (const _Float16*)bias, (const _Float16*)residual, (_Float16*)out,
-                         N, H, W, Cin, Cout, m_tiles, n_tiles, 1, (float*)nullptr, Hin, Win, geom_h, chan_stats, gnb, tapsel);
+      const int geom_h = c.geom() | CV_LDS_EPI | (c.gn_in ? CV_GN_IN : 0);
+      hipLaunchKernelGGL((conv3x3_kernel<BN, TAPS, GEGLU, true>), dim3(m_tiles * n_tiles), dim3(CV_THREADS), lds_h, s,
+                         (const _Float16*)c.x, (const _Float16*)c.w, (const _Float16*)c.bias, (const _Float16*)c.residual, (_Float16*)c.out,
+                         N, H, W, Cin, Cout, m_tiles, n_tiles, 1, (float*)nullptr, Hin, Win, geom_h, c.chan_stats, gnb, tapsel);
       return hipGetLastError() == hipSuccess ? 0 : 3;
     }
   }
-  if (gn_in) return 1;
-  const size_t lds = STAGES * (size_t)(CV_BM + BN) * 128;
-  static_assert((size_t)CV_BM * (BN * 2 + 16) + (size_t)(CV_THREADS / (BN / 8)) * BN * 8 <= STAGES * (size_t)(CV_BM + BN) * 128,
+  if (c.gn_in) return 1;
+  const size_t lds = CV_STAGES * (size_t)(CV_BM + BN) * 128;
+  static_assert((size_t)CV_BM * (BN * 2 + 16) + (size_t)(CV_THREADS / (BN / 8)) * BN * 8 <= CV_STAGES * (size_t)(CV_BM + BN) * 128,
                 "epilogue tile image + statistics partials must fit in the stage buffers");
   static bool attr_set = false;
   if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)conv3x3_kernel<BN, STAGES, TAPS, GEGLU>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)lds) != hipSuccess)
+    if (hipFuncSetAttribute((const void*)conv3x3_kernel<BN, TAPS, GEGLU>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
       return 3;
     attr_set = true;
   }
   // split-K when the output tiles cannot fill the chip and a workspace was handed in: the largest factor that still
   // fits ONE round of 2 workgroups per CU (240 tiles: 2 -> 480 workgroups; 3 -> 720 = 1.4 rounds measured 16 % slower;
-  // 60 tiles: 8; tools/exp_conv5.py)
+  // 60 tiles: 8)
   int ksplit = 1;
   const int tiles = m_tiles * n_tiles, KT = (TAPS == 9 ? __builtin_popcount(tapsel & 0x1ff) : TAPS) * (Cin / CV_BK);
-  if (!GEGLU && workspace && tiles < 256 && !((tapsel >> 11) & 1)) {
+  if (!GEGLU && c.workspace && tiles < 256 && !((tapsel >> 11) & 1)) {
     ksplit = 512 / tiles;
     if (ksplit > KT / 8) ksplit = KT / 8;
     if (ksplit > 16) ksplit = 16;
-    while (ksplit > 1 && (size_t)ksplit * M * Cout * sizeof(float) > workspace_bytes) ksplit--;
+    while (ksplit > 1 && (size_t)ksplit * M * Cout * sizeof(float) > c.workspace_bytes) ksplit--;
     if (ksplit < 2) ksplit = 1;
   }
-  if (gip_dbg_conv_ksplit > 0 && !GEGLU && workspace) {
-    ksplit = gip_dbg_conv_ksplit;
-    while (ksplit > 1 && ((size_t)ksplit * M * Cout * sizeof(float) > workspace_bytes || ksplit > KT)) ksplit--;
-  }
   // tile order: n-major only where the pixel count is tiny against the weights (the 8x8 level: 6 pixel blocks, 30-60 MB
-  // of weights: 55 -> 50 us); measured slower everywhere else, also at 16x16 (tools/exp_conv5.py)
-  int nmajor = m_tiles <= 8 && n_tiles > 1 ? 1 : 0;
-  if (gip_dbg_conv_order >= 0) nmajor = gip_dbg_conv_order;
-  int lds_epi = 1;
-  if (gip_dbg_conv_epilogue >= 0) lds_epi = gip_dbg_conv_epilogue;
-  const bool stats_in_reduce = chan_stats && ksplit > 1 && !gnb.x;      // split-K: the reduce kernel makes the statistics
-  if (chan_stats && !stats_in_reduce) {            // statistics come out of the LDS epilogue of whole-K tiles (128-row blocks)
-    if (GEGLU || (Cout & 7) || stats_rows != 128) return 1;
+  // of weights: 55 -> 50 us); measured slower everywhere else, also at 16x16
+  const bool nmajor = m_tiles <= 8 && n_tiles > 1;
+  bool lds_epi = gip_dbg_conv_epilogue != 0;
+  const bool stats_in_reduce = c.chan_stats && ksplit > 1 && !gnb.x;      // split-K: the reduce kernel makes the statistics
+  if (c.chan_stats && !stats_in_reduce) {          // statistics come out of the LDS epilogue of whole-K tiles (128-row blocks)
+    if (GEGLU || (Cout & 7) || c.stats_rows != 128) return 1;
     ksplit = 1;
-    lds_epi = 1;
+    lds_epi = true;
   }
   if (gnb.ln_rows || gnb.rows_out) {               // LayerNorm fold / row statistics: whole-K tiles with the LDS epilogue
-    if (TAPS != 1 || ksplit != 1 || (!GEGLU && (Cout & 7)) || (gnb.rows_out && (GEGLU || chan_stats))) return 1;
-    lds_epi = 1;
+    if (TAPS != 1 || ksplit != 1 || (!GEGLU && (Cout & 7)) || (gnb.rows_out && (GEGLU || c.chan_stats))) return 1;
+    lds_epi = true;
   }
-  geom |= (nmajor << 24) | (lds_epi << 25) | ((gip_dbg_conv_ablate & 7) << 26) | (1 << 29);   // bits 26-28: timing ablations (WRONG results)
+  const int geom = c.geom() | (nmajor ? CV_NMAJOR : 0) | (lds_epi ? CV_LDS_EPI : 0);
   const int classes = (tapsel >> 12) & 1 ? 4 : 1;
   if constexpr (TAPS == 1 && !GEGLU) {
     // two K groups per workgroup (KG = 2, see conv3x3_kernel) where the grid leaves at most one workgroup per CU and the K loop is long
     // enough to split: the GEMMs of the 8 x 8 level at batch 12, most GEMMs of a 1-view shard (batch 3)
-    const bool kg2 = gip_dbg_linear_kg >= 0 ? gip_dbg_linear_kg != 0 : true;
-    if (kg2 && ksplit == 1 && batch == 1 && tiles <= 256 && KT >= 8 && lds_epi) {
-      constexpr size_t lds2 = 2 * STAGES * (size_t)(CV_BM + BN) * 128;
+    if (gip_dbg_linear_kg != 0 && ksplit == 1 && c.batch == 1 && tiles <= 256 && KT >= 8 && lds_epi) {
+      constexpr size_t lds2 = 2 * CV_STAGES * (size_t)(CV_BM + BN) * 128;
       static_assert((size_t)(BN / 32) * 4 * CV_THREADS * 16 <= lds2, "the handed-over accumulators must fit the stage buffers");
       static bool attr2 = false;
       if (!attr2) {
-        if (hipFuncSetAttribute((const void*)conv3x3_kernel<BN, STAGES, TAPS, GEGLU, false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize,
+        if (hipFuncSetAttribute((const void*)conv3x3_kernel<BN, TAPS, GEGLU, false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)lds2) != hipSuccess)
           return 3;
         attr2 = true;
       }
-      hipLaunchKernelGGL((conv3x3_kernel<BN, STAGES, TAPS, GEGLU, false, 2>), dim3(tiles), dim3(CV_THREADS * 2), lds2, s,
-                         (const _Float16*)x, (const _Float16*)w, (const _Float16*)bias, (const _Float16*)residual, (_Float16*)out,
-                         N, H, W, Cin, Cout, m_tiles, n_tiles, 1, (float*)nullptr, Hin, Win, geom, chan_stats, gnb, tapsel, bs_x, bs_w, bs_o);
+      hipLaunchKernelGGL((conv3x3_kernel<BN, TAPS, GEGLU, false, 2>), dim3(tiles), dim3(CV_THREADS * 2), lds2, s,
+                         (const _Float16*)c.x, (const _Float16*)c.w, (const _Float16*)c.bias, (const _Float16*)c.residual, (_Float16*)c.out,
+                         N, H, W, Cin, Cout, m_tiles, n_tiles, 1, (float*)nullptr, Hin, Win, geom, c.chan_stats, gnb, tapsel, c.bs_x, c.bs_w,
+                         c.bs_o);
       return hipGetLastError() == hipSuccess ? 0 : 3;
     }
   }
-  hipLaunchKernelGGL((conv3x3_kernel<BN, STAGES, TAPS, GEGLU>), dim3(tiles * ksplit * classes, batch), dim3(CV_THREADS), lds, s,
-                     (const _Float16*)x, (const _Float16*)w, (const _Float16*)bias, (const _Float16*)residual, (_Float16*)out,
-                     N, H, W, Cin, Cout, m_tiles, n_tiles, ksplit, (float*)workspace, Hin, Win, geom,
-                     stats_in_reduce ? nullptr : chan_stats, gnb, tapsel, bs_x, bs_w, bs_o);
+  hipLaunchKernelGGL((conv3x3_kernel<BN, TAPS, GEGLU>), dim3(tiles * ksplit * classes, c.batch), dim3(CV_THREADS), lds, s,
+                     (const _Float16*)c.x, (const _Float16*)c.w, (const _Float16*)c.bias, (const _Float16*)c.residual, (_Float16*)c.out,
+                     N, H, W, Cin, Cout, m_tiles, n_tiles, ksplit, (float*)c.workspace, Hin, Win, geom,
+                     stats_in_reduce ? nullptr : c.chan_stats, gnb, tapsel, c.bs_x, c.bs_w, c.bs_o);
   if (stats_in_reduce) {
-    if ((Cout & 3) || M % stats_rows) return 1;
-    const dim3 grid((unsigned)(M / stats_rows), (unsigned)((Cout + 63) / 64));
-    if (stats_rows == 128)
-      hipLaunchKernelGGL((conv_splitk_reduce_stats_kernel<128>), grid, dim3(256), 0, s, (const float*)workspace, (const _Float16*)bias,
-                         (const _Float16*)residual, (_Float16*)out, chan_stats, (unsigned)M, Cout, ksplit, (size_t)M * Cout);
-    else if (stats_rows == 64)
-      hipLaunchKernelGGL((conv_splitk_reduce_stats_kernel<64>), grid, dim3(256), 0, s, (const float*)workspace, (const _Float16*)bias,
-                         (const _Float16*)residual, (_Float16*)out, chan_stats, (unsigned)M, Cout, ksplit, (size_t)M * Cout);
+    if ((Cout & 3) || M % c.stats_rows) return 1;
+    const dim3 grid((unsigned)(M / c.stats_rows), (unsigned)((Cout + 63) / 64));
+    if (c.stats_rows == 128)
+      hipLaunchKernelGGL((conv_splitk_reduce_stats_kernel<128>), grid, dim3(256), 0, s, (const float*)c.workspace, (const _Float16*)c.bias,
+                         (const _Float16*)c.residual, (_Float16*)c.out, c.chan_stats, (unsigned)M, Cout, ksplit, (size_t)M * Cout);
+    else if (c.stats_rows == 64)
+      hipLaunchKernelGGL((conv_splitk_reduce_stats_kernel<64>), grid, dim3(256), 0, s, (const float*)c.workspace, (const _Float16*)c.bias,
+                         (const _Float16*)c.residual, (_Float16*)c.out, c.chan_stats, (unsigned)M, Cout, ksplit, (size_t)M * Cout);
     else
       return 1;
   } else if (ksplit > 1) {
     const unsigned n4 = (unsigned)(M * Cout / 4);
-    hipLaunchKernelGGL(conv_splitk_reduce_kernel, dim3((n4 + 255) / 256), dim3(256), 0, s, (const float*)workspace,
-                       (const _Float16*)bias, (const _Float16*)residual, (_Float16*)out, n4, Cout / 4, ksplit, (size_t)M * Cout);
+    hipLaunchKernelGGL(conv_splitk_reduce_kernel, dim3((n4 + 255) / 256), dim3(256), 0, s, (const float*)c.workspace,
+                       (const _Float16*)c.bias, (const _Float16*)c.residual, (_Float16*)c.out, n4, Cout / 4, ksplit, (size_t)M * Cout);
   }
   return hipGetLastError() == hipSuccess ? 0 : 3;
 }
 
+// channel-tile width of a 3x3 convolution (and of a batched GEMM): 160 where Cout is a multiple of 160 but not of 128 (320, 960),
+// 128 otherwise
+static int wide_width(int Cout) { return (Cout % 160 == 0 && Cout % 128 != 0) ? 160 : 128; }
+template <class F>
+static int with_conv_width(int Cout, F f) {
+  return wide_width(Cout) == 160 ? f(std::integral_constant<int, 160>{}) : f(std::integral_constant<int, 128>{});
+}
+
 // GEMMs whose 128 x 128 (160) tiles leave most CUs with at most ONE workgroup run on 128 x 64 tiles: twice the workgroups, and a
 // lone workgroup's K step (8 LDS-DMA instructions per wave + 32 MFMAs, in series inside the wave: tools/experiments/
-// conv3x3_four_stage.diff.txt) becomes 6 + 16.  GIP_LINEAR_NARROW = the largest 128-wide grid that takes the narrow tile (0: off).
+// conv3x3_four_stage.diff.txt) becomes 6 + 16.  Up to 256 tiles of 128 x 128 (gip_dbg_linear_narrow: another limit, 0 = off).
 static bool narrow_tiles(long long M, int Nout, int bn) {
-  static const int env_narrow = env_int("GIP_LINEAR_NARROW", 256);
-  const int lim = gip_dbg_linear_narrow >= 0 ? gip_dbg_linear_narrow : env_narrow;
+  const int lim = gip_dbg_linear_narrow >= 0 ? gip_dbg_linear_narrow : 256;
   return lim > 0 && !(Nout & 63) && ((M + CV_BM - 1) / CV_BM) * ((Nout + bn - 1) / bn) <= lim;
 }
 
-// channel-tile width of the plain (no GEGLU) linear for an [M, Nout] output: 160 where Nout is a multiple of 160 but not of 128
-// (320, 960), 128 otherwise, 64 on small grids (narrow_tiles)
+// channel-tile width of the plain (no GEGLU) linear for an [M, Nout] output: wide_width, or 64 on small grids (narrow_tiles)
 static int linear_width(long long M, int Nout) {
-  const int wide = (Nout % 160 == 0 && Nout % 128 != 0) ? 160 : 128;
+  const int wide = wide_width(Nout);
   return narrow_tiles(M, Nout, wide) ? 64 : wide;
 }
 template <class F>
@@ -1331,10 +1346,9 @@ extern "C" int gip_conv3x3_nhwc_f16(const void* x, const void* w, const void* bi
                                     size_t workspace_bytes, void* stream) {
   if (!x || !w || !out || N < 1 || H < 1 || W < 1 || Cin < CV_BK || Cin % CV_BK || Cout < 4 || (Cout & 3)) return 1;
   if (!fits32((long long)N * H * W, Cin, Cout, Cout, 9)) return 1;   // 32-bit byte offsets
-  hipStream_t s = (hipStream_t)stream;
-  const bool wide = Cout % 160 == 0 && Cout % 128 != 0;
-  return wide ? launch<160, 2, 9, false>(x, w, bias, residual, out, N, H, W, Cin, Cout, s, workspace, workspace_bytes)
-              : launch<128, 2, 9, false>(x, w, bias, residual, out, N, H, W, Cin, Cout, s, workspace, workspace_bytes);
+  ConvCall c = conv_call(x, w, bias, residual, out, N, H, W, Cin, Cout);
+  c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+  return with_conv_width(Cout, [&](auto bn) { return launch<decltype(bn)::value, 9, false>(c, (hipStream_t)stream); });
 }
 
 extern "C" int gip_conv3x3_stats_nhwc_f16(const void* x, const void* w, const void* bias, const void* residual, void* out,
@@ -1342,11 +1356,9 @@ extern "C" int gip_conv3x3_stats_nhwc_f16(const void* x, const void* w, const vo
                                           void* stream) {
   if (!x || !w || !out || !chan_stats || N < 1 || H < 1 || W < 1 || Cin < CV_BK || Cin % CV_BK || Cout < 8 || (Cout & 7)) return 1;
   if (!fits32((long long)N * H * W, Cin, Cout, Cout, 9)) return 1;
-  hipStream_t s = (hipStream_t)stream;
-  const bool wide = Cout % 160 == 0 && Cout % 128 != 0;
-  const int geom = 1 | (1 << 8) | (1 << 16);
-  return wide ? launch<160, 2, 9, false>(x, w, bias, residual, out, N, H, W, Cin, Cout, s, nullptr, 0, 0, 0, geom, chan_stats)
-              : launch<128, 2, 9, false>(x, w, bias, residual, out, N, H, W, Cin, Cout, s, nullptr, 0, 0, 0, geom, chan_stats);
+  ConvCall c = conv_call(x, w, bias, residual, out, N, H, W, Cin, Cout);
+  c.chan_stats = chan_stats;
+  return with_conv_width(Cout, [&](auto bn) { return launch<decltype(bn)::value, 9, false>(c, (hipStream_t)stream); });
 }
 
 extern "C" int gip_conv3x3_stats_ws_nhwc_f16(const void* x, const void* w, const void* bias, const void* residual, void* out,
@@ -1355,13 +1367,10 @@ extern "C" int gip_conv3x3_stats_ws_nhwc_f16(const void* x, const void* w, const
   if (!x || !w || !out || !chan_stats || N < 1 || H < 1 || W < 1 || Cin < CV_BK || Cin % CV_BK || Cout < 8 || (Cout & 7)) return 1;
   if ((stats_rows != 128 && stats_rows != 64) || ((long long)H * W) % stats_rows) return 1;
   if (!fits32((long long)N * H * W, Cin, Cout, Cout, 9)) return 1;
-  hipStream_t s = (hipStream_t)stream;
-  const bool wide = Cout % 160 == 0 && Cout % 128 != 0;
-  const int geom = 1 | (1 << 8) | (1 << 16);
-  return wide ? launch<160, 2, 9, false>(x, w, bias, residual, out, N, H, W, Cin, Cout, s, workspace, workspace_bytes, 0, 0, geom, chan_stats,
-                                         nullptr, 0x1ff, stats_rows)
-              : launch<128, 2, 9, false>(x, w, bias, residual, out, N, H, W, Cin, Cout, s, workspace, workspace_bytes, 0, 0, geom, chan_stats,
-                                         nullptr, 0x1ff, stats_rows);
+  ConvCall c = conv_call(x, w, bias, residual, out, N, H, W, Cin, Cout);
+  c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+  c.chan_stats = chan_stats; c.stats_rows = stats_rows;
+  return with_conv_width(Cout, [&](auto bn) { return launch<decltype(bn)::value, 9, false>(c, (hipStream_t)stream); });
 }
 
 extern "C" int gip_conv3x3_gnbwd_nhwc_f16(const void* dy_in, const void* w, void* out, int32_t N, int32_t H, int32_t W, int32_t Cin,
@@ -1372,25 +1381,21 @@ extern "C" int gip_conv3x3_gnbwd_nhwc_f16(const void* dy_in, const void* w, void
       Cin % CV_BK || Cout < 8 || (Cout & 7) || G < 1 || Cout % G || ((long long)H * W) % CV_BM)
     return 1;
   if (!fits32((long long)N * H * W, Cin, Cout, Cout, 9)) return 1;
-  GnBwdArgs g = {};
+  ConvCall c = conv_call(dy_in, w, nullptr, nullptr, out, N, H, W, Cin, Cout);
+  c.chan_stats = chan_sums;
+  GnBwdArgs& g = c.gnb;
   g.x = (const _Float16*)gn_x; g.gamma = (const _Float16*)gamma; g.beta = (const _Float16*)beta; g.addend = (const _Float16*)addend;
   g.mean = mean; g.rstd = rstd; g.G = G; g.silu = apply_silu; g.addend_stride = addend_stride; g.HW = H * W;
-  hipStream_t s = (hipStream_t)stream;
-  const bool wide = Cout % 160 == 0 && Cout % 128 != 0;
-  const int geom = 1 | (1 << 8) | (1 << 16);
-  return wide ? launch<160, 2, 9, false>(dy_in, w, nullptr, nullptr, out, N, H, W, Cin, Cout, s, nullptr, 0, 0, 0, geom, chan_sums, &g)
-              : launch<128, 2, 9, false>(dy_in, w, nullptr, nullptr, out, N, H, W, Cin, Cout, s, nullptr, 0, 0, 0, geom, chan_sums, &g);
+  return with_conv_width(Cout, [&](auto bn) { return launch<decltype(bn)::value, 9, false>(c, (hipStream_t)stream); });
 }
 
 extern "C" int gip_linear_stats_f16(const void* x, const void* w, const void* bias, const void* residual, void* out, int64_t M,
                                     int32_t K, int32_t Nout, float* chan_stats, void* stream) {
   if (!x || !w || !out || !chan_stats || M < 1 || M >= (1ll << 31) || K < CV_BK || K % CV_BK || Nout < 8 || (Nout & 7)) return 1;
   if (!fits32(M, K, Nout, Nout, 1)) return 1;
-  hipStream_t s = (hipStream_t)stream;
-  const int geom = 1 | (1 << 8) | (1 << 16);
-  return with_linear_width(M, Nout, [&](auto bn) {
-    return launch<decltype(bn)::value, 2, 1, false>(x, w, bias, residual, out, 1, 1, (int)M, K, Nout, s, nullptr, 0, 0, 0, geom, chan_stats);
-  });
+  ConvCall c = conv_call(x, w, bias, residual, out, 1, 1, (int)M, K, Nout);
+  c.chan_stats = chan_stats;
+  return with_linear_width(M, Nout, [&](auto bn) { return launch<decltype(bn)::value, 1, false>(c, (hipStream_t)stream); });
 }
 
 // Number of per-row partial sums a [M, Nout] output of the linear kernel carries in rows_out (= its channel tiles).
@@ -1405,13 +1410,9 @@ extern "C" int gip_linear_rows_f16(const void* x, const void* w, const void* bia
                                    int32_t K, int32_t Nout, float* rows_out, void* stream) {
   if (!x || !w || !out || !rows_out || M < 1 || M >= (1ll << 31) || K < CV_BK || K % CV_BK || Nout < 8 || (Nout & 7)) return 1;
   if (!fits32(M, K, Nout, Nout, 1)) return 1;
-  GnBwdArgs g = {};
-  g.rows_out = rows_out;
-  hipStream_t s = (hipStream_t)stream;
-  const int geom = 1 | (1 << 8) | (1 << 16);
-  return with_linear_width(M, Nout, [&](auto bn) {
-    return launch<decltype(bn)::value, 2, 1, false>(x, w, bias, residual, out, 1, 1, (int)M, K, Nout, s, nullptr, 0, 0, 0, geom, nullptr, &g);
-  });
+  ConvCall c = conv_call(x, w, bias, residual, out, 1, 1, (int)M, K, Nout);
+  c.gnb.rows_out = rows_out;
+  return with_linear_width(M, Nout, [&](auto bn) { return launch<decltype(bn)::value, 1, false>(c, (hipStream_t)stream); });
 }
 
 // LayerNorm(x) W^T + b (optionally GEGLU of it) WITHOUT a LayerNorm pass: x is read raw, `wg` = W * gamma (half), s_n = sum_k wg[n][k],
@@ -1424,14 +1425,12 @@ extern "C" int gip_linear_ln_f16(const void* x, const void* wg, const float* s_v
     return 1;
   if (geglu && (Nout % 64)) return 1;
   if (!fits32(M, K, geglu ? 2 * Nout : Nout, geglu ? 2 * Nout : Nout, 1)) return 1;
-  GnBwdArgs g = {};
+  ConvCall c = conv_call(x, wg, nullptr, nullptr, out, 1, 1, (int)M, K, Nout);
+  GnBwdArgs& g = c.gnb;
   g.ln_rows = ln_rows; g.ln_s = s_vec; g.ln_t = t_vec; g.ln_parts = ln_parts; g.ln_inv_c = 1.0f / (float)K; g.ln_eps = eps;
   hipStream_t s = (hipStream_t)stream;
-  const int geom = 1 | (1 << 8) | (1 << 16);
-  if (geglu) return launch<128, 2, 1, true>(x, wg, nullptr, nullptr, out, 1, 1, (int)M, K, Nout, s, nullptr, 0, 0, 0, geom, nullptr, &g);
-  return with_linear_width(M, Nout, [&](auto bn) {
-    return launch<decltype(bn)::value, 2, 1, false>(x, wg, nullptr, nullptr, out, 1, 1, (int)M, K, Nout, s, nullptr, 0, 0, 0, geom, nullptr, &g);
-  });
+  if (geglu) return launch<128, 1, true>(c, s);
+  return with_linear_width(M, Nout, [&](auto bn) { return launch<decltype(bn)::value, 1, false>(c, s); });
 }
 
 extern "C" int gip_conv3x3s2_nhwc_f16(const void* x, const void* w, const void* bias, void* out, int32_t N, int32_t Hin,
@@ -1441,11 +1440,10 @@ extern "C" int gip_conv3x3s2_nhwc_f16(const void* x, const void* w, const void* 
       (Cout & 3) || pad_top < 0 || pad_top > 1 || pad_left < 0 || pad_left > 1)
     return 1;
   if (!fits32((long long)N * Hin * Win, Cin, Cout, Cout, 9)) return 1;
-  const int H = Hin / 2, W = Win / 2, geom = 2 | (pad_top << 8) | (pad_left << 16);
-  hipStream_t s = (hipStream_t)stream;
-  const bool wide = Cout % 160 == 0 && Cout % 128 != 0;
-  return wide ? launch<160, 2, 9, false>(x, w, bias, nullptr, out, N, H, W, Cin, Cout, s, workspace, workspace_bytes, Hin, Win, geom)
-              : launch<128, 2, 9, false>(x, w, bias, nullptr, out, N, H, W, Cin, Cout, s, workspace, workspace_bytes, Hin, Win, geom);
+  ConvCall c = conv_call(x, w, bias, nullptr, out, N, Hin / 2, Win / 2, Cin, Cout);
+  c.Hin = Hin; c.Win = Win; c.stride = 2; c.pad_t = pad_top; c.pad_l = pad_left;
+  c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+  return with_conv_width(Cout, [&](auto bn) { return launch<decltype(bn)::value, 9, false>(c, (hipStream_t)stream); });
 }
 
 // The same stride-2 convolution whose epilogue also leaves the NEXT GroupNorm's statistics (per 128 output pixels and channel,
@@ -1457,12 +1455,11 @@ extern "C" int gip_conv3x3s2_stats_nhwc_f16(const void* x, const void* w, const 
       Cout < 8 || (Cout & 7) || pad_top < 0 || pad_top > 1 || pad_left < 0 || pad_left > 1)
     return 1;
   if (!fits32((long long)N * Hin * Win, Cin, Cout, Cout, 9)) return 1;
-  const int H = Hin / 2, W = Win / 2, geom = 2 | (pad_top << 8) | (pad_left << 16);
-  if (((long long)H * W) % 128) return 1;
-  hipStream_t s = (hipStream_t)stream;
-  const bool wide = Cout % 160 == 0 && Cout % 128 != 0;
-  return wide ? launch<160, 2, 9, false>(x, w, bias, nullptr, out, N, H, W, Cin, Cout, s, nullptr, 0, Hin, Win, geom, chan_stats)
-              : launch<128, 2, 9, false>(x, w, bias, nullptr, out, N, H, W, Cin, Cout, s, nullptr, 0, Hin, Win, geom, chan_stats);
+  if (((long long)(Hin / 2) * (Win / 2)) % 128) return 1;
+  ConvCall c = conv_call(x, w, bias, nullptr, out, N, Hin / 2, Win / 2, Cin, Cout);
+  c.Hin = Hin; c.Win = Win; c.stride = 2; c.pad_t = pad_top; c.pad_l = pad_left;
+  c.chan_stats = chan_stats;
+  return with_conv_width(Cout, [&](auto bn) { return launch<decltype(bn)::value, 9, false>(c, (hipStream_t)stream); });
 }
 
 // Data gradient of the 3x3 / stride 2 convolution y[oy][ox] = sum x[2 oy + ky][2 ox + kx] w[ky][kx] (input zero beyond its
@@ -1475,12 +1472,9 @@ extern "C" int gip_conv3x3s2_dgrad_nhwc_f16(const void* dy, const void* wt4, voi
                                             int32_t Cin, int32_t Cout, void* stream) {
   if (!dy || !wt4 || !dx || N < 1 || Ho < 1 || Wo < 1 || Cin < CV_BK || Cin % CV_BK || Cout < 8 || (Cout & 7)) return 1;
   if (!fits32((long long)N * Ho * Wo * 4, Cin, Cout, Cout, 9)) return 1;
-  hipStream_t s = (hipStream_t)stream;
-  const bool wide = Cout % 160 == 0 && Cout % 128 != 0;
-  const int geom = 1 | (1 << 8) | (1 << 16);
-  const int tapsel = 0x1ff | (1 << 11) | (1 << 12);          // four classes in one launch, the stride-2 data-gradient tap sets
-  return wide ? launch<160, 2, 9, false>(dy, wt4, nullptr, nullptr, dx, N, Ho, Wo, Cin, Cout, s, nullptr, 0, 0, 0, geom, nullptr, nullptr, tapsel)
-              : launch<128, 2, 9, false>(dy, wt4, nullptr, nullptr, dx, N, Ho, Wo, Cin, Cout, s, nullptr, 0, 0, 0, geom, nullptr, nullptr, tapsel);
+  ConvCall c = conv_call(dy, wt4, nullptr, nullptr, dx, N, Ho, Wo, Cin, Cout);
+  c.tapsel = 0x1ff | (1 << 11) | (1 << 12);          // four classes in one launch, the stride-2 data-gradient tap sets
+  return with_conv_width(Cout, [&](auto bn) { return launch<decltype(bn)::value, 9, false>(c, (hipStream_t)stream); });
 }
 
 // nearest-neighbour 2x upsampling followed by the 3x3 / pad 1 convolution (diffusers Upsample2D) WITHOUT the upsampled tensor:
@@ -1492,12 +1486,9 @@ extern "C" int gip_upsample2x_conv3x3_nhwc_f16(const void* x, const void* wt4, c
                                                int32_t Win, int32_t Cin, int32_t Cout, void* stream) {
   if (!x || !wt4 || !out || N < 1 || Hin < 1 || Win < 1 || Cin < CV_BK || Cin % CV_BK || Cout < 8 || (Cout & 7)) return 1;
   if (!fits32((long long)N * Hin * Win * 4, Cin, Cout, Cout, 9)) return 1;
-  hipStream_t s = (hipStream_t)stream;
-  const bool wide = Cout % 160 == 0 && Cout % 128 != 0;
-  const int geom = 1 | (1 << 8) | (1 << 16);
-  const int tapsel = 0x1ff | (1 << 11) | (1 << 12) | (1 << 13);
-  return wide ? launch<160, 2, 9, false>(x, wt4, bias, nullptr, out, N, Hin, Win, Cin, Cout, s, nullptr, 0, 0, 0, geom, nullptr, nullptr, tapsel)
-              : launch<128, 2, 9, false>(x, wt4, bias, nullptr, out, N, Hin, Win, Cin, Cout, s, nullptr, 0, 0, 0, geom, nullptr, nullptr, tapsel);
+  ConvCall c = conv_call(x, wt4, bias, nullptr, out, N, Hin, Win, Cin, Cout);
+  c.tapsel = 0x1ff | (1 << 11) | (1 << 12) | (1 << 13);
+  return with_conv_width(Cout, [&](auto bn) { return launch<decltype(bn)::value, 9, false>(c, (hipStream_t)stream); });
 }
 
 extern "C" int gip_conv3x3_gnin_nhwc_f16(const void* x, const void* w, const void* bias, const void* residual, void* out, int32_t N,
@@ -1506,33 +1497,28 @@ extern "C" int gip_conv3x3_gnin_nhwc_f16(const void* x, const void* w, const voi
                                         int32_t addend_stride, float* chan_stats, void* stream) {
   if (!x || !w || !out || !gamma || !beta || !mean || !rstd || N < 1 || Cin != 128 || Cout < 8 || (Cout & 7) || G < 1 || 128 % G) return 1;
   if (!fits32((long long)N * H * W, Cin, Cout, Cout, 9)) return 1;
-  GnBwdArgs gnb = {};
-  gnb.gamma = (const _Float16*)gamma; gnb.beta = (const _Float16*)beta; gnb.addend = (const _Float16*)addend;
-  gnb.mean = mean; gnb.rstd = rstd; gnb.G = G; gnb.silu = apply_silu; gnb.addend_stride = addend_stride; gnb.HW = H * W;
-  return launch<128, 2, 9, false>(x, w, bias, residual, out, N, H, W, Cin, Cout, (hipStream_t)stream, nullptr, 0, 0, 0,
-                                  1 | (1 << 8) | (1 << 16), chan_stats, &gnb, 0x1ff, 128, 1, 0, 0, 0, true);
+  ConvCall c = conv_call(x, w, bias, residual, out, N, H, W, Cin, Cout);
+  c.chan_stats = chan_stats; c.gn_in = true;
+  GnBwdArgs& g = c.gnb;
+  g.gamma = (const _Float16*)gamma; g.beta = (const _Float16*)beta; g.addend = (const _Float16*)addend;
+  g.mean = mean; g.rstd = rstd; g.G = G; g.silu = apply_silu; g.addend_stride = addend_stride; g.HW = H * W;
+  return launch<128, 9, false>(c, (hipStream_t)stream);
 }
 
 extern "C" int gip_linear_batched_f16(const void* x, const void* w, void* out, int32_t B, int64_t M, int32_t K, int32_t Nout,
                                       int64_t bs_x, int64_t bs_w, int64_t bs_o, void* stream) {
   if (!x || !w || !out || B < 1 || B > 65535 || M < 1 || M >= (1ll << 31) || K < CV_BK || K % CV_BK || Nout < 4 || (Nout & 3)) return 1;
   if (!fits32(M, K, Nout, Nout, 1) || bs_x < 0 || bs_w < 0 || bs_o < 0 || (bs_x & 7) || (bs_w & 7) || (bs_o & 3)) return 1;
+  ConvCall c = conv_call(x, w, nullptr, nullptr, out, 1, 1, (int)M, K, Nout);
+  c.batch = B; c.bs_x = bs_x; c.bs_w = bs_w; c.bs_o = bs_o;
   hipStream_t s = (hipStream_t)stream;
-  const bool wide = Nout % 160 == 0 && Nout % 128 != 0;
-  const int geom = 1 | (1 << 8) | (1 << 16);
   // 256 x 256 tiles (one 8-wave workgroup per CU, half the operand bytes per MAC) where the batch of products fills the chip with
   // them: the sixteen [768, K] x [K, 1280] products of a Winograd convolution at the 16 x 16 level are 3 x 5 x 16 = 240 tiles
   if (!(Nout & 255) && gip_dbg_conv_big != 0) {
     const long long tiles = ((M + 255) / 256) * (Nout / 256) * B;
-    if (tiles >= 224 && (M % 256 == 0 || M >= 2048)) {
-      GnBwdArgs none = {};
-      return launch_big<256, 256, 1>(x, w, nullptr, nullptr, out, 1, 1, (int)M, K, Nout, s, 1, (int)M, geom, nullptr, none, B, bs_x, bs_w, bs_o);
-    }
+    if (tiles >= 224 && (M % 256 == 0 || M >= 2048)) return launch_big<256, 256, 1>(c, s);
   }
-  return wide ? launch<160, 2, 1, false>(x, w, nullptr, nullptr, out, 1, 1, (int)M, K, Nout, s, nullptr, 0, 0, 0, geom, nullptr, nullptr, 0x1ff,
-                                         128, B, bs_x, bs_w, bs_o)
-              : launch<128, 2, 1, false>(x, w, nullptr, nullptr, out, 1, 1, (int)M, K, Nout, s, nullptr, 0, 0, 0, geom, nullptr, nullptr, 0x1ff,
-                                         128, B, bs_x, bs_w, bs_o);
+  return with_conv_width(Nout, [&](auto bn) { return launch<decltype(bn)::value, 1, false>(c, s); });
 }
 
 extern "C" int gip_linear_f16(const void* x, const void* w, const void* bias, const void* residual, void* out, int64_t M,
@@ -1540,9 +1526,8 @@ extern "C" int gip_linear_f16(const void* x, const void* w, const void* bias, co
   if (!x || !w || !out || M < 1 || M >= (1ll << 31) || K < CV_BK || K % CV_BK || Nout < 4 || (Nout & 3)) return 1;
   if (geglu && (residual || Nout % 64)) return 1;
   if (!fits32(M, K, Nout, geglu ? 2 * Nout : Nout, 1)) return 1;
+  ConvCall c = conv_call(x, w, bias, residual, out, 1, 1, (int)M, K, Nout);
   hipStream_t s = (hipStream_t)stream;
-  if (geglu) return launch<128, 2, 1, true>(x, w, bias, nullptr, out, 1, 1, (int)M, K, Nout, s);
-  return with_linear_width(M, Nout, [&](auto bn) {
-    return launch<decltype(bn)::value, 2, 1, false>(x, w, bias, residual, out, 1, 1, (int)M, K, Nout, s);
-  });
+  if (geglu) return launch<128, 1, true>(c, s);
+  return with_linear_width(M, Nout, [&](auto bn) { return launch<decltype(bn)::value, 1, false>(c, s); });
 }

@@ -156,7 +156,7 @@ def fallback(site, t, library=False):
 # of those bumps this counter; it is part of the graph keys, so a stale graph is never replayed.
 _weights_epoch = 0
 _ENV_KNOBS = ("GIP_WINOGRAD", "GIP_WINOGRAD_SHAPES", "GIP_WINOGRAD_GEMM", "GIP_GN_STATS", "GIP_FUSE_QKV", "GIP_GN_BWD_SUMS", "GIP_RESBLOCK_NODE",
-              "GIP_OWN_GEMM", "GIP_CONV_HALO", "GIP_CONV_GNIN", "GIP_WINOGRAD_GN", "GIP_TUNABLEOP", "GIP_LN_FOLD", "GIP_CONV_S2_STATS")
+              "GIP_OWN_GEMM", "GIP_CONV_GNIN", "GIP_WINOGRAD_GN", "GIP_TUNABLEOP", "GIP_LN_FOLD", "GIP_CONV_S2_STATS")
 
 
 def bump_weights_epoch():
@@ -906,7 +906,7 @@ def _conv_gn_in(x, gn, addend, chan_stats, w, bias, residual, stats):
     cout = w.shape[0]
     # (Cout % 256 == 0 layers run on the 256-wide tile, which has no halo mode and is faster for them than this kernel)
     if (chan_stats is None or _DISABLED or C != 128 or H % 8 or W % 16 or cout % 8 or cout % 256 == 0 or C % gn.num_groups or
-            _conv_tiles(N, H, W, cout) < 256 or os.environ.get("GIP_CONV_GNIN", "1") == "0" or os.environ.get("GIP_CONV_HALO", "1") == "0" or
+            _conv_tiles(N, H, W, cout) < 256 or os.environ.get("GIP_CONV_GNIN", "1") == "0" or
             x.numel() * 2 >= (1 << 31) or N * H * W * cout * 2 >= (1 << 31)):
         return None
     lib = _lib.nn_lib()

@@ -1,6 +1,5 @@
 """Halo-resident pixel tile (conv3x3_kernel<..., HALO>) against the streaming kernel on the Cin = 128 shapes of the VAE encoder,
-same process (debug knob gip_dbg_conv_epilogue = 0 selects the streaming kernel with its per-lane epilogue; GIP_CONV_HALO=0 in
-the environment selects the streaming kernel with the LDS epilogue — run the script twice for that comparison)."""
+same process (debug knob gip_dbg_conv_epilogue = 0 selects the streaming kernel with its per-lane epilogue)."""
 import ctypes
 import os
 import sys
@@ -27,7 +26,6 @@ def timed(fn, n=20):
 
 
 cl = dict(memory_format=torch.channels_last)
-print("GIP_CONV_HALO=%s" % os.environ.get("GIP_CONV_HALO", "1"))
 for N, co, H, W, res in [(4, 128, 512, 512, False), (4, 128, 512, 512, True), (4, 256, 256, 256, False), (2, 128, 512, 512, False), (1, 128, 512, 512, False),
                          (1, 128, 1024, 1024, False)]:
     x = torch.randn(N, 128, H, W, device="cuda").half().contiguous(**cl)

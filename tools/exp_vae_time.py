@@ -1,4 +1,4 @@
-"""VAE encoder forward + backward (4 x 512^2, eager launches), wall time per call; environment switches (GIP_CONV_HALO, ...) are read
+"""VAE encoder forward + backward (4 x 512^2, eager launches), wall time per call; environment switches (GIP_CONV_GNIN, ...) are read
 at start-up: run it alternately under both settings on one box."""
 import os
 import sys
