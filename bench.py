@@ -19,12 +19,18 @@ Timing: W warmup steps, then R = --repeats windows of EXACTLY K steps, each brac
 sides and MAX-reduced over the ranks; `ms_per_step` / `value` are the MEDIAN window (config.repeats, all windows in
 `window_ms_per_step`): 20 steps are a 10 ms region, a single one is a +-2 % instrument.
 
+A plain run does only what the headline needs: set up, warm up, the timed windows, --dump-outputs, the line.  Everything
+else is measured only with --full, after the headline windows (the --no-* switches, --profile-iters and --ahds-steps act
+within it); without it those objects of the line are null and config.num_rendered_per_view too (it comes from the
+roofline's profiled pass):
+
 "ahds": the full AHDS stage-1 training step of BASELINE.json configs[2] (render 4 views -> VAE encode -> ControlNet +
 U-Net ANPG at batch 12 -> SDS -> backward -> Adam), measured by tools/bench_ahds.py after the raster timing; steps/s,
 views/s and the denoise MFMA fraction.  Random-initialised SD1.5-shaped networks (no checkpoints without a network).
 
 Extra objects: "roofline" (dominant kernel, live hipEvent durations on the launch stream) and "cpu_baseline" (the CPU
-oracle = "port" of the reference algorithm, timed on this box's host cores on a bounded sample: 1 view fwd+bwd).
+oracle = "port" of the reference algorithm, timed on this box's host cores on a bounded sample: 1 view fwd+bwd);
+"forward_only", "trained_state", "config4", "exact_lists", "replicas_layout" (N > 1) and "roofline_valu".
 
 --dump-outputs DIR: what the last timed step of the headline windows returned — color, radii, depth, alpha and the gradients of
 means3D / shs / opacities / scales / rotations / means2D — as DIR/<name>.npy (float32, a fixed seeded sample of the larger
@@ -309,6 +315,9 @@ def main():
     ap.add_argument("--gaussians", type=int, default=100000)
     ap.add_argument("--size", type=int, default=1024)
     ap.add_argument("--views", type=int, default=4)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline windows, also measure every secondary object of the line (the --no-* switches below "
+                         "leave out single ones); without it the run does only what the headline figure needs")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--profile-iters", type=int, default=10)
     ap.add_argument("--no-ahds", action="store_true", help="skip the full AHDS training-step measurement (configs[2])")
@@ -466,37 +475,43 @@ def main():
     views_total = n_groups * V * args.steps                          # views of all optimizer steps taken in a window
     mpix_s = views_total * H * W / elapsed / 1e6
 
+    # ---- everything below up to the line is --full only: the headline figure and the dumped arrays are complete here
     # forward only (SURVEY §8d asks for forward and forward+backward separately): the same 4-view launch set rendered
     # without a backward to follow.  Grad mode stays on so that the capacity check stays deferred as in training; an
     # output render under no_grad additionally waits for its header (one host round trip per call)
-    def fwd_step():
-        m2d = torch.zeros((Vl, P, 3), device=dev, requires_grad=True)
-        return rasterize_views(t["means3D"], m2d, t["opacities"], sts, shs=t["shs"], scales=t["scales"], rotations=t["rotations"])
-    for _ in range(3):
-        fwd_step()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        fwd_step()
-    torch.cuda.synchronize()
-    fwd_ms = (time.perf_counter() - t0) / args.steps * 1e3
-    # an OUTPUT render (torch.no_grad(): orbit frames, the refine pass' inputs): GipRasterConfig::forward_only — the kernel
-    # skips the checkpoints and the n_contrib / final_T images — and the capacity header is awaited in every call
-    def nograd_step():
-        with torch.no_grad():
-            return rasterize_views(t["means3D"], None, t["opacities"], sts, shs=t["shs"], scales=t["scales"], rotations=t["rotations"])
-    for _ in range(3):
-        nograd_step()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        nograd_step()
-    torch.cuda.synchronize()
-    nograd_ms = (time.perf_counter() - t0) / args.steps * 1e3
+    forward_only = None
+    if args.full:
+        def fwd_step():
+            m2d = torch.zeros((Vl, P, 3), device=dev, requires_grad=True)
+            return rasterize_views(t["means3D"], m2d, t["opacities"], sts, shs=t["shs"], scales=t["scales"], rotations=t["rotations"])
+        for _ in range(3):
+            fwd_step()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            fwd_step()
+        torch.cuda.synchronize()
+        fwd_ms = (time.perf_counter() - t0) / args.steps * 1e3
+        # an OUTPUT render (torch.no_grad(): orbit frames, the refine pass' inputs): GipRasterConfig::forward_only — the kernel
+        # skips the checkpoints and the n_contrib / final_T images — and the capacity header is awaited in every call
+        def nograd_step():
+            with torch.no_grad():
+                return rasterize_views(t["means3D"], None, t["opacities"], sts, shs=t["shs"], scales=t["scales"], rotations=t["rotations"])
+        for _ in range(3):
+            nograd_step()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            nograd_step()
+        torch.cuda.synchronize()
+        nograd_ms = (time.perf_counter() - t0) / args.steps * 1e3
+        forward_only = {"ms_per_step": round(fwd_ms, 4), "mpix_per_s_per_gpu": round(Vl * H * W / fwd_ms / 1e3, 1),
+                        "no_grad_render_ms_per_call": round(nograd_ms, 4),
+                        "note": "ms_per_step: forward with the state a backward needs, capacity check deferred; no_grad_render: forward_only kernels, header awaited per call"}
 
     # ---- the same step on a TRAINED-looking state (secondary: the headline config is the init state SURVEY §8d prescribes)
     trained = None
-    if rank == 0 and not args.no_trained:
+    if args.full and rank == 0 and not args.no_trained:
         sct = scenes.trained_look(scenes.make_scene("human", P, seed=42, sh_degree=0), seed=7)
         tt_ = {k: torch.from_numpy(np.ascontiguousarray(v)).to(dev).contiguous().requires_grad_(True) for k, v in sct.items()}
         pl_ = [tt_[n] for n in names]
@@ -524,7 +539,7 @@ def main():
 
     # ---- BASELINE configs[4]: per-stage HBM roofline at 1M Gaussians (N = 1 only; the headline config stays configs[1]) ----
     config4 = None
-    if world == 1 and not args.no_config4:
+    if args.full and world == 1 and not args.no_config4:
         try:
             config4 = measure_config4(dev)
         except Exception as e:  # noqa: BLE001  (secondary measurement: never lose the contract line to it)
@@ -534,7 +549,7 @@ def main():
     # ---- N > 1 extra: the replica layout of rounds 1-2 (every rank its own 4 cameras of the replicated Gaussians, a 4 x N
     # batch, gradients averaged over all ranks) — weak scaling, NOT the contract value
     replicas = None
-    if world > 1:
+    if args.full and world > 1:
         sts_r = settings(scenes.train_cameras(V, seed=42 + rank, H=H, W=W))
         wr_, _ = timed_windows(make_step(sts_r, None, True), 3, args.steps, args.warmup)
         dtr = sorted(wr_)[1] / args.steps
@@ -545,7 +560,7 @@ def main():
     # ---- the bit-exact-lists mode (GipRasterConfig::exact_lists: the fork's tile / index buffers bit for bit; the default
     # emits the same lists minus provably dead entries): the same step, driver-measured (N = 1 only)
     exact = None
-    if world == 1 and not args.no_exact:
+    if args.full and world == 1 and not args.no_exact:
         os.environ["GIP_RASTER_EXACT_LISTS"] = "1"
         try:
             we_, _ = timed_windows(step, 5, args.steps, max(args.warmup, 3))
@@ -564,7 +579,7 @@ def main():
 
     # ---- metric (i) of BASELINE.json: full AHDS training steps/s (configs[2]; at N>1 configs[3]'s view sharding) ----
     ahds = None
-    if not args.no_ahds:
+    if args.full and not args.no_ahds:
         sys.path.insert(0, os.path.join(ROOT, "tools"))
         import bench_ahds
         try:
@@ -623,8 +638,8 @@ def main():
                 config4["stage3"] = bench_stage3.measure()
             except Exception as e:  # noqa: BLE001
                 config4["refine_error"] = "%s: %s" % (type(e).__name__, str(e)[:300])
-    out = None
-    if rank == 0:
+    Rv, roofline, valu, cpu = None, None, None, None
+    if args.full and rank == 0:
         # ---- roofline: live per-kernel durations (hipEvents on the launch stream) ----
         stages, num_rendered = R.profile_stages(
             t["means3D"].detach(), t["opacities"].detach(), sts, gC[:Vl], gD[:Vl], None, shs=t["shs"].detach(),
@@ -698,7 +713,6 @@ def main():
                     "whole_step_frac": round((b_f + b_b) * Vl / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
                     "pair_evals_per_s_fwd": round(Rv * Vl * 256 / (stages["render_fwd"] * 1e-3), 0)}
 
-        cpu = None
         if not args.no_cpu_baseline:
             from oracle import oracle as orc
             orc.build()
@@ -764,14 +778,15 @@ def main():
                    "sample": "median of 5 x (1 view forward, then backward; P=%d, %dx%d) after one warm-up, on the C oracle "
                              "(oracle/raster_oracle.c, OpenMP over tiles, %d threads); value = forward+backward" % (P, H, W, ncores)}
 
+    if rank == 0:
         out = {"metric": "raster_fwd_bwd_mpix_per_s", "value": round(mpix_s, 2), "unit": "Mpix/s", "n_gpus": world,
                "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4),
                "higher_is_better": True, "scaling": "weak" if world == 1 else "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
                "config": {"workload": "BASELINE.json configs[1]: %d Gaussians (synthetic human surface, SMPL-X-style "
                                       "init), %dx%d, %d views per optimizer step, raster forward+backward" % (P, H, W, V),
                           "gaussians": P, "height": H, "width": W, "views_per_step": V, "views_per_step_per_gpu": Vl,
-                          "prewarm_steps": args.prewarm, "repeats": len(windows), "value_is": "median window",
-                          "num_rendered_per_view": int(Rv), "sh_degree": 0,
+                          "prewarm_steps": args.prewarm, "repeats": len(windows), "value_is": "median window", "full": args.full,
+                          "num_rendered_per_view": None if Rv is None else int(Rv), "sh_degree": 0,
                           "backend": None if world == 1 else ("rccl" if backend == "nccl" else backend),
                           "dist_world_size": 1 if world == 1 else dist.get_world_size(),
                           "gpus_visible": int(os.environ.get("GIP_BENCH_VISIBLE_GPUS", torch.cuda.device_count())),
@@ -779,16 +794,13 @@ def main():
                               V, shard.group_size, shard.n_seed_groups)},
                "window_ms_per_step": [round(w_ / args.steps * 1e3, 4) for w_ in windows],
                "raster_steps_per_s": round(1e3 / ms_per_step, 3), "views_per_s": round(views_total / elapsed, 2),
-               "forward_only": {"ms_per_step": round(fwd_ms, 4), "mpix_per_s_per_gpu": round(Vl * H * W / fwd_ms / 1e3, 1),
-                                "no_grad_render_ms_per_call": round(nograd_ms, 4),
-                                "note": "ms_per_step: forward with the state a backward needs, capacity check deferred; no_grad_render: forward_only kernels, header awaited per call"},
+               "forward_only": forward_only,
                "trained_state": trained,
                "config4": config4,
                "exact_lists": exact,
                "replicas_layout": replicas,
                "roofline": roofline, "roofline_valu": valu, "cpu_baseline": cpu,
                "dump_outputs": None if dumped is None else {"dir": args.dump_outputs, "arrays": dumped}}
-    if rank == 0:
         out["ahds"] = ahds
         # BASELINE.json's metric names the AHDS training-step rate first: first-class beside the raster rate
         out["ahds_steps_per_s"] = ahds.get("value") if isinstance(ahds, dict) else None

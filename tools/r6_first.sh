@@ -8,7 +8,7 @@ cd $GRAFT_REPO_ROOT
 OUT=$GRAFT_REPO_ROOT/gpurun_out/r6a; mkdir -p $OUT
 timeout 120 tools/micro/grid_barrier 64 > $OUT/grid_barrier.txt 2>&1
 for lib in libgip_raster.so libgip_raster_seg128.so libgip_raster_seg256.so libgip_raster.so; do
-  GIP_RASTER_LIB=$lib timeout 600 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-ahds --no-proxy 2>$OUT/bench_$lib.err | tail -1 > $OUT/bench_$lib.json
+  GIP_RASTER_LIB=$lib timeout 600 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-ahds --no-proxy 2>$OUT/bench_$lib.err | tail -1 > $OUT/bench_$lib.json
   python - <<PY
 import json
 d = json.loads(open("$OUT/bench_$lib.json").readline())
