@@ -186,6 +186,12 @@ def model_lib():
         lib.gip_activate_gaussians_backward.argtypes = [_vp] * 6 + [ctypes.c_int64, _vp, _vp, _vp, _vp]
         lib.gip_densify_stats.restype = ctypes.c_int
         lib.gip_densify_stats.argtypes = [_vp, ctypes.c_int32, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, _vp]
+        lib.gip_ssim_workspace_bytes.restype = ctypes.c_size_t
+        lib.gip_ssim_workspace_bytes.argtypes = [ctypes.c_int32] * 4
+        lib.gip_ssim_forward.restype = ctypes.c_int
+        lib.gip_ssim_forward.argtypes = [_vp, _vp] + [ctypes.c_int32] * 4 + [_vp, _vp, _vp, _vp, _vp]
+        lib.gip_ssim_backward.restype = ctypes.c_int
+        lib.gip_ssim_backward.argtypes = [_vp, _vp, _vp, _vp] + [ctypes.c_int32] * 4 + [_vp, _vp]
         _model = _Counted(lib)
     return _model
 

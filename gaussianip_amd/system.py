@@ -383,11 +383,14 @@ class StageThreeStep:
 
     def __init__(self, gaussian, pipe, background, cameras, refined_rgbs=None, view_idx_all=None, lambda_l1=1.0,
                  lambda_lpips=0.0, perceptual=None, train_bs=4, cfg: Optional[StageOneConfig] = None,
-                 refined_rgbs_small=None):
+                 refined_rgbs_small=None, lambda_ssim: float = 0.0):
         """Either `refined_rgbs` [n, H, W, 3] in refinement order with `view_idx_all` (the refiner's return values), or
-        `refined_rgbs_small` [n, 3, h, w] in orbit order as stored in after_refine.pth (`load_after_refine`)."""
+        `refined_rgbs_small` [n, 3, h, w] in orbit order as stored in after_refine.pth (`load_after_refine`).
+        `lambda_ssim` (not in the reference's stage 3; the D-SSIM term of the 3DGS trainers, loss_utils.py:33-63) adds
+        lambda_ssim * (1 - ssim(render, target)) through the fused kernels of utils/loss.py; 0.0 leaves the loss as it is."""
         self.gaussian, self.pipe, self.background, self.cameras = gaussian, pipe, background, cameras
         self.lambda_l1, self.lambda_lpips, self.perceptual, self.train_bs = lambda_l1, lambda_lpips, perceptual, train_bs
+        self.lambda_ssim = lambda_ssim
         self.cfg = cfg or StageOneConfig()
         self.viewspace_points = self.refine_radii = self.refine_visibility_filter = None
         if refined_rgbs_small is not None:
@@ -430,6 +433,9 @@ class StageThreeStep:
             else:
                 d = self.perceptual(small, gt)
             loss = loss + self.lambda_lpips * d.mean()
+        if self.lambda_ssim:
+            from .utils.loss import ssim
+            loss = loss + self.lambda_ssim * (1.0 - ssim(small, gt))
         return {"loss": loss, "render_pkg": pkg, "id_list": id_list}
 
     # GaussianIP.on_before_optimizer_step (stage 3 branch, GaussianIP.py:476-506), quirks included

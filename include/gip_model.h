@@ -99,6 +99,25 @@ int gip_activate_gaussians_backward(const float* opacity, const float* scaling, 
  *   xyz_gradient_accum += ||grad[:, :2]|| * visible;  denom += visible.   (visible: bytes 0 / 1; radii int32; the rest float32 [P].) */
 int gip_densify_stats(const float* viewspace_grad, int32_t V, int64_t P, const uint8_t* visible, const int32_t* radii,
                       float* max_radii2D, float* xyz_gradient_accum, float* denom, void* stream);
+
+/* The structural-similarity loss of the 3DGS trainers (gaussiansplatting/utils/loss_utils.py:33-63 ssim / _ssim; the window of
+ * :23-31): an 11 x 11 Gaussian window (sigma 1.5, normalised in float32) with zero padding of 5 pixels, depthwise on
+ * [N, C, H, W] float32 contiguous images, C1 = 0.01^2, C2 = 0.03^2.  One tiled kernel forward (+ a one-workgroup-per-image pass
+ * that adds the per-workgroup partial sums in a fixed order: no float atomics, bitwise reproducible) and one backward, instead of
+ * five grouped 121-tap convolutions, a dozen pointwise ops and their autograd graph.
+ *   gip_ssim_workspace_bytes  bytes of `workspace` for a shape (0 for a shape the entry points reject);
+ *   gip_ssim_forward   per_image_mean[n] = mean over (c, h, w) of the SSIM map of image n  (loss_utils.py:63; their mean is :61).
+ *                      deriv (or NULL: nothing but the means is written) receives [3, N, C, H, W]: the three planes the backward
+ *                      needs (d m / d mu1 with the variance terms folded in, d m / d sigma1^2, d m / d sigma12);
+ *                      map (or NULL) receives the SSIM map [N, C, H, W];
+ *   gip_ssim_backward  g_img1 = sum_n g_per_image[n] * d per_image_mean[n] / d img1   ([N, C, H, W]); g_per_image is a DEVICE
+ *                      array of N floats, so no host synchronisation enters a training step.  img2 is data: no gradient.
+ * Status 1: an empty or negative dimension, a NULL required pointer, more than 2^31 - 1 tiles of 32 x 32. */
+size_t gip_ssim_workspace_bytes(int32_t N, int32_t C, int32_t H, int32_t W);
+int gip_ssim_forward(const float* img1, const float* img2, int32_t N, int32_t C, int32_t H, int32_t W, float* per_image_mean,
+                     float* deriv, float* map, void* workspace, void* stream);
+int gip_ssim_backward(const float* img1, const float* img2, const float* deriv, const float* g_per_image, int32_t N, int32_t C,
+                      int32_t H, int32_t W, float* g_img1, void* stream);
 #ifdef __cplusplus
 }
 #endif

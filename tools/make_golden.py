@@ -592,6 +592,61 @@ def ply():
     print("ply layout written:", list(out["names_deg0"]))
 
 
+def ssim():
+    """gaussiansplatting/utils/loss_utils.py:33-63 (ssim / _ssim) on the seeded images of tests/ssim_inputs.py, in float32 on the
+    CPU: per case the size_average=True scalar, the size_average=False vector and d ssim / d img1 from the reference's own
+    autograd, plus `map_err` = max |map_float32 - map_float64| with the SSIM map captured at the `.mean()` boundary of the
+    reference's _ssim in both precisions (the reference's own float32 error of the map; the map itself is not kept).
+    The stage-3 shape (4, 3, 415, 290) gets the scalar, the vector, `map_err` and `grad_err` = max |grad_float32 - grad_float64| /
+    max |grad_float64| instead of its 5.8 MB gradient.  Outputs only; the float32 gradients of the largest fixture shape exceed
+    one file's size limit and go to ssim_grad_a.npz / ssim_grad_b.npz (three input kinds each)."""
+    sys.path.insert(0, os.path.dirname(OUT))
+    import ssim_inputs
+    from gaussiansplatting.utils import loss_utils
+    captured = []
+    tensor_mean = torch.Tensor.mean
+
+    def spy(self, *a, **k):
+        captured.append(self.detach())
+        return tensor_mean(self, *a, **k)
+
+    def run(a, b, dtype):
+        x = torch.from_numpy(a).to(dtype).requires_grad_(True)
+        y = torch.from_numpy(b).to(dtype)
+        del captured[:]
+        torch.Tensor.mean = spy
+        try:
+            val = loss_utils.ssim(x, y)
+        finally:
+            torch.Tensor.mean = tensor_mean
+        smap = captured[0]
+        assert smap.shape == x.shape
+        grad, = torch.autograd.grad(val, x)
+        with torch.no_grad():
+            vec = loss_utils.ssim(x, y, size_average=False)
+        return val.detach(), vec, grad, smap
+
+    main_file, big = {}, ({}, {})
+    largest = max(ssim_inputs.SHAPES, key=lambda s: int(np.prod(s)))
+    for kind, shape in ssim_inputs.CASES + (ssim_inputs.STAGE3_CASE,):
+        a, b = ssim_inputs.images(kind, shape)
+        val, vec, grad, smap = run(a, b, torch.float32)
+        _, _, grad64, smap64 = run(a, b, torch.float64)
+        key = ssim_inputs.case_key(kind, shape)
+        main_file[key + "_scalar"] = val.numpy()
+        main_file[key + "_vector"] = vec.numpy()
+        main_file[key + "_map_err"] = np.float64((smap.double() - smap64).abs().max())
+        if (kind, shape) == ssim_inputs.STAGE3_CASE:
+            main_file[key + "_grad_err"] = np.float64((grad.double() - grad64).abs().max() / grad64.abs().max())
+            continue
+        dst = main_file if shape != largest else big[ssim_inputs.KINDS.index(kind) // 3]
+        dst[key + "_grad"] = grad.numpy()
+    np.savez_compressed(os.path.join(OUT, "ssim.npz"), **main_file)
+    np.savez_compressed(os.path.join(OUT, "ssim_grad_a.npz"), **big[0])
+    np.savez_compressed(os.path.join(OUT, "ssim_grad_b.npz"), **big[1])
+    print("ssim fixtures written: %d cases" % (len(ssim_inputs.CASES) + 1))
+
+
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "ahds":
         ahds()
@@ -603,5 +658,7 @@ if __name__ == "__main__":
         ops()
     elif len(sys.argv) > 1 and sys.argv[1] == "ply":
         ply()
+    elif len(sys.argv) > 1 and sys.argv[1] == "ssim":
+        ssim()
     else:
         main()
