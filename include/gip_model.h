@@ -118,6 +118,31 @@ int gip_ssim_forward(const float* img1, const float* img2, int32_t N, int32_t C,
                      float* deriv, float* map, void* workspace, void* stream);
 int gip_ssim_backward(const float* img1, const float* img2, const float* deriv, const float* g_per_image, int32_t N, int32_t C,
                       int32_t H, int32_t W, float* g_img1, void* stream);
+/* Leaving the Gaussian representation (gs_renderer.py:67-100 gaussian_3d_coeff, :240-331 GaussianModel.extract_fields; csrc/field.hip).
+ *   gip_density_field  field[i, j, k] ([R, R, R] float32, `ij` order) = sum over the members of the voxel's block of
+ *       opacity * exp(-0.5 d^T Sigma^-1 d), d = (grid[i], grid[j], grid[k]) - xyz', xyz' = (xyz - center) * scale, Sigma from
+ *       scaling * scale and the raw quaternion, inverted by the adjugate with 1 / (det + 1e-24); a positive power counts as 0.
+ *       The grid points are grouped in num_blocks^3 blocks (R % num_blocks == 0, num_blocks <= 1024); a Gaussian is a member of a
+ *       block when xyz' lies strictly inside [first - margin, last + margin] of the block's grid coordinates on all three axes
+ *       (margin = relax_ratio * 2 / num_blocks rounded to float32); blocks without a member are exactly 0.
+ *       The caller passes the P Gaussians that passed its prefilter (P = 0 gives zeros): xyz [P, 3], activated opacity [P], activated
+ *       scaling [P, 3], raw rotation [P, 4], center [3] (device), grid [R] (device; torch.linspace(-1, 1, R), not re-derived here).
+ *       Members are added in the order of the arrays, no float atomics: two runs are bitwise equal.  No host read.
+ *   gip_field_workspace_size  bytes of `workspace` (a record and a block-range word per Gaussian).
+ *   gip_surface_count / gip_surface_emit  the iso-surface f = threshold of any [R, R, R] float32 grid as an indexed triangle mesh
+ *       (marching tetrahedra on the Kuhn decomposition; a grid point is inside when f >= threshold; normals toward decreasing f;
+ *       open where the surface leaves the grid).  count: edge_flag [R^3 * 7] int32 (1 = the edge carries a vertex; edge id =
+ *       point id * 7 + slot, slots x, y, z, xy, xz, yz, xyz) and tri_count [(R - 1)^3] int32 (triangles of each cube).  The caller
+ *       scans both exclusively (edge_index, tri_offset), reads the two totals V and F, allocates vertices [V, 3] float32 (grid-index
+ *       units) and faces [F, 3] int32, and calls emit.  Vertex order = edge id, face order = cube id, tetrahedron: deterministic.
+ * Status 1: a NULL required pointer, a shape outside the limits (R < 2 or 7 R^3 > 2^31 - 1 for the surface), a short workspace. */
+int gip_field_workspace_size(int64_t P, int32_t R, int32_t num_blocks, size_t* bytes);
+int gip_density_field(const float* xyz, const float* opacity, const float* scaling, const float* rotation, int64_t P,
+                      const float* center, float scale, const float* grid, int32_t R, int32_t num_blocks, float margin,
+                      void* workspace, size_t workspace_bytes, float* field, void* stream);
+int gip_surface_count(const float* field, int32_t R, float threshold, int32_t* edge_flag, int32_t* tri_count, void* stream);
+int gip_surface_emit(const float* field, int32_t R, float threshold, const int32_t* edge_flag, const int32_t* edge_index,
+                     const int32_t* tri_offset, float* vertices, int32_t* faces, void* stream);
 #ifdef __cplusplus
 }
 #endif

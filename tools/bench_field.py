@@ -1,0 +1,129 @@
+#!/usr/bin/env python3
+"""Times GaussianModel.extract_fields and extract_mesh (csrc/field.hip) on 100k Gaussians of the human-shaped cloud of tests/scenes.py
+at 128^3 and 256^3, next to the same field written as the reference's block loop of PyTorch ops on the same GPU (this file's own
+statement of that op chain: one masked gather and a [voxels, members] evaluation per block, Gaussians in batches of 1024).
+
+hipEvent timing around each call, warm-up runs first, the median of the timed runs.  Usage:
+    python tools/bench_field.py [--points 100000] [--runs 7] [--warmup 2] [--chain-runs 3] [--out profiles/field_extract.txt]
+    python tools/bench_field.py --once 128      one extract_fields + extract_mesh call (for a kernel trace)"""
+import argparse
+import os
+import statistics
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+
+def make_model(P):
+    import scenes
+    from gaussianip_amd.scene import GaussianModel
+    sc = scenes.trained_look(scenes.make_scene("human", P, seed=42))
+    gm = GaussianModel(0)
+    gm._xyz = torch.from_numpy(sc["means3D"]).cuda()
+    gm._opacity = torch.logit(torch.from_numpy(sc["opacities"])).cuda()
+    gm._scaling = torch.log(torch.from_numpy(sc["scales"])).cuda()
+    gm._rotation = torch.from_numpy(sc["rotations"]).cuda()
+    return gm
+
+
+@torch.no_grad()
+def op_chain(gm, resolution, num_blocks=16, relax_ratio=1.5, count_pairs=False):
+    """The field as a loop over blocks of PyTorch ops (the form the reference computes it in)."""
+    from gaussianip_amd.utils.general import build_scaling_rotation
+    dev = gm._xyz.device
+    opac = torch.sigmoid(gm._opacity)
+    keep = (opac > 0.005).squeeze(1)
+    opac, xyz, std, rot = opac[keep], gm._xyz[keep], torch.exp(gm._scaling[keep]), gm._rotation[keep]
+    mn, mx = xyz.amin(0), xyz.amax(0)
+    center, scale = (mn + mx) / 2, 1.8 / (mx - mn).amax().item()
+    xyz, std = (xyz - center) * scale, std * scale
+    L = build_scaling_rotation(std, rot)
+    S = L @ L.transpose(1, 2)
+    a, b, c, d, e, f = S[:, 0, 0], S[:, 0, 1], S[:, 0, 2], S[:, 1, 1], S[:, 1, 2], S[:, 2, 2]
+    inv_det = 1 / (a * d * f + 2 * e * c * b - e ** 2 * a - c ** 2 * d - b ** 2 * f + 1e-24)
+    inv = torch.stack(((d * f - e ** 2) * inv_det, (e * c - b * f) * inv_det, (e * b - c * d) * inv_det, (a * f - c ** 2) * inv_det,
+                       (b * c - e * a) * inv_det, (a * d - b ** 2) * inv_det), 1)
+    occ = torch.zeros((resolution,) * 3, device=dev)
+    pairs = 0
+    s, margin = resolution // num_blocks, (2 / num_blocks) * relax_ratio
+    parts = torch.linspace(-1, 1, resolution).to(dev).split(s)
+    for xi, xs in enumerate(parts):
+        for yi, ys in enumerate(parts):
+            for zi, zs in enumerate(parts):
+                lo = torch.stack((xs[0], ys[0], zs[0])) - margin
+                hi = torch.stack((xs[-1], ys[-1], zs[-1])) + margin
+                m = (xyz < hi).all(-1) & (xyz > lo).all(-1)
+                if not m.any():
+                    continue
+                pairs += int(m.sum()) * s ** 3 if count_pairs else 0
+                pts = torch.stack(torch.meshgrid(xs, ys, zs, indexing="ij"), -1).reshape(-1, 3)
+                mx_, mi, mo = xyz[m], inv[m], opac[m].view(1, -1)
+                val = 0
+                for st in range(0, mx_.shape[0], 1024):
+                    g = pts.unsqueeze(1) - mx_[st:st + 1024].unsqueeze(0)
+                    x, y, z = g[..., 0], g[..., 1], g[..., 2]
+                    q = mi[st:st + 1024]
+                    power = -0.5 * (x ** 2 * q[:, 0] + y ** 2 * q[:, 3] + z ** 2 * q[:, 5]) - x * y * q[:, 1] - x * z * q[:, 2] - y * z * q[:, 4]
+                    power = torch.where(power > 0, torch.full_like(power, -1e10), power)
+                    val = val + (mo[:, st:st + 1024] * torch.exp(power)).sum(-1)
+                occ[xi * s:xi * s + s, yi * s:yi * s + s, zi * s:zi * s + s] = val.reshape(s, s, s)
+    return (occ, pairs) if count_pairs else occ
+
+
+def timed(fn, warmup, runs):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(runs):
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        fn()
+        t1.record()
+        t1.synchronize()
+        ms.append(t0.elapsed_time(t1))
+    return statistics.median(ms), min(ms), max(ms)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--points", type=int, default=100000)
+    ap.add_argument("--runs", type=int, default=7)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--chain-runs", type=int, default=3)
+    ap.add_argument("--once", type=int, default=0)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "field_extract.txt"))
+    args = ap.parse_args()
+    gm = make_model(args.points)
+    if args.once:
+        gm.extract_mesh(resolution=args.once)
+        torch.cuda.synchronize()
+        return
+    lines = ["tools/bench_field.py: %d Gaussians (human cloud, trained look), %s, median [min, max] of %d runs after %d warm-up, ms" % (
+        args.points, "%s (%s)" % (torch.cuda.get_device_name(0), torch.cuda.get_device_properties(0).gcnArchName), args.runs, args.warmup)]
+    for R in (128, 256):
+        field = gm.extract_fields(resolution=R)
+        chain, pairs = op_chain(gm, R, count_pairs=True)
+        diff = float((field - chain).abs().max() / chain.abs().max())
+        v, f = gm.extract_mesh(resolution=R)
+        k = timed(lambda: gm.extract_fields(resolution=R), args.warmup, args.runs)
+        m = timed(lambda: gm.extract_mesh(resolution=R), args.warmup, args.runs)
+        c = timed(lambda: op_chain(gm, R), 1, args.chain_runs)
+        lines.append("R %3d  extract_fields %9.3f [%.3f, %.3f]   extract_mesh %9.3f [%.3f, %.3f] (%d vertices, %d faces)" % (
+            (R,) + k + m + (v.shape[0], f.shape[0])))
+        lines.append("       op chain       %9.3f [%.3f, %.3f] (%d runs)   ratio %.1fx   max |kernel - chain| / max %.2e" % (
+            c + (args.chain_runs, c[0] / k[0], diff)))
+        lines.append("       %.3e point-Gaussian evaluations, %.1f per ns of extract_fields" % (pairs, pairs / (k[0] * 1e6)))
+    text = "\n".join(lines) + "\n"
+    print(text, end="")
+    with open(args.out, "w") as fh:
+        fh.write(text)
+
+
+if __name__ == "__main__":
+    main()

@@ -647,8 +647,74 @@ def ssim():
     print("ssim fixtures written: %d cases" % (len(ssim_inputs.CASES) + 1))
 
 
+def field():
+    """gs_renderer.py:240-331 GaussianModel.extract_fields (with :67-100 gaussian_3d_coeff) on the seeded clouds of
+    tests/field_inputs.py, on the CPU, once in float32 and once in float64.  The file is loaded by path; plyfile,
+    diff_gaussian_rasterization, simple_knn._C and kiui (kiui.sh, kiui.mesh) are stubs.  The float64 run sets torch's default dtype
+    to float64, and, because the file spells `dtype=torch.float` (:52, :130) and `dtype=torch.float32` (:270) next to tensors of the
+    default dtype, torch.zeros maps float32 to the default dtype for that run, so that nothing is rounded to float32 on the way.
+    Stored per case: the float32 field (cases a, b) or its values at field_inputs.sample_voxels() in float32 and float64 (case c),
+    err = max |f32 - f64| / max |f64|, center, scale (of the float32 run).  Asserted: in the float64 run no centre lies within 1e-5
+    of a face of a box it is tested against, so both runs agree on every member and err is rounding alone."""
+    _install_device_shim()
+    _install_stub_modules()
+    for n in ("kiui", "kiui.sh", "kiui.mesh"):
+        sys.modules[n] = _Stub(n)
+    sys.path.insert(0, os.path.dirname(OUT))
+    import field_inputs
+    gsr = _load_by_path("gs_renderer", "gs_renderer.py", "")
+    zeros = torch.zeros
+
+    def zeros_default(*a, **k):
+        if k.get("dtype", None) in (torch.float, torch.float32):
+            k["dtype"] = torch.get_default_dtype()
+        return zeros(*a, **k)
+
+    def run(cl, R, nb, dtype):
+        torch.set_default_dtype(dtype)
+        torch.zeros = zeros_default
+        try:
+            gm = gsr.GaussianModel(0)
+            gm._xyz, gm._opacity = torch.from_numpy(cl["xyz"]).to(dtype), torch.from_numpy(cl["opacity"]).to(dtype)
+            gm._scaling, gm._rotation = torch.from_numpy(cl["scaling"]).to(dtype), torch.from_numpy(cl["rotation"]).to(dtype)
+            occ = gm.extract_fields(resolution=R, num_blocks=nb)
+            assert occ.dtype == dtype
+            return occ, gm
+        finally:
+            torch.zeros = zeros
+            torch.set_default_dtype(torch.float32)
+
+    out = {}
+    for name in sorted(field_inputs.CASES):
+        cl, R, nb = field_inputs.case(name)
+        f32, gm32 = run(cl, R, nb, torch.float32)
+        f64, gm64 = run(cl, R, nb, torch.float64)
+        keep = torch.sigmoid(torch.from_numpy(cl["opacity"]).double()).squeeze(1) > 0.005
+        xn = (torch.from_numpy(cl["xyz"]).double()[keep] - gm64.center) * gm64.scale
+        grid, s, margin = torch.linspace(-1, 1, R, dtype=torch.float64), R // nb, (2 / nb) * 1.5
+        faces = torch.cat((grid[0::s] - margin, grid[s - 1::s] + margin))
+        dist = float((xn.reshape(-1, 1) - faces.reshape(1, -1)).abs().min())
+        assert dist > 1e-5, "case %s: a centre lies %.2e from a box face: change its seed" % (name, dist)
+        err = float((f32.double() - f64).abs().max() / f64.abs().max())
+        print("field case %s: P %d kept %d R %d blocks %d max %.4f err %.3e face distance %.2e" % (
+            name, cl["xyz"].shape[0], int(keep.sum()), R, nb, float(f64.max()), err, dist))
+        out[name + "_err"] = np.float64(err)
+        out[name + "_center"], out[name + "_scale"] = gm32.center.numpy(), np.float64(gm32.scale)
+        if name == "c":
+            at = torch.from_numpy(field_inputs.sample_voxels(R))
+            out["c_samples_f32"], out["c_samples_f64"] = f32.reshape(-1)[at].numpy(), f64.reshape(-1)[at].numpy()
+            out["c_max_f64"] = np.float64(f64.abs().max())
+        else:
+            out[name + "_field"] = f32.numpy()
+            out[name + "_max_f64"] = np.float64(f64.abs().max())
+    np.savez_compressed(os.path.join(OUT, "field.npz"), **out)
+    print("field fixtures written")
+
+
 if __name__ == "__main__":
-    if len(sys.argv) > 1 and sys.argv[1] == "ahds":
+    if len(sys.argv) > 1 and sys.argv[1] == "field":
+        field()
+    elif len(sys.argv) > 1 and sys.argv[1] == "ahds":
         ahds()
     elif len(sys.argv) > 1 and sys.argv[1] == "guidance":
         guidance()
