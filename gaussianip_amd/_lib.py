@@ -201,6 +201,11 @@ def model_lib():
         lib.gip_surface_count.argtypes = [_vp, ctypes.c_int32, ctypes.c_float, _vp, _vp, _vp]
         lib.gip_surface_emit.restype = ctypes.c_int
         lib.gip_surface_emit.argtypes = [_vp, ctypes.c_int32, ctypes.c_float, _vp, _vp, _vp, _vp, _vp, _vp]
+        lib.gip_field_sample_workspace_size.restype = ctypes.c_int
+        lib.gip_field_sample_workspace_size.argtypes = [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_size_t)]
+        lib.gip_field_sample.restype = ctypes.c_int
+        lib.gip_field_sample.argtypes = [_vp, _vp, _vp, _vp, _vp, ctypes.c_int64, _vp, ctypes.c_float, _vp, ctypes.c_int32, ctypes.c_int32,
+                                         ctypes.c_float, _vp, _vp, ctypes.c_int64, _vp, ctypes.c_size_t, _vp, _vp, _vp, _vp]
         _model = _Counted(lib)
     return _model
 
@@ -344,3 +349,4 @@ RASTER_SYMBOLS = ["gip_abi_version", "gip_status_string", "gip_raster_state_byte
                   "gip_raster_state_layout", "gip_raster_forward", "gip_raster_backward", "gip_raster_read_header",
                   "gip_raster_mark_visible", "gip_raster_forward_profiled", "gip_raster_backward_profiled"]
 FIELD_SYMBOLS = ["gip_field_workspace_size", "gip_density_field", "gip_surface_count", "gip_surface_emit"]
+SAMPLE_SYMBOLS = ["gip_field_sample_workspace_size", "gip_field_sample"]

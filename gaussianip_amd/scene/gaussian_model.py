@@ -147,6 +147,34 @@ class GaussianModel:
             self.active_sh_degree += 1
 
     # ------------------------------------------------------------------ density field and mesh (gs_renderer.py:240-361)
+    def _field_geometry(self, what, resolution, num_blocks):
+        """The argument checks shared by extract_fields and sample_fields; (resolution, num_blocks) as ints."""
+        resolution, num_blocks = int(resolution), int(num_blocks)
+        if resolution < 1 or num_blocks < 1 or resolution % num_blocks != 0:
+            raise ValueError("%s: num_blocks (%d) must divide resolution (%d)" % (what, num_blocks, resolution))
+        if num_blocks > 1024:
+            raise ValueError("%s: at most 1024 blocks per axis" % what)
+        if not self._xyz.is_cuda:
+            raise RuntimeError("%s runs on the GPU only (the model's tensors are on %s)" % (what, self._xyz.device))
+        return resolution, num_blocks
+
+    def _field_sources(self):
+        """(mask, xyz, opacity [P], scaling, rotation) of the Gaussians the density field is made of — those with opacity > 0.005 —
+        or None when there are none; sets self.center / self.scale, the normalisation to ~ [-1, 1] (gs_renderer.py:252-261)."""
+        opacities = self.get_opacity.float()
+        mask = (opacities > 0.005).squeeze(1)         # pre-filter, :252
+        opacities = opacities[mask].reshape(-1).contiguous()
+        if int(opacities.shape[0]) == 0:
+            return None
+        xyzs = self.get_xyz.float()[mask].contiguous()
+        stds = self.get_scaling.float()[mask].contiguous()
+        rots = self._rotation.float()[mask].contiguous()
+        mn, mx = xyzs.amin(0), xyzs.amax(0)           # normalise to ~ [-1, 1], :259-261
+        self.center = (mn + mx) / 2
+        extent = (mx - mn).amax().item()
+        self.scale = 1.8 / extent if extent > 0 else 1.0      # a single centre has no extent (the reference divides by zero there)
+        return mask, xyzs, opacities, stds, rots
+
     @torch.no_grad()
     def extract_fields(self, resolution=128, num_blocks=16, relax_ratio=1.5):
         """The density of the Gaussians on a resolution^3 grid over the normalised cloud ([R, R, R] float32, `ij` order), the
@@ -157,28 +185,14 @@ class GaussianModel:
         import ctypes
 
         from .. import _lib
-        resolution, num_blocks = int(resolution), int(num_blocks)
-        if resolution < 1 or num_blocks < 1 or resolution % num_blocks != 0:
-            raise ValueError("extract_fields: num_blocks (%d) must divide resolution (%d)" % (num_blocks, resolution))
-        if num_blocks > 1024:
-            raise ValueError("extract_fields: at most 1024 blocks per axis")
-        if not self._xyz.is_cuda:
-            raise RuntimeError("extract_fields runs on the GPU only (the model's tensors are on %s)" % self._xyz.device)
+        resolution, num_blocks = self._field_geometry("extract_fields", resolution, num_blocks)
         dev = self._xyz.device
         occ = torch.zeros((resolution,) * 3, dtype=torch.float32, device=dev)
-        opacities = self.get_opacity.float()
-        mask = (opacities > 0.005).squeeze(1)         # pre-filter, :252
-        opacities = opacities[mask].reshape(-1).contiguous()
-        P = int(opacities.shape[0])
-        if P == 0:
+        src = self._field_sources()
+        if src is None:
             return occ
-        xyzs = self.get_xyz.float()[mask].contiguous()
-        stds = self.get_scaling.float()[mask].contiguous()
-        rots = self._rotation.float()[mask].contiguous()
-        mn, mx = xyzs.amin(0), xyzs.amax(0)           # normalise to ~ [-1, 1], :259-261
-        self.center = (mn + mx) / 2
-        extent = (mx - mn).amax().item()
-        self.scale = 1.8 / extent if extent > 0 else 1.0      # a single centre has no extent (the reference divides by zero there)
+        _, xyzs, opacities, stds, rots = src
+        P = int(opacities.shape[0])
         grid = torch.linspace(-1, 1, resolution, dtype=torch.float32).to(dev)      # the host's values: the cut below depends on their bits
         margin = (2 / num_blocks) * relax_ratio       # rounded to float32 on the way in, like `vmin -= block_size * relax_ratio`
         lib = _lib.model_lib()
@@ -211,6 +225,118 @@ class GaussianModel:
             os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
             mesh.write_obj(path, vertices, faces)
         return vertices, faces
+
+    def _sample(self, what, u, block, colors, resolution, num_blocks, relax_ratio):
+        """density [V], gradient [V, 3] (normalised space) and colour sum [V, 3] at the normalised points u [V, 3], each evaluated in
+        the block `block` [V] (int64, (bx * nb + by) * nb + bz) — one call of gip_field_sample (csrc/field_sample.hip).  Outputs in
+        the caller's order.  `colors`: [N, 3] per Gaussian of the model (before the opacity prefilter), None = the base colour."""
+        import ctypes
+
+        from .. import _lib
+        from ..utils.sh import C0
+        dev = self._xyz.device
+        V = int(u.shape[0])
+        out = {"density": torch.zeros(V, dtype=torch.float32, device=dev), "gradient": torch.zeros((V, 3), dtype=torch.float32, device=dev),
+               "color_sum": torch.zeros((V, 3), dtype=torch.float32, device=dev)}
+        if colors is None:
+            colors = (0.5 + C0 * self._features_dc.float().reshape(-1, 3)).clamp(0, 1)
+        if not (isinstance(colors, torch.Tensor) and colors.device == dev and colors.dim() == 2 and
+                tuple(colors.shape) == (self._xyz.shape[0], 3)):
+            raise ValueError("%s: colors must be an [N, 3] tensor on the model's device, one row per Gaussian" % what)
+        src = self._field_sources()
+        if src is None or V == 0:
+            return out
+        mask, xyzs, opacities, stds, rots = src
+        rgb = colors.float()[mask].contiguous()
+        P = int(opacities.shape[0])
+        order = torch.sort(block, stable=True).indices            # grouped by block, the caller's order kept inside a block
+        counts = torch.bincount(block, minlength=num_blocks ** 3)
+        block_start = torch.cat((counts.new_zeros(1), counts.cumsum(0))).to(torch.int32)
+        pts = u[order].contiguous()
+        grid = torch.linspace(-1, 1, resolution, dtype=torch.float32).to(dev)      # as in extract_fields: membership depends on their bits
+        margin = (2 / num_blocks) * relax_ratio
+        lib = _lib.model_lib()
+        need = ctypes.c_size_t(0)
+        rc = lib.gip_field_sample_workspace_size(P, resolution, num_blocks, ctypes.byref(need))
+        if rc != 0:
+            raise RuntimeError("gip_field_sample_workspace_size failed with status %d" % rc)
+        ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+        dens, grad, csum = (torch.empty_like(out[k]) for k in ("density", "gradient", "color_sum"))
+        p = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+        with torch.cuda.device(dev):
+            rc = lib.gip_field_sample(p(xyzs), p(opacities), p(stds), p(rots), p(rgb), P, p(self.center.contiguous()), self.scale, p(grid),
+                                      resolution, num_blocks, margin, p(pts), p(block_start), V, p(ws), need.value, p(dens), p(grad),
+                                      p(csum), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        if rc != 0:
+            raise RuntimeError("gip_field_sample failed with status %d" % rc)
+        out["density"][order], out["gradient"][order], out["color_sum"][order] = dens, grad, csum
+        return out
+
+    @staticmethod
+    def _blend(color_sum, density):
+        """color_sum / density where density > 0, else 0."""
+        d = density.unsqueeze(1)
+        return torch.where(d > 0, color_sum / d.clamp_min(torch.finfo(torch.float32).tiny), torch.zeros_like(color_sum))
+
+    @torch.no_grad()
+    def sample_fields(self, points, colors=None, resolution=128, num_blocks=16, relax_ratio=1.5, normalized=False):
+        """{"density": [V], "gradient": [V, 3], "color": [V, 3]} of the density field at `points` ([V, 3] float32 GPU tensor, world
+        coordinates, or normalised ones with normalized=True), in the caller's order.  The field is extract_fields': the same
+        sources, normalisation, blocks and membership for the same (resolution, num_blocks, relax_ratio); a point is evaluated
+        in the block of the last grid value <= its coordinate per axis (points outside the grid: the edge blocks), so a grid point
+        gives its voxel of extract_fields.  gradient is d density / d point in world units; color is the weight-blended `colors`
+        ([N, 3] per Gaussian; default the view-independent base colour 0.5 + C0 * features_dc, clamped to [0, 1]), 0 where the
+        density is 0.  Raises like extract_fields, and ValueError for points that are not a [V, 3] float32 GPU tensor."""
+        resolution, num_blocks = self._field_geometry("sample_fields", resolution, num_blocks)
+        if not (isinstance(points, torch.Tensor) and points.is_cuda and points.dtype == torch.float32 and points.dim() == 2 and
+                points.shape[1] == 3):
+            raise ValueError("sample_fields needs a [V, 3] float32 GPU tensor of points")
+        dev = self._xyz.device
+        points = points.detach().to(dev)
+        src = self._field_sources()                   # sets center / scale; None: nothing passes the prefilter, every sum is empty
+        if normalized or src is None:
+            u = points
+        else:
+            u = (points - self.center) * self.scale
+        grid = torch.linspace(-1, 1, resolution, dtype=torch.float32).to(dev)
+        cell = (torch.bucketize(u.contiguous(), grid, right=True) - 1).clamp(0, resolution - 1) // (resolution // num_blocks)
+        block = (cell[:, 0] * num_blocks + cell[:, 1]) * num_blocks + cell[:, 2]
+        out = self._sample("sample_fields", u, block, colors, resolution, num_blocks, relax_ratio)
+        scale = self.scale if src is not None else 1.0
+        return {"density": out["density"], "gradient": out["gradient"] * scale, "color": self._blend(out["color_sum"], out["density"])}
+
+    @torch.no_grad()
+    def extract_mesh_with_attributes(self, path=None, density_thresh=1.0, resolution=128, num_blocks=16, relax_ratio=1.5, colors=None):
+        """(vertices [V, 3] float32, faces [F, 3] int32, normals [V, 3] float32, colors [V, 3] float32 in [0, 1]): extract_mesh's
+        vertices and faces, bit for bit, with the Gaussians sampled at the vertices (sample_fields' sums; a vertex is evaluated in the
+        block of the grid point that owns its edge).  normals = -gradient / |gradient|: analytic, toward decreasing density like the
+        faces' winding, zero where the gradient is zero.  colors: the blend of `colors` (default: the base colour), which must lie
+        in [0, 1] for the result to.  `path` ending in .ply writes a binary PLY, any other path a Wavefront OBJ."""
+        from ..utils import mesh
+        resolution, num_blocks = self._field_geometry("extract_mesh_with_attributes", resolution, num_blocks)
+        occ = self.extract_fields(resolution, num_blocks, relax_ratio)
+        v, faces = mesh.extract_surface(occ, density_thresh)
+        vertices = v
+        if v.shape[0]:
+            vertices = v / (resolution - 1.0) * 2 - 1
+            u = vertices
+            vertices = vertices / self.scale + self.center       # back to the original space, as extract_mesh
+            cell = v.floor().long().clamp(0, resolution - 1) // (resolution // num_blocks)
+            block = (cell[:, 0] * num_blocks + cell[:, 1]) * num_blocks + cell[:, 2]
+            out = self._sample("extract_mesh_with_attributes", u, block, colors, resolution, num_blocks, relax_ratio)
+            g = out["gradient"].double()
+            n = g.norm(dim=1, keepdim=True)
+            normals = torch.where(n > 0, -g / n.clamp_min(1e-300), torch.zeros_like(g)).float()
+            vcolors = self._blend(out["color_sum"], out["density"])
+        else:
+            normals, vcolors = torch.zeros_like(v), torch.zeros_like(v)
+        if path is not None:
+            os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+            if str(path).lower().endswith(".ply"):
+                mesh.write_ply_mesh(path, vertices, faces, colors=vcolors, normals=normals)
+            else:
+                mesh.write_obj(path, vertices, faces, colors=vcolors, normals=normals)
+        return vertices, faces, normals, vcolors
 
     # ------------------------------------------------------------------ initialisation
     def create_from_pcd(self, pcd: BasicPointCloud, spatial_lr_scale: float, dist2=None):

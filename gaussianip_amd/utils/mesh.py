@@ -1,5 +1,6 @@
 """Iso-surface of a regular grid as an indexed triangle mesh (csrc/field.hip: marching tetrahedra on the Kuhn decomposition;
-include/gip_model.h gip_surface_count / gip_surface_emit), and a Wavefront OBJ writer / reader for it.
+include/gip_model.h gip_surface_count / gip_surface_emit), and Wavefront OBJ / binary PLY writers and readers for it, with optional
+per-vertex colours and normals.
 
 The reference hands its density grid to the third-party `mcubes` (gs_renderer.py:338-340); here the surface is extracted on the
 GPU.  There is no CPU path: a tensor that is not a float32 GPU tensor is an error."""
@@ -50,19 +51,37 @@ def extract_surface(field, threshold):
     return vertices, faces
 
 
-def write_obj(path, vertices, faces):
-    """Wavefront OBJ: `v x y z` lines (9 significant digits: a float32 survives the round trip), `f a b c` lines, 1-based."""
-    v = np.asarray(vertices.detach().cpu() if isinstance(vertices, torch.Tensor) else vertices, dtype=np.float32)
-    f = np.asarray(faces.detach().cpu() if isinstance(faces, torch.Tensor) else faces, dtype=np.int64) + 1
+def _array(t, dtype):
+    return np.asarray(t.detach().cpu() if isinstance(t, torch.Tensor) else t, dtype=dtype)
+
+
+def write_obj(path, vertices, faces, colors=None, normals=None):
+    """Wavefront OBJ: `v x y z` lines (9 significant digits: a float32 survives the round trip), `f a b c` lines, 1-based.  With
+    `colors` ([V, 3] in [0, 1]) the vertex lines become `v x y z r g b` (the common vertex-colour extension); with `normals` ([V, 3])
+    the file gains one `vn` line per vertex and the faces are written `f a//a b//b c//c`."""
+    v = _array(vertices, np.float32)
+    f = _array(faces, np.int64) + 1
+    col = None if colors is None else _array(colors, np.float32).reshape(-1, 3)
+    nrm = None if normals is None else _array(normals, np.float32).reshape(-1, 3)
+    if (col is not None and col.shape[0] != v.shape[0]) or (nrm is not None and nrm.shape[0] != v.shape[0]):
+        raise ValueError("write_obj: colors and normals need one row per vertex")
     with open(path, "w") as out:
         out.write("# %d vertices, %d faces\n" % (v.shape[0], f.shape[0]))
-        out.write("".join("v %.9g %.9g %.9g\n" % (float(a), float(b), float(c)) for a, b, c in v))
-        out.write("".join("f %d %d %d\n" % (a, b, c) for a, b, c in f))
+        if col is None:
+            out.write("".join("v %.9g %.9g %.9g\n" % (float(a), float(b), float(c)) for a, b, c in v))
+        else:
+            out.write("".join("v %.9g %.9g %.9g %.9g %.9g %.9g\n" % tuple(float(x) for x in row) for row in np.concatenate((v, col), 1)))
+        if nrm is None:
+            out.write("".join("f %d %d %d\n" % (a, b, c) for a, b, c in f))
+        else:
+            out.write("".join("vn %.9g %.9g %.9g\n" % (float(a), float(b), float(c)) for a, b, c in nrm))
+            out.write("".join("f %d//%d %d//%d %d//%d\n" % (a, a, b, b, c, c) for a, b, c in f))
 
 
-def read_obj(path):
-    """(vertices [V, 3] float32, faces [F, 3] int32, 0-based) of an OBJ that write_obj wrote (v and triangular f lines only)."""
-    v, f = [], []
+def read_obj_full(path):
+    """(vertices [V, 3] float32, faces [F, 3] int32 0-based, colors [V, 3] float32 or None, normals [V, 3] float32 or None) of an OBJ
+    that write_obj wrote: colours are the fourth to sixth number of the `v` lines, normals the `vn` lines."""
+    v, f, c, n = [], [], [], []
     with open(path) as src:
         for line in src:
             parts = line.split()
@@ -70,6 +89,98 @@ def read_obj(path):
                 continue
             if parts[0] == "v":
                 v.append([float(x) for x in parts[1:4]])
+                if len(parts) >= 7:
+                    c.append([float(x) for x in parts[4:7]])
+            elif parts[0] == "vn":
+                n.append([float(x) for x in parts[1:4]])
             elif parts[0] == "f":
                 f.append([int(x.split("/")[0]) - 1 for x in parts[1:4]])
-    return np.asarray(v, np.float32).reshape(-1, 3), np.asarray(f, np.int32).reshape(-1, 3)
+    if c and len(c) != len(v):
+        raise ValueError("%s: some vertices carry a colour and some do not" % path)
+    return (np.asarray(v, np.float32).reshape(-1, 3), np.asarray(f, np.int32).reshape(-1, 3),
+            np.asarray(c, np.float32).reshape(-1, 3) if c else None, np.asarray(n, np.float32).reshape(-1, 3) if n else None)
+
+
+def read_obj(path):
+    """(vertices [V, 3] float32, faces [F, 3] int32, 0-based) of an OBJ that write_obj wrote; colours and normals, if the file has
+    them, are left to read_obj_full."""
+    return read_obj_full(path)[:2]
+
+
+def write_ply_mesh(path, vertices, faces, colors=None, normals=None):
+    """Binary little-endian PLY: vertex x y z float32, then nx ny nz float32 (with `normals`), then red green blue uchar (with
+    `colors`, rounded from [0, 1]); face `list uchar int vertex_indices`.  The layout MeshLab and Blender read vertex colours from."""
+    v = _array(vertices, np.float32).reshape(-1, 3)
+    f = _array(faces, np.int32).reshape(-1, 3)
+    fields, props = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")], ["property float x", "property float y", "property float z"]
+    if normals is not None:
+        fields += [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
+        props += ["property float nx", "property float ny", "property float nz"]
+    if colors is not None:
+        fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+        props += ["property uchar red", "property uchar green", "property uchar blue"]
+    table = np.zeros(v.shape[0], dtype=fields)
+    cols = [("x", "y", "z", v)]
+    if normals is not None:
+        cols.append(("nx", "ny", "nz", _array(normals, np.float32).reshape(-1, 3)))
+    if colors is not None:
+        cols.append(("red", "green", "blue", np.rint(np.clip(_array(colors, np.float64).reshape(-1, 3), 0, 1) * 255).astype(np.uint8)))
+    for a, b, c, src in cols:
+        if src.shape[0] != v.shape[0]:
+            raise ValueError("write_ply_mesh: colors and normals need one row per vertex")
+        table[a], table[b], table[c] = src[:, 0], src[:, 1], src[:, 2]
+    tris = np.zeros(f.shape[0], dtype=[("n", "u1"), ("idx", "<i4", (3,))])
+    tris["n"], tris["idx"] = 3, f
+    header = ["ply", "format binary_little_endian 1.0", "element vertex %d" % v.shape[0]] + props + \
+             ["element face %d" % f.shape[0], "property list uchar int vertex_indices", "end_header"]
+    with open(path, "wb") as out:
+        out.write(("\n".join(header) + "\n").encode("ascii"))
+        out.write(table.tobytes())
+        out.write(tris.tobytes())
+
+
+_PLY_TYPES = {"float": "<f4", "float32": "<f4", "uchar": "u1", "uint8": "u1", "int": "<i4", "int32": "<i4"}
+
+
+def read_ply_mesh(path):
+    """(vertices [V, 3] float32, faces [F, 3] int32, colors [V, 3] float32 in [0, 1] or None, normals [V, 3] float32 or None) of a
+    PLY that write_ply_mesh wrote (binary little-endian, triangles only)."""
+    with open(path, "rb") as src:
+        if src.readline().strip() != b"ply":
+            raise ValueError("%s is not a PLY file" % path)
+        fmt, element, counts, vprops, fprop = None, None, {}, [], None
+        while True:
+            line = src.readline()
+            if not line:
+                raise ValueError("%s: no end_header" % path)
+            parts = line.decode("ascii").split()
+            if not parts or parts[0] == "comment":
+                continue
+            if parts[0] == "format":
+                fmt = parts[1]
+            elif parts[0] == "element":
+                element = parts[1]
+                counts[element] = int(parts[2])
+            elif parts[0] == "property" and element == "vertex":
+                vprops.append((parts[2], _PLY_TYPES[parts[1]]))
+            elif parts[0] == "property" and element == "face":
+                fprop = parts[1:]
+            elif parts[0] == "end_header":
+                break
+        if fmt != "binary_little_endian":
+            raise ValueError("unsupported PLY format %r" % fmt)
+        if counts.get("face", 0) and (fprop is None or fprop[0] != "list" or _PLY_TYPES[fprop[1]] != "u1" or _PLY_TYPES[fprop[2]] != "<i4"):
+            raise ValueError("%s: faces must be `list uchar int`" % path)
+        nv, nf = counts.get("vertex", 0), counts.get("face", 0)
+        vdt = np.dtype(vprops)
+        table = np.frombuffer(src.read(nv * vdt.itemsize), dtype=vdt, count=nv)
+        fdt = np.dtype([("n", "u1"), ("idx", "<i4", (3,))])
+        tris = np.frombuffer(src.read(nf * fdt.itemsize), dtype=fdt, count=nf)
+    if nf and (tris["n"] != 3).any():
+        raise ValueError("%s: only triangles are supported" % path)
+    names = set(vdt.names)
+    pick = lambda keys: np.stack([table[k] for k in keys], 1)  # noqa: E731
+    vertices = pick(("x", "y", "z")).astype(np.float32).reshape(-1, 3)
+    normals = pick(("nx", "ny", "nz")).astype(np.float32).reshape(-1, 3) if {"nx", "ny", "nz"} <= names else None
+    colors = (pick(("red", "green", "blue")).astype(np.float32) / 255).reshape(-1, 3) if {"red", "green", "blue"} <= names else None
+    return vertices, tris["idx"].astype(np.int32).reshape(-1, 3), colors, normals

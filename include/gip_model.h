@@ -143,6 +143,25 @@ int gip_density_field(const float* xyz, const float* opacity, const float* scali
 int gip_surface_count(const float* field, int32_t R, float threshold, int32_t* edge_flag, int32_t* tri_count, void* stream);
 int gip_surface_emit(const float* field, int32_t R, float threshold, const int32_t* edge_flag, const int32_t* edge_index,
                      const int32_t* tri_offset, float* vertices, int32_t* faces, void* stream);
+/* The same field asked for at arbitrary points (csrc/field_sample.hip): vertex colours and analytic normals of the mesh above.
+ *   gip_field_sample  for each of V query points, given in NORMALISED coordinates and grouped by the block they are evaluated in
+ *       (points [V, 3]; block_start [num_blocks^3 + 1] int32 exclusive offsets into points, block id = (bx * nb + by) * nb + bz;
+ *       the CALLER decides a point's block), the sums over that block's members of
+ *           density   [V]     sum w,              w = opacity * exp(-0.5 d^T Sigma^-1 d), d = x - xyz', a positive power counting as 0
+ *           gradient  [V, 3]  sum w * (-Sigma^-1 d)   (the gradient of the density in normalised space; or NULL)
+ *           color_sum [V, 3]  sum w * rgb             (raw: dividing by density is the caller's; or NULL, rgb [P, 3] may then be NULL)
+ *       Sources, normalisation, inverse covariance, blocks, membership and `margin` are gip_density_field's, argument for argument;
+ *       at a grid point evaluated in its own block, density is bit for bit that voxel of gip_density_field.  A block without points
+ *       costs nothing but its launch; members are added in the order of the arrays, no float atomics: two runs are bitwise equal.
+ *       V == 0 is a successful no-op; P == 0 fills the outputs with zeros.  No host read.
+ *   gip_field_sample_workspace_size  bytes of `workspace` (a record and a block-range word per Gaussian).
+ * Status 1: a NULL required pointer, a shape outside gip_density_field's limits, V > 2^31 - 1, a short workspace, rgb == NULL while
+ * color_sum != NULL. */
+int gip_field_sample_workspace_size(int64_t P, int32_t R, int32_t num_blocks, size_t* bytes);
+int gip_field_sample(const float* xyz, const float* opacity, const float* scaling, const float* rotation, const float* rgb, int64_t P,
+                     const float* center, float scale, const float* grid, int32_t R, int32_t num_blocks, float margin,
+                     const float* points, const int32_t* block_start, int64_t V, void* workspace, size_t workspace_bytes,
+                     float* density, float* gradient, float* color_sum, void* stream);
 #ifdef __cplusplus
 }
 #endif

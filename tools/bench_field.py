@@ -5,7 +5,10 @@ statement of that op chain: one masked gather and a [voxels, members] evaluation
 
 hipEvent timing around each call, warm-up runs first, the median of the timed runs.  Usage:
     python tools/bench_field.py [--points 100000] [--runs 7] [--warmup 2] [--chain-runs 3] [--out profiles/field_extract.txt]
-    python tools/bench_field.py --once 128      one extract_fields + extract_mesh call (for a kernel trace)"""
+    python tools/bench_field.py --once 128      one extract_fields + extract_mesh call (for a kernel trace)
+    python tools/bench_field.py --attributes    extract_mesh_with_attributes (csrc/field_sample.hip) next to extract_mesh at the default
+                                                geometry (R 128, 16 blocks), and the same three sums at the same vertices as a
+                                                chunked dense evaluation in PyTorch ops (--out defaults to profiles/field_sample.txt)"""
 import argparse
 import os
 import statistics
@@ -75,6 +78,69 @@ def op_chain(gm, resolution, num_blocks=16, relax_ratio=1.5, count_pairs=False):
     return (occ, pairs) if count_pairs else occ
 
 
+@torch.no_grad()
+def dense_sample(gm, u, block, rgb, resolution=128, num_blocks=16, relax_ratio=1.5, chunk=1024):
+    """density, gradient and colour sum at the normalised points u, point i in block[i], as PyTorch ops: every point of a chunk
+    meets every Gaussian and non-members are masked (this file's statement of what csrc/field_sample.hip computes)."""
+    from gaussianip_amd.utils.general import build_scaling_rotation
+    dev = gm._xyz.device
+    opac = torch.sigmoid(gm._opacity)
+    keep = (opac > 0.005).squeeze(1)
+    opac, xyz, std, rot, rgb = opac[keep].view(1, -1), gm._xyz[keep], torch.exp(gm._scaling[keep]), gm._rotation[keep], rgb[keep]
+    mn, mx = xyz.amin(0), xyz.amax(0)
+    center, scale = (mn + mx) / 2, 1.8 / (mx - mn).amax().item()
+    xyz, std = (xyz - center) * scale, std * scale
+    L = build_scaling_rotation(std, rot)
+    S = L @ L.transpose(1, 2)
+    a, b, c, d, e, f = S[:, 0, 0], S[:, 0, 1], S[:, 0, 2], S[:, 1, 1], S[:, 1, 2], S[:, 2, 2]
+    inv_det = 1 / (a * d * f + 2 * e * c * b - e ** 2 * a - c ** 2 * d - b ** 2 * f + 1e-24)
+    ia, ib, ic = (d * f - e ** 2) * inv_det, (e * c - b * f) * inv_det, (e * b - c * d) * inv_det
+    id_, ie, if_ = (a * f - c ** 2) * inv_det, (b * c - e * a) * inv_det, (a * d - b ** 2) * inv_det
+    s, margin = resolution // num_blocks, (2 / num_blocks) * relax_ratio
+    grid = torch.linspace(-1, 1, resolution).to(dev)
+    lo, hi = grid[0::s] - margin, grid[s - 1::s] + margin
+    inside = (xyz.unsqueeze(-1) > lo) & (xyz.unsqueeze(-1) < hi)                      # [P, 3, nb]
+    bx, by, bz = block // (num_blocks * num_blocks), (block // num_blocks) % num_blocks, block % num_blocks
+    dens, grad, csum = [], [], []
+    for st in range(0, u.shape[0], chunk):
+        sl = slice(st, st + chunk)
+        m = (inside[:, 0, bx[sl]] & inside[:, 1, by[sl]] & inside[:, 2, bz[sl]]).t()  # [v, P]
+        x, y, z = (u[sl, k:k + 1] - xyz[:, k].unsqueeze(0) for k in range(3))
+        power = -0.5 * (x ** 2 * ia + y ** 2 * id_ + z ** 2 * if_) - x * y * ib - x * z * ic - y * z * ie
+        w = torch.where(m & ~(power > 0), opac * torch.exp(power.clamp_max(0)), torch.zeros_like(power))
+        dens.append(w.sum(1))
+        grad.append(torch.stack(((w * -(ia * x + ib * y + ic * z)).sum(1), (w * -(ib * x + id_ * y + ie * z)).sum(1),
+                                 (w * -(ic * x + ie * y + if_ * z)).sum(1)), 1))
+        csum.append(w @ rgb)
+    return torch.cat(dens), torch.cat(grad), torch.cat(csum)
+
+
+def attributes(gm, args):
+    """extract_mesh, extract_mesh_with_attributes and the dense PyTorch evaluation at the default geometry."""
+    from gaussianip_amd.utils import mesh
+    R, nb = 128, 16
+    rgb = torch.rand(gm._xyz.shape[0], 3, device="cuda", generator=torch.Generator(device="cuda").manual_seed(0))
+    v, f, n, c = gm.extract_mesh_with_attributes(resolution=R, num_blocks=nb, colors=rgb)
+    idx, _ = mesh.extract_surface(gm.extract_fields(resolution=R, num_blocks=nb), 1.0)       # the vertices in grid-index units
+    u = idx / (R - 1.0) * 2 - 1
+    cell = idx.floor().long().clamp(0, R - 1) // (R // nb)
+    block = (cell[:, 0] * nb + cell[:, 1]) * nb + cell[:, 2]
+    occupied = int(torch.unique(block).numel())
+    dens, grad, csum = dense_sample(gm, u, block, rgb, R, nb)
+    got = gm._sample("bench_field", u, block, rgb, R, nb, 1.5)
+    diffs = [float((got[k] - ref).abs().max() / ref.abs().max()) for k, ref in (("density", dens), ("gradient", grad), ("color_sum", csum))]
+    m = timed(lambda: gm.extract_mesh(resolution=R, num_blocks=nb), args.warmup, args.runs)
+    a = timed(lambda: gm.extract_mesh_with_attributes(resolution=R, num_blocks=nb, colors=rgb), args.warmup, args.runs)
+    k = timed(lambda: gm._sample("bench_field", u, block, rgb, R, nb, 1.5), args.warmup, args.runs)
+    t = timed(lambda: dense_sample(gm, u, block, rgb, R, nb), 1, args.chain_runs)
+    return ["R %3d  extract_mesh %9.3f [%.3f, %.3f]   extract_mesh_with_attributes %9.3f [%.3f, %.3f]" % ((R,) + m + a),
+            "       %d vertices, %d faces, %d of %d blocks hold a vertex" % (v.shape[0], f.shape[0], occupied, nb ** 3),
+            "       sampling alone (sort by block + gip_field_sample) %9.3f [%.3f, %.3f]" % k,
+            "       dense PyTorch evaluation at the same vertices %9.3f [%.3f, %.3f] (%d runs)   ratio to sampling %.1fx" % (
+                t + (args.chain_runs, t[0] / k[0])),
+            "       max |kernel - dense| / max: density %.2e, gradient %.2e, color_sum %.2e" % tuple(diffs)]
+
+
 def timed(fn, warmup, runs):
     for _ in range(warmup):
         fn()
@@ -97,8 +163,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--chain-runs", type=int, default=3)
     ap.add_argument("--once", type=int, default=0)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "field_extract.txt"))
+    ap.add_argument("--attributes", action="store_true")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "field_sample.txt" if args.attributes else "field_extract.txt")
     gm = make_model(args.points)
     if args.once:
         gm.extract_mesh(resolution=args.once)
@@ -106,7 +175,9 @@ def main():
         return
     lines = ["tools/bench_field.py: %d Gaussians (human cloud, trained look), %s, median [min, max] of %d runs after %d warm-up, ms" % (
         args.points, "%s (%s)" % (torch.cuda.get_device_name(0), torch.cuda.get_device_properties(0).gcnArchName), args.runs, args.warmup)]
-    for R in (128, 256):
+    if args.attributes:
+        lines += attributes(gm, args)
+    for R in (() if args.attributes else (128, 256)):
         field = gm.extract_fields(resolution=R)
         chain, pairs = op_chain(gm, R, count_pairs=True)
         diff = float((field - chain).abs().max() / chain.abs().max())
