@@ -52,9 +52,10 @@ def _check_forward(oracle, kind, P, H, W, seed, sh_degree, cam_args, bg=(0.0, 0.
     return _check_forward_scene(oracle, sc, cam, H, W, sh_degree, bg, nc_mismatch_frac)[0]
 
 
-def _check_forward_scene(oracle, sc, cam, H, W, sh_degree, bg=(0.0, 0.0, 0.0), nc_mismatch_frac=2e-4, min_keep=0.5):
+def _check_forward_scene(oracle, sc, cam, H, W, sh_degree, bg=(0.0, 0.0, 0.0), nc_mismatch_frac=2e-4, min_keep=0.5, stats=None):
     """Forward of one view through the C-ABI against the oracle: integer buffers bit-exact, images within IMG_TOL.
-    Returns (num_rendered, oracle object with its forward state) so a backward comparison can follow."""
+    Returns (num_rendered, oracle object with its forward state) so a backward comparison can follow.
+    `stats`: a dict that receives the library's header words and the number of (proven knife-edge) pixels out of tolerance."""
     from gaussianip_amd import rasterizer as R
     ro, (o_color, o_radii, o_depth, o_alpha) = _oracle_forward(oracle, sc, cam, H, W, bg, sh_degree)
     st = _settings(cam, H, W, bg, sh_degree)
@@ -81,7 +82,12 @@ def _check_forward_scene(oracle, sc, cam, H, W, sh_degree, bg=(0.0, 0.0, 0.0), n
     else:
         nc_expected = compare_tile_lists(sv, hdr, geom, keys, vals, ranges, tt, nc, H, W, min_keep=min_keep)
     # ---- images ----
-    _assert_images(ro, color[0], depth[0], alpha[0], o_color, o_depth, o_alpha, sv["n_contrib"][0], nc_expected, nc_mismatch_frac)
+    n_out = _assert_images(ro, color[0], depth[0], alpha[0], o_color, o_depth, o_alpha, sv["n_contrib"][0], nc_expected,
+                           nc_mismatch_frac)
+    if stats is not None:
+        ts = sv["tile_start"].cpu().numpy().astype(np.int64)
+        stats.update(num_rendered=int(hdr[1]), max_tile_count=int(hdr[3]), num_segments=int(hdr[5]), pixels_out_of_tolerance=n_out,
+                     n_contrib_median=float(np.median(sv["n_contrib"][0].cpu().numpy())), lists_median=int(np.median(ts[1:] - ts[:-1])))
     return Rn, ro
 
 
@@ -132,8 +138,9 @@ def compare_tile_lists(sv, hdr, geom, keys, vals, ranges, tt, nc, H, W, min_keep
     assert np.array_equal(rec_u[:, 7].astype(np.int64), np.bincount(g_idx, minlength=P)), "tiles_touched of the kept lists"
     # dropped entries are dead (float64 evaluation of the fork's test on every pixel of the tile, no margin needed: the
     # library's bound is conservative by > 1 %)
-    d = np.flatnonzero(~kept)
-    if d.size:
+    dropped = np.flatnonzero(~kept)
+
+    def contributes(d):
         co = geom["conic_opacity"][o_idx[d]].astype(np.float64)
         mx, my = geom["means2D"][o_idx[d], 0].astype(np.float64), geom["means2D"][o_idx[d], 1].astype(np.float64)
         x0, y0 = (o_tile[d] % tiles_x) * 16.0, (o_tile[d] // tiles_x) * 16.0
@@ -142,7 +149,18 @@ def compare_tile_lists(sv, hdr, geom, keys, vals, ranges, tt, nc, H, W, min_keep
         dy = (my - y0)[:, None, None] - off[None, :, None]
         power = -0.5 * (co[:, 0, None, None] * dx * dx + co[:, 2, None, None] * dy * dy) - co[:, 1, None, None] * dx * dy
         a = np.minimum(0.99, co[:, 3, None, None] * np.exp(np.minimum(power, 0.0)))
-        assert not ((power <= 0) & (a >= 1.0 / 255.0)).any(), "a dropped instance would have contributed"
+        return bool(((power <= 0) & (a >= 1.0 / 255.0)).any())
+
+    # in blocks of 1024 entries (256 float64 per entry and temporary: a million dropped entries would not fit at once), a few
+    # blocks at a time (numpy releases the interpreter lock inside its loops)
+    blocks = [dropped[s:s + 1024] for s in range(0, dropped.size, 1024)]
+    if len(blocks) > 8:
+        from concurrent.futures import ThreadPoolExecutor
+        with ThreadPoolExecutor(4) as pool:
+            alive = any(pool.map(contributes, blocks))
+    else:
+        alive = any(contributes(b) for b in blocks)
+    assert not alive, "a dropped instance would have contributed"
     # n_contrib: position of the last contributor, counted in the kept list of its tile
     ck = np.concatenate([[0], np.cumsum(kept)])
     tile_of_pixel = (np.arange(H)[:, None] // 16) * tiles_x + (np.arange(W)[None, :] // 16)

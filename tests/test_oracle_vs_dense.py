@@ -7,9 +7,10 @@ import torch
 from dense_reference import dense_render, look_at_camera, random_scene
 
 
-def _run(oracle, P, H, W, seed, sh_degree=0, use_cov=False, use_colors=False, bgval=(0.2, 0.5, 0.9), cam=(10.0, 40.0, 1.6, 60.0)):
+def _run(oracle, P, H, W, seed, sh_degree=0, use_cov=False, use_colors=False, bgval=(0.2, 0.5, 0.9), cam=(10.0, 40.0, 1.6, 60.0),
+         scene_kw=None):
     M = (sh_degree + 1) ** 2
-    sc = random_scene(P, seed, sh_M=M)
+    sc = random_scene(P, seed, sh_M=M, **(scene_kw or {}))
     view, proj, campos, tanx, tany = look_at_camera(cam[0], cam[1], cam[2], cam[3], H, W)
     bg = torch.tensor(bgval, dtype=torch.float64)
     leaves = {k: v.clone().requires_grad_(True) for k, v in sc.items()}
@@ -73,7 +74,11 @@ def test_forward_matches_dense(oracle, P, H, W, seed, deg):
 
 
 def _grad_check(oracle, **kwargs):
-    sc, leaves, m2d, cov_leaf, col_leaf, out, ro, (color, radii, depth, alpha) = _run(oracle, **kwargs)
+    _grad_compare(_run(oracle, **kwargs))
+
+
+def _grad_compare(run):
+    sc, leaves, m2d, cov_leaf, col_leaf, out, ro, (color, radii, depth, alpha) = run
     H, W = color.shape[1:]
     g = torch.Generator().manual_seed(99)
     gC = torch.randn(3, H, W, generator=g, dtype=torch.float64)
@@ -114,6 +119,26 @@ def test_backward_matches_autograd_precomp(oracle):
 
 def test_backward_black_bg_dense_scene(oracle):
     _grad_check(oracle, P=300, H=64, W=64, seed=33, sh_degree=0, bgval=(0.0, 0.0, 0.0), cam=(5.0, 90.0, 1.8, 70.0))
+
+
+def test_deep_one_tile_list_matches_dense(oracle):
+    """One 16 x 16 tile under 2400 large, nearly transparent Gaussians: a list of 2400 entries that the pixels walk to its
+    end (median n_contrib above 2300) with the image still translucent.  The oracle is the reference of the GPU tests on
+    long and deep tile lists (test_gpu_deep_lists.py); here its own images and every gradient are pinned to the dense
+    float64 autograd model at this file's tolerances, thousands of blended entries per pixel included."""
+    run = _run(oracle, P=2400, H=16, W=16, seed=7, sh_degree=1, cam=(10.0, 40.0, 1.6, 40.0),
+               scene_kw=dict(scale_lo=0.2, scale_hi=0.6, opa_lo=0.0045, opa_hi=0.0075))
+    sc, leaves, m2d, _, _, out, ro, (color, radii, depth, alpha) = run
+    keys, vals, ranges, tt, nc = ro.binning()
+    assert ranges.shape[0] == 1 and int(ranges[0, 1]) - int(ranges[0, 0]) >= 2048, ranges
+    assert float(np.median(nc)) > 1024, float(np.median(nc))
+    assert np.array_equal(radii, out["radii"].numpy())
+    assert np.array_equal(tt.astype(np.int64), out["tiles_touched"].numpy())
+    assert np.array_equal(nc.astype(np.int64), out["n_contrib"].numpy())
+    np.testing.assert_allclose(color, out["color"].detach().numpy(), atol=2e-5)
+    np.testing.assert_allclose(depth, out["depth"].detach().numpy(), atol=2e-5)
+    np.testing.assert_allclose(alpha, out["alpha"].detach().numpy(), atol=2e-5)
+    _grad_compare(run)
 
 
 def test_argument_validation(oracle):
