@@ -206,6 +206,12 @@ def model_lib():
         lib.gip_field_sample.restype = ctypes.c_int
         lib.gip_field_sample.argtypes = [_vp, _vp, _vp, _vp, _vp, ctypes.c_int64, _vp, ctypes.c_float, _vp, ctypes.c_int32, ctypes.c_int32,
                                          ctypes.c_float, _vp, _vp, ctypes.c_int64, _vp, ctypes.c_size_t, _vp, _vp, _vp, _vp]
+        lib.gip_texture_bake_workspace_size.restype = ctypes.c_int
+        lib.gip_texture_bake_workspace_size.argtypes = [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_size_t)]
+        lib.gip_texture_bake.restype = ctypes.c_int
+        lib.gip_texture_bake.argtypes = [_vp, _vp, _vp, _vp, _vp, ctypes.c_int64, _vp, ctypes.c_float, _vp, ctypes.c_int32, ctypes.c_int32,
+                                         ctypes.c_float, _vp, ctypes.c_int64, _vp, ctypes.c_int64, _vp, _vp, ctypes.c_int32, ctypes.c_int32,
+                                         ctypes.c_int32, _vp, ctypes.c_size_t, _vp, _vp, _vp]
         _model = _Counted(lib)
     return _model
 
@@ -350,3 +356,4 @@ RASTER_SYMBOLS = ["gip_abi_version", "gip_status_string", "gip_raster_state_byte
                   "gip_raster_mark_visible", "gip_raster_forward_profiled", "gip_raster_backward_profiled"]
 FIELD_SYMBOLS = ["gip_field_workspace_size", "gip_density_field", "gip_surface_count", "gip_surface_emit"]
 SAMPLE_SYMBOLS = ["gip_field_sample_workspace_size", "gip_field_sample"]
+TEXTURE_SYMBOLS = ["gip_texture_bake_workspace_size", "gip_texture_bake"]

@@ -338,6 +338,133 @@ class GaussianModel:
                 mesh.write_obj(path, vertices, faces, colors=vcolors, normals=normals)
         return vertices, faces, normals, vcolors
 
+    @staticmethod
+    def _default_texture_size(F):
+        """The smallest power of two >= 64 whose atlas has cells of side >= 8, at most 8192 (ValueError if F faces do not fit that)."""
+        from ..utils import texture as tex
+        size = 64
+        while size < 8192:
+            try:
+                if tex.atlas_layout(F, size)[0] >= 8:
+                    break
+            except ValueError:
+                pass
+            size *= 2
+        tex.atlas_layout(F, size)
+        return size
+
+    @torch.no_grad()
+    def bake_texture(self, vertices, faces, texture_size=None, colors=None, resolution=128, num_blocks=16, relax_ratio=1.5, slices=None,
+                     normalized=False):
+        """{"texture": [T, T, 3] float32, "density": [T, T], "uv": [F, 3, 2] float32, "cell": c}: the weight-blended `colors` of the
+        Gaussians baked into a T x T texture of the mesh (vertices [V, 3] float32 in world coordinates, faces [F, 3] int32, both on
+        the GPU, as extract_mesh returns them; normalized=True: vertices in the field's normalised coordinates, as in
+        sample_fields).  The atlas is utils/texture.py's: every face owns a right-isosceles triangle of texels in a cell of side c,
+        `uv` are its corners' OBJ texture coordinates; row 0 of the texture is the top image row.  A texel is the field of
+        sample_fields (same sources, normalisation, blocks and membership for the same resolution, num_blocks, relax_ratio) at its
+        point on the face's plane, evaluated in the block of the face's centroid; texture = color_sum / density, 0 where the density
+        is 0 or no face owns the texel, in [0, 1] when `colors` are.  One call of csrc/texture.hip, no point array.
+        texture_size=None: the smallest power of two >= 64 with c >= 8, at most 8192.  colors: [N, 3] per Gaussian, default the base
+        colour (a view-dependent colour from one direction is baked by passing it here).  slices: workgroups a block's texels are
+        spread over (None: from the fullest block); the result does not depend on it.  Raises like sample_fields, and ValueError
+        for faces that do not fit the texture or index outside [0, V)."""
+        out = self._bake_sums(vertices, faces, texture_size, colors, resolution, num_blocks, relax_ratio, slices, normalized)
+        T = out["density"].shape[0]
+        texture = self._blend(out["color_sum"].reshape(-1, 3), out["density"].reshape(-1)).reshape(T, T, 3)
+        return {"texture": texture, "density": out["density"], "uv": out["uv"], "cell": out["cell"]}
+
+    @torch.no_grad()
+    def _bake_sums(self, vertices, faces, texture_size=None, colors=None, resolution=128, num_blocks=16, relax_ratio=1.5, slices=None,
+                   normalized=False):
+        """bake_texture's checks and its one call of gip_texture_bake: {"density": [T, T], "color_sum": [T, T, 3], "uv", "cell"}, the
+        raw sums (0 at unowned texels)."""
+        import ctypes
+
+        from .. import _lib
+        from ..utils import texture as tex
+        from ..utils.sh import C0
+        resolution, num_blocks = self._field_geometry("bake_texture", resolution, num_blocks)
+        dev = self._xyz.device
+        if not (isinstance(vertices, torch.Tensor) and vertices.is_cuda and vertices.dtype == torch.float32 and vertices.dim() == 2 and
+                vertices.shape[1] == 3):
+            raise ValueError("bake_texture needs a [V, 3] float32 GPU tensor of vertices")
+        if not (isinstance(faces, torch.Tensor) and faces.is_cuda and faces.dtype == torch.int32 and faces.dim() == 2 and
+                faces.shape[1] == 3):
+            raise ValueError("bake_texture needs an [F, 3] int32 GPU tensor of faces")
+        if slices is not None and not 1 <= int(slices) <= 65535:
+            raise ValueError("bake_texture: slices must lie in 1 .. 65535")
+        V, F = int(vertices.shape[0]), int(faces.shape[0])
+        T = self._default_texture_size(F) if texture_size is None else int(texture_size)
+        if T < 4 or T > 16384:
+            raise ValueError("bake_texture: texture_size must lie in 4 .. 16384")
+        c, _, _ = tex.atlas_layout(F, T)
+        if colors is None:
+            colors = (0.5 + C0 * self._features_dc.float().reshape(-1, 3)).clamp(0, 1)
+        if not (isinstance(colors, torch.Tensor) and colors.device == dev and colors.dim() == 2 and
+                tuple(colors.shape) == (self._xyz.shape[0], 3)):
+            raise ValueError("bake_texture: colors must be an [N, 3] tensor on the model's device, one row per Gaussian")
+        density = torch.zeros((T, T), dtype=torch.float32, device=dev)
+        color_sum = torch.zeros((T, T, 3), dtype=torch.float32, device=dev)
+        out = {"density": density, "color_sum": color_sum, "uv": torch.from_numpy(tex.atlas_uv(F, T)).to(dev), "cell": c}
+        if F == 0:
+            return out
+        vertices, faces = vertices.detach().to(dev).contiguous(), faces.detach().to(dev).contiguous()
+        src = self._field_sources()
+        fl = faces.long()
+        if src is not None and V > 0:
+            mask, xyzs, opacities, stds, rots = src
+            u = vertices if normalized else ((vertices - self.center) * self.scale).contiguous()
+            tri = u[fl.clamp(0, V - 1)]
+            centroid = ((tri[:, 0] + tri[:, 1] + tri[:, 2]) / 3).contiguous()
+            grid = torch.linspace(-1, 1, resolution, dtype=torch.float32).to(dev)      # as in extract_fields: membership depends on their bits
+            cell = (torch.bucketize(centroid, grid, right=True) - 1).clamp(0, resolution - 1) // (resolution // num_blocks)
+            block = (cell[:, 0] * num_blocks + cell[:, 1]) * num_blocks + cell[:, 2]
+            counts = torch.bincount(block, minlength=num_blocks ** 3)
+            lo, hi, fullest = (int(x) for x in torch.stack((fl.min(), fl.max(), counts.max())).cpu())      # the one host read
+        else:
+            lo, hi = (int(x) for x in torch.stack((fl.min(), fl.max())).cpu())
+        if lo < 0 or hi >= V:
+            raise ValueError("bake_texture: face indices must lie in [0, %d)" % V)
+        if src is None:
+            return out
+        if slices is None:      # one pass (256 lanes * 4 texels) per workgroup of the fullest block, within reason
+            slices = min(max((fullest * (c * (c + 1) // 2) + 1023) // 1024, 1), 1024)
+        face_order = torch.sort(block, stable=True).indices.to(torch.int32)
+        block_start = torch.cat((counts.new_zeros(1), counts.cumsum(0))).to(torch.int32)
+        rgb = colors.float()[mask].contiguous()
+        P = int(opacities.shape[0])
+        margin = (2 / num_blocks) * relax_ratio
+        lib = _lib.model_lib()
+        need = ctypes.c_size_t(0)
+        rc = lib.gip_texture_bake_workspace_size(P, resolution, num_blocks, ctypes.byref(need))
+        if rc != 0:
+            raise RuntimeError("gip_texture_bake_workspace_size failed with status %d" % rc)
+        ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+        p = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+        with torch.cuda.device(dev):
+            rc = lib.gip_texture_bake(p(xyzs), p(opacities), p(stds), p(rots), p(rgb), P, p(self.center.contiguous()), self.scale, p(grid),
+                                      resolution, num_blocks, margin, p(u), V, p(faces), F, p(face_order), p(block_start), T, c,
+                                      int(slices), p(ws), need.value, p(density), p(color_sum),
+                                      ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        if rc != 0:
+            raise RuntimeError("gip_texture_bake failed with status %d" % rc)
+        return out
+
+    @torch.no_grad()
+    def extract_textured_mesh(self, path=None, density_thresh=1.0, resolution=128, num_blocks=16, relax_ratio=1.5, texture_size=None,
+                              colors=None):
+        """(vertices [V, 3], faces [F, 3] int32, normals [V, 3], uv [F, 3, 2], texture [T, T, 3]): the mesh and normals of
+        extract_mesh_with_attributes, bit for bit, with bake_texture's atlas and texture in place of vertex colours — the reference's
+        export_obj_with_mtl (threestudio/models/exporters/mesh_exporter.py:53-137) without its third-party unwrapping, rasterising
+        and inpainting.  With path = dir/name.obj it writes name.obj, name.mtl and name_kd.png (utils.mesh.write_obj_textured)."""
+        from ..utils import mesh
+        vertices, faces, normals, _ = self.extract_mesh_with_attributes(None, density_thresh, resolution, num_blocks, relax_ratio, colors)
+        baked = self.bake_texture(vertices, faces, texture_size, colors, resolution, num_blocks, relax_ratio)
+        if path is not None:
+            os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+            mesh.write_obj_textured(path, vertices, faces, baked["uv"], baked["texture"], normals=normals)
+        return vertices, faces, normals, baked["uv"], baked["texture"]
+
     # ------------------------------------------------------------------ initialisation
     def create_from_pcd(self, pcd: BasicPointCloud, spatial_lr_scale: float, dist2=None):
         """`dist2` (mean squared 3-NN distance per point) defaults to the HIP distCUDA2 replacement."""

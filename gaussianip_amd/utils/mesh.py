@@ -184,3 +184,79 @@ def read_ply_mesh(path):
     normals = pick(("nx", "ny", "nz")).astype(np.float32).reshape(-1, 3) if {"nx", "ny", "nz"} <= names else None
     colors = (pick(("red", "green", "blue")).astype(np.float32) / 255).reshape(-1, 3) if {"red", "green", "blue"} <= names else None
     return vertices, tris["idx"].astype(np.int32).reshape(-1, 3), colors, normals
+
+
+def write_obj_textured(path, vertices, faces, uv, texture, normals=None):
+    """Wavefront OBJ with a material and a texture, the layout of the reference's exporter (threestudio/utils/saving.py:519-545):
+    `path` = dir/name.obj gets `mtllib name.mtl`, `g object`, `usemtl default`, the `v` lines, `vn` lines (with `normals`, one per
+    vertex) and `vt u v` lines (uv [F, 3, 2]: three per face, none shared; numbers with 9 significant digits as write_obj), then
+    `f a/t/a b/t/b c/t/c` (`f a/t b/t c/t` without normals) with t = 3 f + 1 .. 3 f + 3.  dir/name.mtl holds the reference's
+    statements in its order and names dir/name_kd.png, the texture ([H, W, 3] in [0, 1], row 0 on top) as an 8-bit PNG.  The
+    reference calls every texture `texture_kd.*`; here the name follows the OBJ's, because two exports into one directory would
+    otherwise overwrite each other's texture."""
+    import os
+
+    from .texture import write_png_rgb
+    v = _array(vertices, np.float32).reshape(-1, 3)
+    f = _array(faces, np.int64).reshape(-1, 3) + 1
+    vt = _array(uv, np.float32).reshape(-1, 2)
+    nrm = None if normals is None else _array(normals, np.float32).reshape(-1, 3)
+    if vt.shape[0] != 3 * f.shape[0]:
+        raise ValueError("write_obj_textured: uv needs three rows per face")
+    if nrm is not None and nrm.shape[0] != v.shape[0]:
+        raise ValueError("write_obj_textured: normals need one row per vertex")
+    stem = os.path.splitext(os.path.abspath(path))[0]
+    name = os.path.basename(stem)
+    with open(path, "w") as out:
+        out.write("mtllib %s.mtl\ng object\nusemtl default\n" % name)
+        out.write("".join("v %.9g %.9g %.9g\n" % (float(a), float(b), float(c)) for a, b, c in v))
+        if nrm is not None:
+            out.write("".join("vn %.9g %.9g %.9g\n" % (float(a), float(b), float(c)) for a, b, c in nrm))
+        out.write("".join("vt %.9g %.9g\n" % (float(a), float(b)) for a, b in vt))
+        if nrm is None:
+            out.write("".join("f %d/%d %d/%d %d/%d\n" % (a, 3 * i + 1, b, 3 * i + 2, c, 3 * i + 3) for i, (a, b, c) in enumerate(f)))
+        else:
+            out.write("".join("f %d/%d/%d %d/%d/%d %d/%d/%d\n" % (a, 3 * i + 1, a, b, 3 * i + 2, b, c, 3 * i + 3, c)
+                              for i, (a, b, c) in enumerate(f)))
+    with open(stem + ".mtl", "w") as out:
+        out.write("newmtl default\nKa 0.0 0.0 0.0\nmap_Kd %s_kd.png\nKs 0.0 0.0 0.0\n" % name)
+    write_png_rgb(stem + "_kd.png", texture)
+
+
+def read_obj_textured(path):
+    """(vertices [V, 3] float32, faces [F, 3] int32 0-based, normals [V, 3] float32 or None, uv [F, 3, 2] float32, texture [H, W, 3]
+    float32 in [0, 1]) of what write_obj_textured wrote: the texture is the `map_Kd` of the file that `mtllib` names."""
+    import os
+
+    from .texture import read_png_rgb
+    v, n, vt, f, ft, mtl = [], [], [], [], [], None
+    with open(path) as src:
+        for line in src:
+            parts = line.split()
+            if not parts:
+                continue
+            if parts[0] == "mtllib":
+                mtl = parts[1]
+            elif parts[0] == "v":
+                v.append([float(x) for x in parts[1:4]])
+            elif parts[0] == "vn":
+                n.append([float(x) for x in parts[1:4]])
+            elif parts[0] == "vt":
+                vt.append([float(x) for x in parts[1:3]])
+            elif parts[0] == "f":
+                f.append([int(x.split("/")[0]) - 1 for x in parts[1:4]])
+                ft.append([int(x.split("/")[1]) - 1 for x in parts[1:4]])
+    if mtl is None:
+        raise ValueError("%s names no material library" % path)
+    folder, image = os.path.dirname(os.path.abspath(path)), None
+    with open(os.path.join(folder, mtl)) as src:
+        for line in src:
+            parts = line.split()
+            if parts and parts[0] == "map_Kd":
+                image = parts[1]
+    if image is None:
+        raise ValueError("%s has no map_Kd" % mtl)
+    uv = np.asarray(vt, np.float32).reshape(-1, 2)[np.asarray(ft, np.int64).reshape(-1, 3)]
+    texture = read_png_rgb(os.path.join(folder, image)).astype(np.float32) / 255
+    return (np.asarray(v, np.float32).reshape(-1, 3), np.asarray(f, np.int32).reshape(-1, 3),
+            np.asarray(n, np.float32).reshape(-1, 3) if n else None, uv.reshape(-1, 3, 2), texture)

@@ -162,6 +162,29 @@ int gip_field_sample(const float* xyz, const float* opacity, const float* scalin
                      const float* center, float scale, const float* grid, int32_t R, int32_t num_blocks, float margin,
                      const float* points, const int32_t* block_start, int64_t V, void* workspace, size_t workspace_bytes,
                      float* density, float* gradient, float* color_sum, void* stream);
+/* The colour of the Gaussians baked into a UV texture of a triangle mesh (csrc/texture.hip; the atlas is stated in
+ * gaussianip_amd/utils/texture.py): face f owns a right-isosceles triangle of texels, half f & 1 of the cell x cell square f / 2
+ * (row-major, T / cell squares per row; a texel with cell-local indices (i, j) belongs to half (i + j >= cell)).
+ *   gip_texture_bake  for every owned texel of a T x T texture (row 0 = the top image row), at the point
+ *           p = v0 + (li / b) (v1 - v0) + (lj / b) (v2 - v0),   b = cell - 3,   (li, lj) = (i, j) or (cell - 1 - i, cell - 1 - j) for half 1,
+ *       of its face (float32, that operand order; vertices [V, 3] in NORMALISED coordinates, faces [F, 3] int32), the sums over the
+ *       members of the face's block of
+ *           density   [T, T]     sum w            color_sum [T, T, 3]  sum w * rgb        (w as in gip_field_sample; raw sums)
+ *       The CALLER decides a face's block: face_order [F] int32 lists the face ids grouped by block, block_start [num_blocks^3 + 1]
+ *       int32 are the exclusive offsets into it.  Sources, normalisation, inverse covariance, blocks, membership and `margin` are
+ *       gip_density_field's, argument for argument; the walk over the Gaussians is gip_field_sample's, so the sums equal
+ *       gip_field_sample's at the same points and blocks bit for bit.  A block's texels are spread over `slices` workgroups (0: chosen
+ *       here from F alone; the result does not depend on it); no float atomics: two runs are bitwise equal.  Unowned texels are not
+ *       written: the caller zero-fills.  F == 0 is a successful no-op; P == 0 fills both outputs with zeros.  No host read.
+ *   gip_texture_bake_workspace_size  bytes of `workspace` (gip_field_sample_workspace_size's).
+ * Status 1: a NULL required pointer, a shape outside gip_density_field's limits, T < 4 or T > 16384, cell < 4, cell > T or
+ * 2 (T / cell)^2 < F, slices < 0 or > 65535, a short workspace, F or V above 2^31 - 1, faces without vertices.  Status 3: a launch error. */
+int gip_texture_bake_workspace_size(int64_t P, int32_t R, int32_t num_blocks, size_t* bytes);
+int gip_texture_bake(const float* xyz, const float* opacity, const float* scaling, const float* rotation, const float* rgb, int64_t P,
+                     const float* center, float scale, const float* grid, int32_t R, int32_t num_blocks, float margin,
+                     const float* vertices, int64_t V, const int32_t* faces, int64_t F, const int32_t* face_order,
+                     const int32_t* block_start, int32_t T, int32_t cell, int32_t slices, void* workspace, size_t workspace_bytes,
+                     float* density, float* color_sum, void* stream);
 #ifdef __cplusplus
 }
 #endif

@@ -8,7 +8,11 @@ hipEvent timing around each call, warm-up runs first, the median of the timed ru
     python tools/bench_field.py --once 128      one extract_fields + extract_mesh call (for a kernel trace)
     python tools/bench_field.py --attributes    extract_mesh_with_attributes (csrc/field_sample.hip) next to extract_mesh at the default
                                                 geometry (R 128, 16 blocks), and the same three sums at the same vertices as a
-                                                chunked dense evaluation in PyTorch ops (--out defaults to profiles/field_sample.txt)"""
+                                                chunked dense evaluation in PyTorch ops (--out defaults to profiles/field_sample.txt)
+    python tools/bench_field.py --texture       bake_texture (csrc/texture.hip) on the mesh of R 128 / 16 blocks at the default texture
+                                                size and at 2048: the whole call, gip_texture_bake alone, and the route without it on
+                                                the same texels — texel_points materialised, sorted by block, gip_field_sample, the
+                                                sums scattered into the texture (--out defaults to profiles/texture_bake.txt)"""
 import argparse
 import os
 import statistics
@@ -141,6 +145,79 @@ def attributes(gm, args):
             "       max |kernel - dense| / max: density %.2e, gradient %.2e, color_sum %.2e" % tuple(diffs)]
 
 
+def texture(gm, args):
+    """bake_texture, its C entry point alone and the sampler's route on the same texels, at the default texture size and at 2048."""
+    import ctypes
+
+    from gaussianip_amd import _lib
+    from gaussianip_amd.utils import texture as tex
+    R, nb = 128, 16
+    rgb = torch.rand(gm._xyz.shape[0], 3, device="cuda", generator=torch.Generator(device="cuda").manual_seed(0))
+    v, f = gm.extract_mesh(resolution=R, num_blocks=nb)
+    F = int(f.shape[0])
+    lines = ["R %3d  %d vertices, %d faces" % (R, v.shape[0], F)]
+    for T in (gm._default_texture_size(F), 2048):
+        c = tex.atlas_layout(F, T)[0]
+        _, xyzs, opac, stds, rots = gm._field_sources()
+        mask = (gm.get_opacity > 0.005).squeeze(1)
+        cols = rgb[mask].contiguous()
+        u = ((v - gm.center) * gm.scale).contiguous()
+        tri = u[f.long()]
+        grid = torch.linspace(-1, 1, R, dtype=torch.float32).cuda()
+        cell = (torch.bucketize(((tri[:, 0] + tri[:, 1] + tri[:, 2]) / 3).contiguous(), grid, right=True) - 1).clamp(0, R - 1) // (R // nb)
+        block = (cell[:, 0] * nb + cell[:, 1]) * nb + cell[:, 2]
+        counts = torch.bincount(block, minlength=nb ** 3)
+        order = torch.sort(block, stable=True).indices.to(torch.int32)
+        start = torch.cat((counts.new_zeros(1), counts.cumsum(0))).to(torch.int32)
+        slices = min(max((int(counts.max()) * (c * (c + 1) // 2) + 1023) // 1024, 1), 1024)
+        P = int(opac.shape[0])
+        need = ctypes.c_size_t(0)
+        lib = _lib.model_lib()
+        assert lib.gip_texture_bake_workspace_size(P, R, nb, ctypes.byref(need)) == 0
+        ws = torch.empty(need.value, dtype=torch.uint8, device="cuda")
+        dens, csum = torch.zeros((T, T), device="cuda"), torch.zeros((T, T, 3), device="cuda")
+        p = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+        center = gm.center.contiguous()
+
+        def kernel():
+            rc = lib.gip_texture_bake(p(xyzs), p(opac), p(stds), p(rots), p(cols), P, p(center), gm.scale, p(grid), R, nb, (2 / nb) * 1.5,
+                                      p(u), int(u.shape[0]), p(f), F, p(order), p(start), T, c, slices, p(ws), need.value, p(dens), p(csum),
+                                      ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+            assert rc == 0, rc
+
+        def route():
+            pts, face, x, y = tex.texel_points(u, f, T)
+            out = gm._sample("bench_field", pts.contiguous(), block[face], rgb, R, nb, 1.5)
+            d, cs = torch.zeros((T, T), device="cuda"), torch.zeros((T, T, 3), device="cuda")
+            d[y, x], cs[y, x] = out["density"], out["color_sum"]
+            return d, cs
+
+        # texel-Gaussian pairs: every owned texel meets every member of its face's block
+        s_, margin = R // nb, (2 / nb) * 1.5
+        xn = (xyzs - gm.center) * gm.scale
+        inside = ((xn.unsqueeze(-1) > grid[0::s_] - margin) & (xn.unsqueeze(-1) < grid[s_ - 1::s_] + margin)).float()      # [P, 3, nb]
+        members = torch.einsum("pa,pb,pc->abc", inside[:, 0], inside[:, 1], inside[:, 2]).reshape(-1).double()
+        per_face = torch.where(torch.arange(F, device="cuda") % 2 == 0, c * (c + 1) // 2, c * (c - 1) // 2).double()
+        pairs = float((per_face * members[block]).sum())
+        baked = gm._bake_sums(v, f, T, rgb, R, nb, 1.5)
+        d, cs = route()
+        same = bool(torch.equal(baked["density"], d) and torch.equal(baked["color_sum"], cs))
+        owned = int((torch.from_numpy(tex.texel_owner(F, T)) >= 0).sum())
+        del d, cs
+        b = timed(lambda: gm.bake_texture(v, f, T, rgb, R, nb), args.warmup, args.runs)
+        k = timed(kernel, args.warmup, args.runs)
+        r = timed(route, args.warmup, args.runs)
+        lines += ["T %4d  cell %d, %d owned texels, %d of %d blocks hold a face (the fullest %d faces), %d slices" % (
+                      T, c, owned, int((counts > 0).sum()), nb ** 3, int(counts.max()), slices),
+                  "        bake_texture %9.3f [%.3f, %.3f]   gip_texture_bake alone %9.3f [%.3f, %.3f]" % (b + k),
+                  "        texel_points + sort by block + gip_field_sample + scatter %9.3f [%.3f, %.3f]   ratio to bake_texture %.2fx" % (
+                      r + (r[0] / b[0],)),
+                  "        sums bitwise equal to that route: %s" % same,
+                  "        %.3e texel-Gaussian evaluations (%.0f per texel), %.1f per ns of gip_texture_bake" % (
+                      pairs, pairs / owned, pairs / (k[0] * 1e6))]
+    return lines
+
+
 def timed(fn, warmup, runs):
     for _ in range(warmup):
         fn()
@@ -164,10 +241,12 @@ def main():
     ap.add_argument("--chain-runs", type=int, default=3)
     ap.add_argument("--once", type=int, default=0)
     ap.add_argument("--attributes", action="store_true")
+    ap.add_argument("--texture", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "field_sample.txt" if args.attributes else "field_extract.txt")
+        args.out = os.path.join(ROOT, "profiles", "texture_bake.txt" if args.texture else "field_sample.txt" if args.attributes else
+                                "field_extract.txt")
     gm = make_model(args.points)
     if args.once:
         gm.extract_mesh(resolution=args.once)
@@ -175,9 +254,11 @@ def main():
         return
     lines = ["tools/bench_field.py: %d Gaussians (human cloud, trained look), %s, median [min, max] of %d runs after %d warm-up, ms" % (
         args.points, "%s (%s)" % (torch.cuda.get_device_name(0), torch.cuda.get_device_properties(0).gcnArchName), args.runs, args.warmup)]
-    if args.attributes:
+    if args.texture:
+        lines += texture(gm, args)
+    elif args.attributes:
         lines += attributes(gm, args)
-    for R in (() if args.attributes else (128, 256)):
+    for R in (() if args.attributes or args.texture else (128, 256)):
         field = gm.extract_fields(resolution=R)
         chain, pairs = op_chain(gm, R, count_pairs=True)
         diff = float((field - chain).abs().max() / chain.abs().max())
