@@ -1,0 +1,557 @@
+// mesh_raster.hip — a triangle rasterizer for the exported textured mesh: coverage and visibility, perspective-correct attribute
+// interpolation, a bilinear texture lookup with its gradients, and the fused shade of gaussianip_amd.utils.rasterize.render_mesh
+// (DESIGN.md "Rendering the mesh").  Linked into libgip_model.so, compiled with its -ffp-contract=off.
+//
+// Definition of coverage and visibility (tests/mesh_render_reference.py restates it; the forward is bit-reproducible).
+//   * Input is clip-space positions pos [B, V, 4] float32 and tri [F, 3] int32, one topology for all B views.
+//   * The pixel (px, py) has its centre at NDC ((2 px + 1) / W - 1, (2 py + 1) / H - 1).  Row index grows with NDC y.  This is the
+//     Gaussian rasterizer's ndc2Pix, so verts_h @ camera.full_proj_transform lands pixel for pixel on the Gaussian render.
+//   * Per vertex, in float32, in this operand order: ndc = x / w; s = (ndc * 0.5f + 0.5f) * W; X = (int) rintf(s * 256.0f), which
+//     gives 8 sub-pixel bits.  The same holds for Y with H.  The division is correctly rounded.
+//   * A triangle is dropped whole in any of three cases: a vertex has w <= 0 (or a NaN w); a snapped coordinate exceeds +-2^22 in
+//     magnitude (the guard band; a NaN counts as exceeding it); its integer area (X1 - X0)(Y2 - Y0) - (Y1 - Y0)(X2 - X0) is zero.
+//     There is no polygon clipping.  A triangle with a vertex index outside [0, V) is dropped as well.
+//   * Coverage uses exact integer edge functions in int64 at the pixel centre P = (256 px + 128, 256 py + 128), normalised by the
+//     sign of the area:  E0 = (X2 - X1)(Py - Y1) - (Y2 - Y1)(Px - X1),  E1 = (X0 - X2)(Py - Y2) - (Y0 - Y2)(Px - X2),
+//     E2 = (X1 - X0)(Py - Y0) - (Y1 - Y0)(Px - X0), all three and the area negated when the area is negative.  Both windings are
+//     drawn; cull_backfaces drops negative area.  A pixel is covered when every E_i > 0, or E_i == 0 on an edge that owns its
+//     points: the top-left fill rule, here in the form "the edge's direction (dx, dy) = sign(area) (end - start) has dy < 0, or
+//     dy == 0 and dx > 0" (the sample point moved by an infinitesimal (+1, +0)), so a shared edge or vertex has exactly one owner.
+//   * Screen-space weights b_i = (float) E_i / (float) area.  Depth d = b0 * (z0 / w0) + b1 * (z1 / w1) + b2 * (z2 / w2), float32,
+//     left to right.  Fragments with d < -1 or d > 1 (or a NaN d) are discarded; -0 counts as +0.
+//   * Visibility: a fragment's key is the order-preserving 32-bit image of d (bits ^ 0x80000000 for d >= 0, ~bits for d < 0),
+//     shifted left by 32 bits and OR-ed with the triangle index.  The smallest 64-bit key wins: the nearest fragment, and at equal
+//     depth the lower triangle index; a 64-bit unsigned atomic minimum on a [B, H, W] key buffer, so the result does not depend on
+//     the order of execution.
+//   * rast [B, H, W, 4] = (u, v, d, triangle index + 1), all zeros at an empty pixel; u, v are the perspective-correct weights of
+//     corners 0 and 1: q_i = b_i / w_i, u = q0 / ((q0 + q1) + q2), v = q1 / ((q0 + q1) + q2).
+//   * Interpolation: a = (u * a0 + v * a1) + ((1 - u) - v) * a2.  Lookup at uv = (s, t), (0, 0) the corner of tex[0, 0], texel
+//     centres at (i + 0.5) / T: x = s * Tw - 0.5, x0 = floor(x), fx = x - x0, the indices x0, x0 + 1 clamped to the border, the same
+//     in y;  value = (1 - fy) * ((1 - fx) * t00 + fx * t01) + fy * ((1 - fx) * t10 + fx * t11).
+//
+//   mesh_setup_kernel           one lane per (view, triangle): snaps the three vertices, classifies, walks the bounding box of a small
+//                               triangle (at most MR_SMALL_MAX pixel centres) with incrementally updated edge functions, appends a
+//                               larger one to a list (a wavefront's larger ones take their slots with one atomic add).
+//   mesh_large_kernel           one wavefront per listed triangle, lanes striding over the bounding box.
+//   mesh_resolve_kernel         one lane per pixel: key -> rast, one 16-byte store.
+//   mesh_shade_kernel           one lane per pixel: face-varying uv [F, 3, 2] interpolated (flip_v: every corner's v replaced by 1 - v
+//                               first, the OBJ convention), texture [Th, Tw, 3] looked up, (r, g, b, alpha) over the background in one
+//                               16-byte store.
+//   mesh_shade_backward_kernel  dL/dcolor scattered to the four texels with float atomic adds (and to the corners' uv when asked
+//                               for): not bit-reproducible.  No gradient reaches vertex positions.
+//   mesh_interpolate_kernel / mesh_interpolate_backward_kernel / mesh_texture_kernel / mesh_texture_backward_kernel: the unfused
+//                               pieces with any channel count.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/gip_model.h"
+
+#define MR_THREADS 256
+#define MR_SMALL_MAX 64        // pixel centres in the bounding box up to which the setup lane rasterizes the triangle itself (tuning)
+#define MR_GUARD 4194304.f     // 2^22: the guard band of snapped coordinates
+#define MR_MAX_SIZE 16384      // image side: 256 * side + 128 stays inside the guard band
+#define MR_LARGE_BLOCKS 1024   // workgroups of the cooperative kernel (4 wavefronts each, striding over the list)
+#define MR_MAX_FACES 16777215  // triangle index + 1 must be exact in float32
+
+typedef unsigned long long mr_key;
+
+struct MrTri {
+  int X0, Y0, X1, Y1, X2, Y2;   // snapped, 8 sub-pixel bits
+  int sgn;                      // sign of the area
+  int64_t area;                 // normalised: > 0
+  float zw0, zw1, zw2, w0, w1, w2;
+};
+
+__device__ __forceinline__ bool mr_snap(float x, float w, int size, int& out) {
+  const float ndc = x / w;
+  const float s = (ndc * 0.5f + 0.5f) * (float)size;
+  const float t = rintf(s * 256.0f);
+  if (!(fabsf(t) <= MR_GUARD)) return false;
+  out = (int)t;
+  return true;
+}
+
+// the triangle f of one view as the definition sees it; false: dropped whole
+__device__ __forceinline__ bool mr_load(const float* __restrict__ pos, const int32_t* __restrict__ tri, int f, int V, int H, int W,
+                                        int cull, MrTri& t) {
+  const int i0 = tri[(int64_t)f * 3], i1 = tri[(int64_t)f * 3 + 1], i2 = tri[(int64_t)f * 3 + 2];
+  if (i0 < 0 || i0 >= V || i1 < 0 || i1 >= V || i2 < 0 || i2 >= V) return false;
+  const float4 p0 = ((const float4*)pos)[i0], p1 = ((const float4*)pos)[i1], p2 = ((const float4*)pos)[i2];
+  if (!(p0.w > 0.f) || !(p1.w > 0.f) || !(p2.w > 0.f)) return false;
+  if (!mr_snap(p0.x, p0.w, W, t.X0) || !mr_snap(p0.y, p0.w, H, t.Y0) || !mr_snap(p1.x, p1.w, W, t.X1) ||
+      !mr_snap(p1.y, p1.w, H, t.Y1) || !mr_snap(p2.x, p2.w, W, t.X2) || !mr_snap(p2.y, p2.w, H, t.Y2))
+    return false;
+  const int64_t area = (int64_t)(t.X1 - t.X0) * (t.Y2 - t.Y0) - (int64_t)(t.Y1 - t.Y0) * (t.X2 - t.X0);
+  if (area == 0 || (area < 0 && cull)) return false;
+  t.sgn = area < 0 ? -1 : 1;
+  t.area = area < 0 ? -area : area;
+  t.zw0 = p0.z / p0.w;
+  t.zw1 = p1.z / p1.w;
+  t.zw2 = p2.z / p2.w;
+  t.w0 = p0.w;
+  t.w1 = p1.w;
+  t.w2 = p2.w;
+  return true;
+}
+
+// the three normalised edge functions at the point (Px, Py)
+__device__ __forceinline__ void mr_edges(const MrTri& t, int Px, int Py, int64_t& e0, int64_t& e1, int64_t& e2) {
+  e0 = t.sgn * ((int64_t)(t.X2 - t.X1) * (Py - t.Y1) - (int64_t)(t.Y2 - t.Y1) * (Px - t.X1));
+  e1 = t.sgn * ((int64_t)(t.X0 - t.X2) * (Py - t.Y2) - (int64_t)(t.Y0 - t.Y2) * (Px - t.X2));
+  e2 = t.sgn * ((int64_t)(t.X1 - t.X0) * (Py - t.Y0) - (int64_t)(t.Y1 - t.Y0) * (Px - t.X0));
+}
+
+// the smallest value of E that still counts as inside: 0 on an edge that owns its points, 1 on the others
+__device__ __forceinline__ int mr_bias(int dx, int dy) { return (dy < 0 || (dy == 0 && dx > 0)) ? 0 : 1; }
+
+__device__ __forceinline__ void mr_biases(const MrTri& t, int& c0, int& c1, int& c2) {
+  c0 = mr_bias(t.sgn * (t.X2 - t.X1), t.sgn * (t.Y2 - t.Y1));
+  c1 = mr_bias(t.sgn * (t.X0 - t.X2), t.sgn * (t.Y0 - t.Y2));
+  c2 = mr_bias(t.sgn * (t.X1 - t.X0), t.sgn * (t.Y1 - t.Y0));
+}
+
+__device__ __forceinline__ void mr_weights(const MrTri& t, int64_t e0, int64_t e1, int64_t e2, float& b0, float& b1, float& b2) {
+  const float fa = (float)t.area;
+  b0 = (float)e0 / fa;
+  b1 = (float)e1 / fa;
+  b2 = (float)e2 / fa;
+}
+
+__device__ __forceinline__ void mr_fragment(const MrTri& t, int64_t e0, int64_t e1, int64_t e2, uint32_t f, mr_key* __restrict__ at) {
+  float b0, b1, b2;
+  mr_weights(t, e0, e1, e2, b0, b1, b2);
+  const float d = b0 * t.zw0 + b1 * t.zw1 + b2 * t.zw2;
+  if (!(d >= -1.f && d <= 1.f)) return;
+  uint32_t u = __float_as_uint(d);
+  if ((u & 0x7fffffffu) == 0) u = 0;
+  u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+  atomicMin(at, ((mr_key)u << 32) | f);
+}
+
+// the pixel centres inside the bounding box, clipped to the image; false when there is none
+__device__ __forceinline__ bool mr_box(const MrTri& t, int H, int W, int& x_lo, int& x_hi, int& y_lo, int& y_hi) {
+  const int minX = min(t.X0, min(t.X1, t.X2)), maxX = max(t.X0, max(t.X1, t.X2));
+  const int minY = min(t.Y0, min(t.Y1, t.Y2)), maxY = max(t.Y0, max(t.Y1, t.Y2));
+  x_lo = max((minX + 127) >> 8, 0);      // the first px with 256 px + 128 >= minX
+  x_hi = min((maxX - 128) >> 8, W - 1);  // the last px with 256 px + 128 <= maxX
+  y_lo = max((minY + 127) >> 8, 0);
+  y_hi = min((maxY - 128) >> 8, H - 1);
+  return x_lo <= x_hi && y_lo <= y_hi;
+}
+
+// ------------------------------------------------------------------------------------------------------------------ setup
+__global__ void __launch_bounds__(MR_THREADS)
+mesh_setup_kernel(const float* __restrict__ pos, const int32_t* __restrict__ tri, int B, int V, int F, int H, int W, int cull,
+                  mr_key* __restrict__ keys, uint32_t* __restrict__ large_count, int32_t* __restrict__ large_list) {
+  const int64_t g = (int64_t)blockIdx.x * MR_THREADS + threadIdx.x;
+  const bool live = g < (int64_t)B * F;
+  const int b = live ? (int)(g / F) : 0, f = live ? (int)(g - (int64_t)b * F) : 0;
+  MrTri t;
+  int x_lo = 0, x_hi = -1, y_lo = 0, y_hi = -1;
+  int kind = 0;   // 0: nothing to draw, 1: rasterized here, 2: listed
+  if (live && mr_load(pos + (int64_t)b * V * 4, tri, f, V, H, W, cull, t) && mr_box(t, H, W, x_lo, x_hi, y_lo, y_hi))
+    kind = (int64_t)(x_hi - x_lo + 1) * (y_hi - y_lo + 1) > MR_SMALL_MAX ? 2 : 1;
+  // the wavefront's listed triangles take their slots with one add; every (view, triangle) is appended at most once: the list holds B * F
+  const unsigned long long big = __ballot(kind == 2);
+  if (big) {
+    const int lane = threadIdx.x & 63, leader = __ffsll((long long)big) - 1;
+    uint32_t base = 0;
+    if (lane == leader) base = atomicAdd(large_count, (uint32_t)__popcll(big));
+    base = (uint32_t)__shfl((int)base, leader);
+    if (kind == 2) large_list[base + (uint32_t)__popcll(big & ((1ull << lane) - 1ull))] = (int32_t)g;
+  }
+  if (kind != 1) return;
+  int c0, c1, c2;
+  mr_biases(t, c0, c1, c2);
+  int64_t r0, r1, r2;
+  mr_edges(t, 256 * x_lo + 128, 256 * y_lo + 128, r0, r1, r2);
+  // E(Px + 256, Py) - E(Px, Py) = -256 dy,  E(Px, Py + 256) - E(Px, Py) = 256 dx
+  const int64_t sx0 = -256 * (int64_t)(t.sgn * (t.Y2 - t.Y1)), sy0 = 256 * (int64_t)(t.sgn * (t.X2 - t.X1));
+  const int64_t sx1 = -256 * (int64_t)(t.sgn * (t.Y0 - t.Y2)), sy1 = 256 * (int64_t)(t.sgn * (t.X0 - t.X2));
+  const int64_t sx2 = -256 * (int64_t)(t.sgn * (t.Y1 - t.Y0)), sy2 = 256 * (int64_t)(t.sgn * (t.X1 - t.X0));
+  mr_key* view = keys + (int64_t)b * H * W;
+  for (int py = y_lo; py <= y_hi; py++) {
+    int64_t e0 = r0, e1 = r1, e2 = r2;
+    for (int px = x_lo; px <= x_hi; px++) {
+      if (e0 >= c0 && e1 >= c1 && e2 >= c2) mr_fragment(t, e0, e1, e2, (uint32_t)f, view + (int64_t)py * W + px);
+      e0 += sx0;
+      e1 += sx1;
+      e2 += sx2;
+    }
+    r0 += sy0;
+    r1 += sy1;
+    r2 += sy2;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------------ large triangles
+__global__ void __launch_bounds__(MR_THREADS)
+mesh_large_kernel(const float* __restrict__ pos, const int32_t* __restrict__ tri, int B, int V, int F, int H, int W, int cull,
+                  mr_key* __restrict__ keys, const uint32_t* __restrict__ large_count, const int32_t* __restrict__ large_list) {
+  const int lane = threadIdx.x & 63;
+  const int64_t total = (int64_t)B * F;
+  const int64_t count = min((int64_t)large_count[0], total);
+  for (int64_t i = (int64_t)blockIdx.x * (MR_THREADS / 64) + (threadIdx.x >> 6); i < count; i += (int64_t)gridDim.x * (MR_THREADS / 64)) {
+    const int64_t g = large_list[i];
+    if (g < 0 || g >= total) continue;
+    const int b = (int)(g / F), f = (int)(g - (int64_t)b * F);
+    MrTri t;
+    int x_lo, x_hi, y_lo, y_hi;
+    if (!mr_load(pos + (int64_t)b * V * 4, tri, f, V, H, W, cull, t) || !mr_box(t, H, W, x_lo, x_hi, y_lo, y_hi)) continue;
+    int c0, c1, c2;
+    mr_biases(t, c0, c1, c2);
+    const int bw = x_hi - x_lo + 1;
+    const int n = bw * (y_hi - y_lo + 1);   // <= H * W < 2^31
+    mr_key* view = keys + (int64_t)b * H * W;
+    for (int k = lane; k < n; k += 64) {
+      const int row = k / bw, px = x_lo + (k - row * bw), py = y_lo + row;
+      int64_t e0, e1, e2;
+      mr_edges(t, 256 * px + 128, 256 * py + 128, e0, e1, e2);
+      if (e0 >= c0 && e1 >= c1 && e2 >= c2) mr_fragment(t, e0, e1, e2, (uint32_t)f, view + (int64_t)py * W + px);
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------------ resolve
+__global__ void __launch_bounds__(MR_THREADS)
+mesh_resolve_kernel(const float* __restrict__ pos, const int32_t* __restrict__ tri, int B, int V, int F, int H, int W,
+                    const mr_key* __restrict__ keys, float4* __restrict__ rast) {
+  const int64_t g = (int64_t)blockIdx.x * MR_THREADS + threadIdx.x;
+  if (g >= (int64_t)B * H * W) return;
+  const mr_key key = keys[g];
+  float4 out = make_float4(0.f, 0.f, 0.f, 0.f);
+  const uint32_t f = (uint32_t)key;
+  if (key != ~0ull && f < (uint32_t)F) {
+    const int b = (int)(g / ((int64_t)H * W));
+    const int pix = (int)(g - (int64_t)b * H * W), py = pix / W, px = pix - py * W;
+    MrTri t;
+    if (mr_load(pos + (int64_t)b * V * 4, tri, (int)f, V, H, W, 0, t)) {
+      const uint32_t u = (uint32_t)(key >> 32);
+      const float d = __uint_as_float((u & 0x80000000u) ? (u ^ 0x80000000u) : ~u);
+      int64_t e0, e1, e2;
+      mr_edges(t, 256 * px + 128, 256 * py + 128, e0, e1, e2);
+      float b0, b1, b2;
+      mr_weights(t, e0, e1, e2, b0, b1, b2);
+      const float q0 = b0 / t.w0, q1 = b1 / t.w1, q2 = b2 / t.w2;
+      const float den = (q0 + q1) + q2;
+      out = make_float4(q0 / den, q1 / den, d, (float)(f + 1));
+    }
+  }
+  rast[g] = out;
+}
+
+// ------------------------------------------------------------------------------------------------------------------ lookup
+struct MrBil {
+  int x0, x1, y0, y1;
+  float fx, fy;
+};
+
+__device__ __forceinline__ MrBil mr_bilinear(float s, float t, int Th, int Tw) {
+  MrBil r;
+  const float x = s * (float)Tw - 0.5f, y = t * (float)Th - 0.5f;
+  const float xf = floorf(x), yf = floorf(y);
+  r.fx = x - xf;
+  r.fy = y - yf;
+  const int xi = (int)fminf(fmaxf(xf, -1.f), (float)Tw), yi = (int)fminf(fmaxf(yf, -1.f), (float)Th);   // NaN: -1
+  r.x0 = min(max(xi, 0), Tw - 1);
+  r.x1 = min(max(xi + 1, 0), Tw - 1);
+  r.y0 = min(max(yi, 0), Th - 1);
+  r.y1 = min(max(yi + 1, 0), Th - 1);
+  return r;
+}
+
+__device__ __forceinline__ float mr_mix(const MrBil& r, float t00, float t01, float t10, float t11) {
+  return (1.f - r.fy) * ((1.f - r.fx) * t00 + r.fx * t01) + r.fy * ((1.f - r.fx) * t10 + r.fx * t11);
+}
+
+__device__ __forceinline__ float mr_interp(float u, float v, float w, float a0, float a1, float a2) { return (u * a0 + v * a1) + w * a2; }
+
+// ------------------------------------------------------------------------------------------------------------------ fused shade
+__global__ void __launch_bounds__(MR_THREADS)
+mesh_shade_kernel(const float4* __restrict__ rast, const float* __restrict__ uv, const float* __restrict__ tex, const float* __restrict__ bg,
+                  int64_t pixels, int F, int flip_v, int Th, int Tw, float4* __restrict__ shaded) {
+  const int64_t g = (int64_t)blockIdx.x * MR_THREADS + threadIdx.x;
+  if (g >= pixels) return;
+  const float4 r = rast[g];
+  const int f = (int)r.w - 1;
+  float4 out = make_float4(bg[0], bg[1], bg[2], 0.f);
+  if (f >= 0 && f < F) {
+    const float* a = uv + (int64_t)f * 6;
+    const float w = (1.f - r.x) - r.y;
+    const float v0 = flip_v ? 1.f - a[1] : a[1], v1 = flip_v ? 1.f - a[3] : a[3], v2 = flip_v ? 1.f - a[5] : a[5];
+    const MrBil q = mr_bilinear(mr_interp(r.x, r.y, w, a[0], a[2], a[4]), mr_interp(r.x, r.y, w, v0, v1, v2), Th, Tw);
+    const float* t00 = tex + ((int64_t)q.y0 * Tw + q.x0) * 3;
+    const float* t01 = tex + ((int64_t)q.y0 * Tw + q.x1) * 3;
+    const float* t10 = tex + ((int64_t)q.y1 * Tw + q.x0) * 3;
+    const float* t11 = tex + ((int64_t)q.y1 * Tw + q.x1) * 3;
+    out = make_float4(mr_mix(q, t00[0], t01[0], t10[0], t11[0]), mr_mix(q, t00[1], t01[1], t10[1], t11[1]),
+                      mr_mix(q, t00[2], t01[2], t10[2], t11[2]), 1.f);
+  }
+  shaded[g] = out;
+}
+
+__global__ void __launch_bounds__(MR_THREADS)
+mesh_shade_backward_kernel(const float4* __restrict__ rast, const float* __restrict__ uv, const float* __restrict__ tex,
+                           const float4* __restrict__ g_shaded, int64_t pixels, int F, int flip_v, int Th, int Tw, float* __restrict__ g_tex,
+                           float* __restrict__ g_uv) {
+  const int64_t g = (int64_t)blockIdx.x * MR_THREADS + threadIdx.x;
+  if (g >= pixels) return;
+  const float4 r = rast[g];
+  const int f = (int)r.w - 1;
+  if (f < 0 || f >= F) return;
+  const float4 go = g_shaded[g];
+  const float gc[3] = {go.x, go.y, go.z};
+  const float* a = uv + (int64_t)f * 6;
+  const float w = (1.f - r.x) - r.y;
+  const float v0 = flip_v ? 1.f - a[1] : a[1], v1 = flip_v ? 1.f - a[3] : a[3], v2 = flip_v ? 1.f - a[5] : a[5];
+  const MrBil q = mr_bilinear(mr_interp(r.x, r.y, w, a[0], a[2], a[4]), mr_interp(r.x, r.y, w, v0, v1, v2), Th, Tw);
+  const int64_t o00 = ((int64_t)q.y0 * Tw + q.x0) * 3, o01 = ((int64_t)q.y0 * Tw + q.x1) * 3, o10 = ((int64_t)q.y1 * Tw + q.x0) * 3,
+                o11 = ((int64_t)q.y1 * Tw + q.x1) * 3;
+  const float w00 = (1.f - q.fy) * (1.f - q.fx), w01 = (1.f - q.fy) * q.fx, w10 = q.fy * (1.f - q.fx), w11 = q.fy * q.fx;
+  float gs = 0.f, gt = 0.f;
+#pragma unroll
+  for (int c = 0; c < 3; c++) {
+    if (g_tex) {
+      atomicAdd(g_tex + o00 + c, w00 * gc[c]);
+      atomicAdd(g_tex + o01 + c, w01 * gc[c]);
+      atomicAdd(g_tex + o10 + c, w10 * gc[c]);
+      atomicAdd(g_tex + o11 + c, w11 * gc[c]);
+    }
+    if (g_uv) {
+      const float t00 = tex[o00 + c], t01 = tex[o01 + c], t10 = tex[o10 + c], t11 = tex[o11 + c];
+      gs += gc[c] * ((1.f - q.fy) * (t01 - t00) + q.fy * (t11 - t10));
+      gt += gc[c] * ((1.f - q.fx) * (t10 - t00) + q.fx * (t11 - t01));
+    }
+  }
+  if (g_uv) {
+    gs *= (float)Tw;
+    gt *= flip_v ? -(float)Th : (float)Th;   // d(1 - v) / dv
+    float* o = g_uv + (int64_t)f * 6;
+    atomicAdd(o + 0, r.x * gs);
+    atomicAdd(o + 1, r.x * gt);
+    atomicAdd(o + 2, r.y * gs);
+    atomicAdd(o + 3, r.y * gt);
+    atomicAdd(o + 4, w * gs);
+    atomicAdd(o + 5, w * gt);
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------------ the unfused pieces
+// the three rows of attr that the pixel's triangle names; false at an empty pixel or a triangle / row out of range
+__device__ __forceinline__ bool mr_corners(const float4& r, const int32_t* __restrict__ idx, int F, int N, int64_t& i0, int64_t& i1,
+                                           int64_t& i2) {
+  const int f = (int)r.w - 1;
+  if (f < 0 || f >= F) return false;
+  if (idx) {
+    i0 = idx[(int64_t)f * 3];
+    i1 = idx[(int64_t)f * 3 + 1];
+    i2 = idx[(int64_t)f * 3 + 2];
+  } else {
+    i0 = (int64_t)f * 3;
+    i1 = i0 + 1;
+    i2 = i0 + 2;
+  }
+  return i0 >= 0 && i0 < N && i1 >= 0 && i1 < N && i2 >= 0 && i2 < N;
+}
+
+__global__ void __launch_bounds__(MR_THREADS)
+mesh_interpolate_kernel(const float* __restrict__ attr, int64_t attr_stride, const int32_t* __restrict__ idx, const float4* __restrict__ rast,
+                        int64_t pixels, int64_t per_view, int F, int N, int C, float* __restrict__ out) {
+  const int64_t g = (int64_t)blockIdx.x * MR_THREADS + threadIdx.x;
+  if (g >= pixels) return;
+  const float4 r = rast[g];
+  float* o = out + g * C;
+  int64_t i0, i1, i2;
+  if (!mr_corners(r, idx, F, N, i0, i1, i2)) {
+    for (int c = 0; c < C; c++) o[c] = 0.f;
+    return;
+  }
+  const float* a = attr + (g / per_view) * attr_stride;
+  const float w = (1.f - r.x) - r.y;
+  for (int c = 0; c < C; c++) o[c] = mr_interp(r.x, r.y, w, a[i0 * C + c], a[i1 * C + c], a[i2 * C + c]);
+}
+
+__global__ void __launch_bounds__(MR_THREADS)
+mesh_interpolate_backward_kernel(const float* __restrict__ g_out, const int32_t* __restrict__ idx, const float4* __restrict__ rast,
+                                 int64_t pixels, int64_t per_view, int F, int N, int C, float* __restrict__ g_attr, int64_t attr_stride) {
+  const int64_t g = (int64_t)blockIdx.x * MR_THREADS + threadIdx.x;
+  if (g >= pixels) return;
+  const float4 r = rast[g];
+  int64_t i0, i1, i2;
+  if (!mr_corners(r, idx, F, N, i0, i1, i2)) return;
+  float* a = g_attr + (g / per_view) * attr_stride;
+  const float* go = g_out + g * C;
+  const float w = (1.f - r.x) - r.y;
+  for (int c = 0; c < C; c++) {
+    const float v = go[c];
+    atomicAdd(a + i0 * C + c, r.x * v);
+    atomicAdd(a + i1 * C + c, r.y * v);
+    atomicAdd(a + i2 * C + c, w * v);
+  }
+}
+
+__global__ void __launch_bounds__(MR_THREADS)
+mesh_texture_kernel(const float* __restrict__ tex, int64_t tex_stride, const float2* __restrict__ uv, int64_t pixels, int64_t per_view, int Th,
+                    int Tw, int C, float* __restrict__ out) {
+  const int64_t g = (int64_t)blockIdx.x * MR_THREADS + threadIdx.x;
+  if (g >= pixels) return;
+  const float2 st = uv[g];
+  const MrBil q = mr_bilinear(st.x, st.y, Th, Tw);
+  const float* t = tex + (g / per_view) * tex_stride;
+  const float* t00 = t + ((int64_t)q.y0 * Tw + q.x0) * C;
+  const float* t01 = t + ((int64_t)q.y0 * Tw + q.x1) * C;
+  const float* t10 = t + ((int64_t)q.y1 * Tw + q.x0) * C;
+  const float* t11 = t + ((int64_t)q.y1 * Tw + q.x1) * C;
+  float* o = out + g * C;
+  for (int c = 0; c < C; c++) o[c] = mr_mix(q, t00[c], t01[c], t10[c], t11[c]);
+}
+
+__global__ void __launch_bounds__(MR_THREADS)
+mesh_texture_backward_kernel(const float* __restrict__ tex, int64_t tex_stride, const float2* __restrict__ uv, const float* __restrict__ g_out,
+                             int64_t pixels, int64_t per_view, int Th, int Tw, int C, float* __restrict__ g_tex, float2* __restrict__ g_uv) {
+  const int64_t g = (int64_t)blockIdx.x * MR_THREADS + threadIdx.x;
+  if (g >= pixels) return;
+  const float2 st = uv[g];
+  const MrBil q = mr_bilinear(st.x, st.y, Th, Tw);
+  const int64_t base = (g / per_view) * tex_stride;
+  const int64_t o00 = base + ((int64_t)q.y0 * Tw + q.x0) * C, o01 = base + ((int64_t)q.y0 * Tw + q.x1) * C,
+                o10 = base + ((int64_t)q.y1 * Tw + q.x0) * C, o11 = base + ((int64_t)q.y1 * Tw + q.x1) * C;
+  const float w00 = (1.f - q.fy) * (1.f - q.fx), w01 = (1.f - q.fy) * q.fx, w10 = q.fy * (1.f - q.fx), w11 = q.fy * q.fx;
+  const float* go = g_out + g * C;
+  float gs = 0.f, gt = 0.f;
+  for (int c = 0; c < C; c++) {
+    const float v = go[c];
+    if (g_tex) {
+      atomicAdd(g_tex + o00 + c, w00 * v);
+      atomicAdd(g_tex + o01 + c, w01 * v);
+      atomicAdd(g_tex + o10 + c, w10 * v);
+      atomicAdd(g_tex + o11 + c, w11 * v);
+    }
+    if (g_uv) {
+      const float t00 = tex[o00 + c], t01 = tex[o01 + c], t10 = tex[o10 + c], t11 = tex[o11 + c];
+      gs += v * ((1.f - q.fy) * (t01 - t00) + q.fy * (t11 - t10));
+      gt += v * ((1.f - q.fx) * (t10 - t00) + q.fx * (t11 - t01));
+    }
+  }
+  if (g_uv) g_uv[g] = make_float2(gs * (float)Tw, gt * (float)Th);
+}
+
+// ------------------------------------------------------------------------------------------------------------------ C-ABI
+static int mr_image_ok(int32_t B, int32_t H, int32_t W) {
+  return B >= 1 && H >= 1 && W >= 1 && H <= MR_MAX_SIZE && W <= MR_MAX_SIZE && (int64_t)B * H * W <= INT32_MAX;
+}
+
+static unsigned mr_blocks(int64_t n) { return (unsigned)((n + MR_THREADS - 1) / MR_THREADS); }
+
+static int mr_done(void) { return hipGetLastError() == hipSuccess ? 0 : 3; }
+
+extern "C" int gip_mesh_raster_workspace_size(int32_t B, int32_t H, int32_t W, int64_t F, size_t* bytes) {
+  if (!bytes || !mr_image_ok(B, H, W) || F < 0 || F > MR_MAX_FACES || (int64_t)B * F > INT32_MAX) return 1;
+  // keys [B, H, W] of 8 bytes, the list's count (16 bytes, keeping the list aligned), the list [B * F] int32
+  *bytes = (size_t)B * H * W * sizeof(mr_key) + 16 + (size_t)B * F * sizeof(int32_t);
+  return 0;
+}
+
+extern "C" int gip_mesh_rasterize(const float* pos, const int32_t* tri, int32_t B, int64_t V, int64_t F, int32_t H, int32_t W,
+                                  int32_t cull_backfaces, void* workspace, size_t workspace_bytes, float* rast, void* stream) {
+  size_t need = 0;
+  if (gip_mesh_raster_workspace_size(B, H, W, F, &need) != 0) return 1;
+  if (V < 0 || V > INT32_MAX || !rast) return 1;
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t pixels = (int64_t)B * H * W;
+  if (F == 0 || V == 0) return hipMemsetAsync(rast, 0, (size_t)pixels * 16, st) == hipSuccess ? 0 : 3;
+  if (!pos || !tri || !workspace || workspace_bytes < need) return 1;
+  mr_key* keys = (mr_key*)workspace;
+  uint32_t* count = (uint32_t*)(keys + pixels);
+  int32_t* list = (int32_t*)(count + 4);
+  if (hipMemsetAsync(keys, 0xFF, (size_t)pixels * sizeof(mr_key), st) != hipSuccess) return 3;
+  if (hipMemsetAsync(count, 0, 16, st) != hipSuccess) return 3;
+  hipLaunchKernelGGL(mesh_setup_kernel, dim3(mr_blocks((int64_t)B * F)), dim3(MR_THREADS), 0, st, pos, tri, (int)B, (int)V, (int)F, (int)H,
+                     (int)W, (int)(cull_backfaces != 0), keys, count, list);
+  const int64_t waves = (int64_t)B * F;
+  const unsigned large = (unsigned)((waves + 3) / 4 < MR_LARGE_BLOCKS ? (waves + 3) / 4 : MR_LARGE_BLOCKS);
+  hipLaunchKernelGGL(mesh_large_kernel, dim3(large), dim3(MR_THREADS), 0, st, pos, tri, (int)B, (int)V, (int)F, (int)H, (int)W,
+                     (int)(cull_backfaces != 0), keys, (const uint32_t*)count, (const int32_t*)list);
+  hipLaunchKernelGGL(mesh_resolve_kernel, dim3(mr_blocks(pixels)), dim3(MR_THREADS), 0, st, pos, tri, (int)B, (int)V, (int)F, (int)H, (int)W,
+                     (const mr_key*)keys, (float4*)rast);
+  return mr_done();
+}
+
+// the shapes shared by the per-pixel entry points: pixels = B * H * W of rast / uv, a batch of 1 or B on the other operand
+static int mr_batch_ok(int32_t B, int32_t H, int32_t W, int32_t batch) { return mr_image_ok(B, H, W) && (batch == 1 || batch == B); }
+
+extern "C" int gip_mesh_interpolate(const float* attr, int32_t attr_batch, int64_t N, int32_t C, const int32_t* idx, int64_t F,
+                                    const float* rast, int32_t B, int32_t H, int32_t W, float* out, void* stream) {
+  if (!mr_batch_ok(B, H, W, attr_batch) || N < 0 || N > INT32_MAX || C < 1 || F < 0 || F > MR_MAX_FACES || !rast || !out) return 1;
+  if ((!idx && N != 3 * F) || N * C > INT32_MAX || (F > 0 && N > 0 && !attr)) return 1;
+  const int64_t pixels = (int64_t)B * H * W;
+  hipLaunchKernelGGL(mesh_interpolate_kernel, dim3(mr_blocks(pixels)), dim3(MR_THREADS), 0, (hipStream_t)stream, attr,
+                     attr_batch == 1 ? (int64_t)0 : N * C, idx, (const float4*)rast, pixels, (int64_t)H * W, (int)F, (int)N, (int)C, out);
+  return mr_done();
+}
+
+extern "C" int gip_mesh_interpolate_backward(const float* g_out, int32_t attr_batch, int64_t N, int32_t C, const int32_t* idx, int64_t F,
+                                             const float* rast, int32_t B, int32_t H, int32_t W, float* g_attr, void* stream) {
+  if (!mr_batch_ok(B, H, W, attr_batch) || N < 0 || N > INT32_MAX || C < 1 || F < 0 || F > MR_MAX_FACES || !rast || !g_out) return 1;
+  if ((!idx && N != 3 * F) || N * C > INT32_MAX) return 1;
+  if (N == 0) return 0;
+  if (!g_attr) return 1;
+  hipStream_t st = (hipStream_t)stream;
+  if (hipMemsetAsync(g_attr, 0, (size_t)attr_batch * N * C * sizeof(float), st) != hipSuccess) return 3;
+  const int64_t pixels = (int64_t)B * H * W;
+  hipLaunchKernelGGL(mesh_interpolate_backward_kernel, dim3(mr_blocks(pixels)), dim3(MR_THREADS), 0, st, g_out, idx, (const float4*)rast,
+                     pixels, (int64_t)H * W, (int)F, (int)N, (int)C, g_attr, attr_batch == 1 ? (int64_t)0 : N * C);
+  return mr_done();
+}
+
+static int mr_tex_ok(int32_t Th, int32_t Tw, int32_t C) {
+  return Th >= 1 && Tw >= 1 && C >= 1 && Th <= MR_MAX_SIZE && Tw <= MR_MAX_SIZE && (int64_t)Th * Tw * C <= INT32_MAX;
+}
+
+extern "C" int gip_mesh_texture(const float* tex, int32_t tex_batch, int32_t Th, int32_t Tw, int32_t C, const float* uv, int32_t B,
+                                int32_t H, int32_t W, float* out, void* stream) {
+  if (!mr_batch_ok(B, H, W, tex_batch) || !mr_tex_ok(Th, Tw, C) || !tex || !uv || !out) return 1;
+  const int64_t pixels = (int64_t)B * H * W;
+  hipLaunchKernelGGL(mesh_texture_kernel, dim3(mr_blocks(pixels)), dim3(MR_THREADS), 0, (hipStream_t)stream, tex,
+                     tex_batch == 1 ? (int64_t)0 : (int64_t)Th * Tw * C, (const float2*)uv, pixels, (int64_t)H * W, (int)Th, (int)Tw, (int)C,
+                     out);
+  return mr_done();
+}
+
+extern "C" int gip_mesh_texture_backward(const float* tex, int32_t tex_batch, int32_t Th, int32_t Tw, int32_t C, const float* uv,
+                                         const float* g_out, int32_t B, int32_t H, int32_t W, float* g_tex, float* g_uv, void* stream) {
+  if (!mr_batch_ok(B, H, W, tex_batch) || !mr_tex_ok(Th, Tw, C) || !tex || !uv || !g_out) return 1;
+  if (!g_tex && !g_uv) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  if (g_tex && hipMemsetAsync(g_tex, 0, (size_t)tex_batch * Th * Tw * C * sizeof(float), st) != hipSuccess) return 3;
+  const int64_t pixels = (int64_t)B * H * W;
+  hipLaunchKernelGGL(mesh_texture_backward_kernel, dim3(mr_blocks(pixels)), dim3(MR_THREADS), 0, st, tex,
+                     tex_batch == 1 ? (int64_t)0 : (int64_t)Th * Tw * C, (const float2*)uv, g_out, pixels, (int64_t)H * W, (int)Th, (int)Tw,
+                     (int)C, g_tex, (float2*)g_uv);
+  return mr_done();
+}
+
+extern "C" int gip_mesh_shade(const float* rast, const float* uv, int64_t F, int32_t flip_v, const float* tex, int32_t Th, int32_t Tw, const float* bg,
+                              int32_t B, int32_t H, int32_t W, float* shaded, void* stream) {
+  if (!mr_image_ok(B, H, W) || !mr_tex_ok(Th, Tw, 3) || F < 0 || F > MR_MAX_FACES || !rast || !tex || !bg || !shaded) return 1;
+  if (F > 0 && !uv) return 1;
+  const int64_t pixels = (int64_t)B * H * W;
+  hipLaunchKernelGGL(mesh_shade_kernel, dim3(mr_blocks(pixels)), dim3(MR_THREADS), 0, (hipStream_t)stream, (const float4*)rast, uv, tex, bg,
+                     pixels, (int)F, (int)(flip_v != 0), (int)Th, (int)Tw, (float4*)shaded);
+  return mr_done();
+}
+
+extern "C" int gip_mesh_shade_backward(const float* rast, const float* uv, int64_t F, int32_t flip_v, const float* tex, int32_t Th, int32_t Tw,
+                                       const float* g_shaded, int32_t B, int32_t H, int32_t W, float* g_tex, float* g_uv, void* stream) {
+  if (!mr_image_ok(B, H, W) || !mr_tex_ok(Th, Tw, 3) || F < 0 || F > MR_MAX_FACES || !rast || !tex || !g_shaded) return 1;
+  if (F > 0 && !uv) return 1;
+  if (!g_tex && !g_uv) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  if (g_tex && hipMemsetAsync(g_tex, 0, (size_t)Th * Tw * 3 * sizeof(float), st) != hipSuccess) return 3;
+  if (g_uv && F > 0 && hipMemsetAsync(g_uv, 0, (size_t)F * 6 * sizeof(float), st) != hipSuccess) return 3;
+  if (F == 0) return 0;
+  const int64_t pixels = (int64_t)B * H * W;
+  hipLaunchKernelGGL(mesh_shade_backward_kernel, dim3(mr_blocks(pixels)), dim3(MR_THREADS), 0, st, (const float4*)rast, uv, tex,
+                     (const float4*)g_shaded, pixels, (int)F, (int)(flip_v != 0), (int)Th, (int)Tw, g_tex, g_uv);
+  return mr_done();
+}

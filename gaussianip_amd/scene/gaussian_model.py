@@ -465,6 +465,18 @@ class GaussianModel:
             mesh.write_obj_textured(path, vertices, faces, baked["uv"], baked["texture"], normals=normals)
         return vertices, faces, normals, baked["uv"], baked["texture"]
 
+    @torch.no_grad()
+    def render_textured_mesh(self, camera, bg_color=None, **extract_kwargs):
+        """utils.rasterize.render_mesh of extract_textured_mesh(**extract_kwargs) from `camera` (or a list of cameras): the exported
+        mesh on the pixel grid of the Gaussian render of the same camera.  The dict of render_mesh plus "mesh": the tuple that
+        extract_textured_mesh returned."""
+        from ..utils.rasterize import render_mesh
+        mesh = self.extract_textured_mesh(**extract_kwargs)
+        vertices, faces, _, uv, texture = mesh
+        out = render_mesh(camera, vertices, faces, uv, texture, bg_color=bg_color, validate=False)      # the extraction's own faces
+        out["mesh"] = mesh
+        return out
+
     # ------------------------------------------------------------------ initialisation
     def create_from_pcd(self, pcd: BasicPointCloud, spatial_lr_scale: float, dist2=None):
         """`dist2` (mean squared 3-NN distance per point) defaults to the HIP distCUDA2 replacement."""

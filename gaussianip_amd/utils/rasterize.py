@@ -1,0 +1,299 @@
+"""A triangle rasterizer for the exported mesh (csrc/mesh_raster.hip, gip_mesh_*): the reference's nvdiffrast wrapper
+(threestudio/utils/rasterize.py, NVDiffRasterizerContext) on gfx950, and render_mesh, which draws what
+GaussianModel.extract_textured_mesh returns from a Camera.
+
+Conventions (the kernel file's header states the whole definition): positions are clip space, pos [B, V, 4]; pixel (px, py) has its
+centre at NDC ((2 px + 1) / W - 1, (2 py + 1) / H - 1) and the row index grows with NDC y, as in the Gaussian rasterizer, so
+`verts_h @ camera.full_proj_transform` lands pixel for pixel on the Gaussian render.  rast [B, H, W, 4] = (u, v, z/w, triangle index
++ 1), zeros where nothing is drawn.  There is no polygon clipping: a triangle with a vertex at w <= 0 (behind the camera) or beyond the
+guard band is dropped whole, which an orbit camera around an avatar never meets.  The forward is bit-reproducible.  Gradients reach
+attributes and textures through float atomic adds, so the backward is not bit-reproducible.  Three things nvdiffrast has are not
+built: gradients to vertex positions (rast carries none, rast_db is None), antialiasing, and mipmaps (the only filter mode is
+"linear"); the functions raise NotImplementedError naming the argument when asked for them.
+"""
+import ctypes
+
+import torch
+
+from .. import _lib
+
+__all__ = ["MeshRasterizerContext", "render_mesh"]
+
+
+def _p(t):
+    return ctypes.c_void_p(t.data_ptr() if t is not None and t.numel() else None)
+
+
+def _stream(dev):
+    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def _check(rc, name):
+    if rc != 0:
+        raise RuntimeError("%s failed with status %d" % (name, rc))
+
+
+def _gpu_float(t, what, dims, last=None):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() in dims and
+            (last is None or t.shape[-1] == last)):
+        raise ValueError("%s must be a float32 GPU tensor with %s dimensions%s" %
+                         (what, " or ".join(str(d) for d in dims), "" if last is None else " and a last dimension of %d" % last))
+    return t.detach().contiguous()
+
+
+def _resolution(resolution):
+    if isinstance(resolution, (tuple, list)):
+        if len(resolution) != 2:
+            raise ValueError("resolution must be an int or (H, W)")
+        H, W = int(resolution[0]), int(resolution[1])
+    else:
+        H = W = int(resolution)
+    if H < 1 or W < 1 or H > 16384 or W > 16384:
+        raise ValueError("resolution must lie in 1 .. 16384")
+    return H, W
+
+
+def _index_tensor(tri, what, limit, validate=True):
+    """[F, 3] int32 GPU indices.  validate: one host read checks that all lie inside [0, limit) (ValueError otherwise).  A caller that
+    knows its indices, such as the faces extract_mesh returned, passes validate=False and saves the synchronisation; the kernels
+    drop a triangle whose index is out of range, so memory safety does not depend on the check."""
+    if not (isinstance(tri, torch.Tensor) and tri.is_cuda and tri.dtype == torch.int32 and tri.dim() == 2 and tri.shape[1] == 3):
+        raise ValueError("%s must be an [F, 3] int32 GPU tensor" % what)
+    if validate and tri.shape[0]:
+        lo, hi = (int(x) for x in torch.stack((tri.min(), tri.max())).cpu())
+        if lo < 0 or hi >= limit:
+            raise ValueError("%s: indices must lie in [0, %d)" % (what, limit))
+    return tri.detach().contiguous()
+
+
+def _workspace_bytes(B, H, W, F):
+    """gip_mesh_raster_workspace_size's formula (tests/test_mesh_render_cpu.py holds the two together): the [B, H, W] keys of 8 bytes,
+    16 bytes of list count, the list of B * F int32.  gip_mesh_rasterize checks the shape limits and the size itself."""
+    return B * H * W * 8 + 16 + B * F * 4
+
+
+def _no_position_gradient(t, what):
+    if isinstance(t, torch.Tensor) and t.requires_grad and torch.is_grad_enabled():
+        raise NotImplementedError("%s requires a gradient, and no gradient reaches vertex positions: pass %s.detach()" % (what, what))
+
+
+def _rasterize(pos, tri, resolution, cull_backfaces=False, validate=True):
+    _no_position_gradient(pos, "pos")
+    pos = _gpu_float(pos, "pos", (3,), 4)
+    if pos.shape[0] < 1:
+        raise ValueError("pos must be [B, V, 4] with B >= 1")
+    B, V = int(pos.shape[0]), int(pos.shape[1])
+    tri = _index_tensor(tri, "tri", V, validate)
+    if tri.device != pos.device:
+        raise ValueError("pos and tri must live on the same device")
+    H, W = _resolution(resolution)
+    F = int(tri.shape[0])
+    if F == 0:      # nothing to draw: no launch
+        return torch.zeros((B, H, W, 4), dtype=torch.float32, device=pos.device)
+    if B * H * W > 2 ** 31 - 1 or F > 2 ** 24 - 1 or B * F > 2 ** 31 - 1:
+        raise ValueError("rasterize: %d views of %d x %d with %d triangles are outside the limits of gip_mesh_rasterize" % (B, H, W, F))
+    need = _workspace_bytes(B, H, W, F)
+    ws = torch.empty(need, dtype=torch.uint8, device=pos.device)
+    rast = torch.empty((B, H, W, 4), dtype=torch.float32, device=pos.device)
+    with torch.cuda.device(pos.device):
+        _check(_lib.model_lib().gip_mesh_rasterize(_p(pos), _p(tri), B, V, F, H, W, int(bool(cull_backfaces)), _p(ws), need, _p(rast),
+                                                   _stream(pos.device)), "gip_mesh_rasterize")
+    return rast
+
+
+def _rast_tensor(rast):
+    return _gpu_float(rast, "rast", (4,), 4)
+
+
+class _Interpolate(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, attr, rast, idx, F):
+        B, H, W, _ = rast.shape
+        nb, N, C = attr.shape
+        out = torch.empty((B, H, W, C), dtype=torch.float32, device=rast.device)
+        with torch.cuda.device(rast.device):
+            _check(_lib.model_lib().gip_mesh_interpolate(_p(attr), nb, N, C, _p(idx), F, _p(rast), B, H, W, _p(out), _stream(rast.device)),
+                   "gip_mesh_interpolate")
+        ctx.save_for_backward(rast, idx)
+        ctx.shape, ctx.F = (nb, N, C), F
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        rast, idx = ctx.saved_tensors
+        nb, N, C = ctx.shape
+        B, H, W, _ = rast.shape
+        g = g.contiguous().float()
+        g_attr = torch.empty((nb, N, C), dtype=torch.float32, device=rast.device)
+        with torch.cuda.device(rast.device):
+            _check(_lib.model_lib().gip_mesh_interpolate_backward(_p(g), nb, N, C, _p(idx), ctx.F, _p(rast), B, H, W, _p(g_attr),
+                                                                  _stream(rast.device)), "gip_mesh_interpolate_backward")
+        return g_attr, None, None, None
+
+
+class _Texture(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, tex, uv):
+        nb, Th, Tw, C = tex.shape
+        B, H, W, _ = uv.shape
+        out = torch.empty((B, H, W, C), dtype=torch.float32, device=uv.device)
+        with torch.cuda.device(uv.device):
+            _check(_lib.model_lib().gip_mesh_texture(_p(tex), nb, Th, Tw, C, _p(uv), B, H, W, _p(out), _stream(uv.device)), "gip_mesh_texture")
+        ctx.save_for_backward(tex, uv)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        tex, uv = ctx.saved_tensors
+        nb, Th, Tw, C = tex.shape
+        B, H, W, _ = uv.shape
+        g = g.contiguous().float()
+        g_tex = torch.empty_like(tex) if ctx.needs_input_grad[0] else None
+        g_uv = torch.empty_like(uv) if ctx.needs_input_grad[1] else None
+        with torch.cuda.device(uv.device):
+            _check(_lib.model_lib().gip_mesh_texture_backward(_p(tex), nb, Th, Tw, C, _p(uv), _p(g), B, H, W, _p(g_tex), _p(g_uv),
+                                                              _stream(uv.device)), "gip_mesh_texture_backward")
+        return g_tex, g_uv
+
+
+class _Shade(torch.autograd.Function):
+    """shaded [B, H, W, 4] = (r, g, b, alpha): the fused interpolate -> lookup -> composite of render_mesh."""
+
+    @staticmethod
+    def forward(ctx, tex, uv, rast, bg, flip_v):
+        Th, Tw, _ = tex.shape
+        B, H, W, _ = rast.shape
+        F = int(uv.shape[0])
+        shaded = torch.empty((B, H, W, 4), dtype=torch.float32, device=rast.device)
+        with torch.cuda.device(rast.device):
+            _check(_lib.model_lib().gip_mesh_shade(_p(rast), _p(uv), F, int(flip_v), _p(tex), Th, Tw, _p(bg), B, H, W, _p(shaded),
+                                                   _stream(rast.device)), "gip_mesh_shade")
+        ctx.save_for_backward(tex, uv, rast)
+        ctx.flip_v = int(flip_v)
+        return shaded
+
+    @staticmethod
+    def backward(ctx, g):
+        tex, uv, rast = ctx.saved_tensors
+        Th, Tw, _ = tex.shape
+        B, H, W, _ = rast.shape
+        F = int(uv.shape[0])
+        g = g.contiguous().float()
+        g_tex = torch.empty_like(tex) if ctx.needs_input_grad[0] else None
+        g_uv = torch.empty_like(uv) if ctx.needs_input_grad[1] else None
+        if F == 0:      # nothing was drawn: no launch
+            return (None if g_tex is None else torch.zeros_like(tex)), (None if g_uv is None else torch.zeros_like(uv)), None, None, None
+        with torch.cuda.device(rast.device):
+            _check(_lib.model_lib().gip_mesh_shade_backward(_p(rast), _p(uv), F, ctx.flip_v, _p(tex), Th, Tw, _p(g), B, H, W, _p(g_tex),
+                                                            _p(g_uv), _stream(rast.device)), "gip_mesh_shade_backward")
+        return g_tex, g_uv, None, None, None
+
+
+class MeshRasterizerContext:
+    """The interface of the reference's NVDiffRasterizerContext.  context_type is accepted and ignored (there is one rasterizer)."""
+
+    def __init__(self, context_type=None, device="cuda"):
+        self.device = torch.device(device)
+
+    def vertex_transform(self, verts, mvp_mtx):
+        """[B, V, 4] clip-space positions of verts [V, 3] under mvp_mtx [B, 4, 4] (column-vector convention: p = mvp @ (x, 1))."""
+        homogeneous = torch.cat((verts, verts.new_ones((verts.shape[0], 1))), 1)
+        return torch.einsum("bij,vj->bvi", mvp_mtx.to(verts.dtype), homogeneous)
+
+    def rasterize(self, pos, tri, resolution, cull_backfaces=False, validate=True):
+        """(rast [B, H, W, 4], None) of pos [B, V, 4] float32 and tri [F, 3] int32, one topology for all views; resolution an int or
+        (H, W).  The second value is nvdiffrast's rast_db, which is not computed: no gradient reaches `pos`.  ValueError for CPU
+        tensors, a wrong dtype or shape, or indices outside [0, V) (one host read; validate=False skips it for indices known to be
+        good: the kernels drop a triangle with an index out of range)."""
+        return _rasterize(pos, tri, resolution, cull_backfaces, validate), None
+
+    def rasterize_one(self, pos, tri, resolution, cull_backfaces=False, validate=True):
+        """rasterize of one view: pos [V, 4] -> (rast [H, W, 4], None)."""
+        if not (isinstance(pos, torch.Tensor) and pos.dim() == 2):
+            raise ValueError("rasterize_one needs pos as [V, 4]")
+        return _rasterize(pos[None, ...], tri, resolution, cull_backfaces, validate)[0], None
+
+    def antialias(self, color, rast, pos, tri):
+        raise NotImplementedError("antialias: the mesh rasterizer has no antialiasing pass")
+
+    def interpolate(self, attr, rast, tri, rast_db=None, diff_attrs=None):
+        """(out [B, H, W, C], None): attr [1 or B, N, C] (or [N, C]) at the corners tri [F, 3] names, weighted by rast's (u, v, 1 - u -
+        v); zeros at empty pixels.  `tri` may be the mesh's faces or an attribute's own index tensor of the same F.  Differentiable
+        in attr (float atomic adds: not bit-reproducible)."""
+        if rast_db is not None:
+            raise NotImplementedError("interpolate: rast_db (pixel differentials) is not supported")
+        if diff_attrs is not None:
+            raise NotImplementedError("interpolate: diff_attrs (attribute pixel differentials) is not supported")
+        if not (isinstance(attr, torch.Tensor) and attr.is_cuda and attr.dtype == torch.float32 and attr.dim() in (2, 3)):
+            raise ValueError("attr must be a float32 GPU tensor, [N, C] or [1 or B, N, C]")
+        rast = _rast_tensor(rast)
+        a = attr[None] if attr.dim() == 2 else attr
+        if a.shape[0] not in (1, rast.shape[0]) or a.shape[2] < 1:
+            raise ValueError("attr must have a batch of 1 or B and at least one channel")
+        idx = _index_tensor(tri, "tri", int(a.shape[1]))
+        return _Interpolate.apply(a.contiguous(), rast, idx, int(idx.shape[0])), None
+
+    def interpolate_one(self, attr, rast, tri, rast_db=None, diff_attrs=None):
+        return self.interpolate(attr[None, ...], rast, tri, rast_db, diff_attrs)
+
+    def texture(self, tex, uv, filter_mode="linear", uv_da=None, mip=None):
+        """[B, H, W, C]: the bilinear lookup of tex [1 or B, Th, Tw, C] (or [Th, Tw, C]) at uv [B, H, W, 2]; uv (0, 0) is the corner
+        of tex[0, 0], texel centres lie at (i + 0.5) / T, indices are clamped at the border.  Differentiable in tex and uv."""
+        if filter_mode != "linear":
+            raise NotImplementedError("texture: filter_mode %r is not supported, only 'linear' (no mipmaps)" % (filter_mode,))
+        if uv_da is not None or mip is not None:
+            raise NotImplementedError("texture: %s (mipmaps) is not supported" % ("uv_da" if uv_da is not None else "mip"))
+        for t, what in ((tex, "tex"), (uv, "uv")):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32):
+                raise ValueError("%s must be a float32 GPU tensor" % what)
+        if uv.dim() != 4 or uv.shape[-1] != 2 or tex.dim() not in (3, 4):
+            raise ValueError("texture needs tex [1 or B, Th, Tw, C] or [Th, Tw, C] and uv [B, H, W, 2]")
+        t = tex[None] if tex.dim() == 3 else tex
+        if t.shape[0] not in (1, uv.shape[0]) or min(t.shape[1:]) < 1 or max(t.shape[1:3]) > 16384:
+            raise ValueError("tex must have a batch of 1 or B, at least one texel and channel, and at most 16384 texels a side")
+        return _Texture.apply(t.contiguous(), uv.contiguous())
+
+
+def render_mesh(camera, vertices, faces, uv, texture, bg_color=None, cull_backfaces=False, validate=True):
+    """{"image": [3, H, W], "alpha": [1, H, W], "depth": [1, H, W], "rast": [H, W, 4]} of the textured mesh that
+    GaussianModel.extract_textured_mesh returns (vertices [V, 3] float32 world coordinates, faces [F, 3] int32, uv [F, 3, 2], texture
+    [T, T, 3], all on the GPU), seen from `camera` (its full_proj_transform and image size): the same pixel grid as the Gaussian
+    render of that camera.  A list of cameras renders as one batch, and every entry gains a leading dimension B.
+
+    uv is in the OBJ convention of extract_textured_mesh (v = 1 - (row + 0.5) / T) and is flipped in the shade kernels.  validate=False
+    skips the host read that checks the faces' indices (GaussianModel.render_textured_mesh does: its faces come from the extraction).  alpha is coverage (0 / 1),
+    depth is z/w of the projection (0 where nothing is drawn), bg_color [3] defaults to black.  image, alpha and depth are views of
+    the kernels' interleaved outputs (`.contiguous()` copies them).  Differentiable in texture (and in uv): float atomic adds, so the
+    backward is not bit-reproducible; the forward is.  No gradient reaches the vertices, nothing is antialiased, and a triangle with a
+    vertex behind the camera is dropped whole (no clipping).  Two calls into the library: rasterize and shade."""
+    many = isinstance(camera, (list, tuple))
+    cams = list(camera) if many else [camera]
+    if not cams:
+        raise ValueError("render_mesh needs at least one camera")
+    _no_position_gradient(vertices, "vertices")
+    vertices = _gpu_float(vertices, "vertices", (2,), 3)
+    dev = vertices.device
+    if not (isinstance(uv, torch.Tensor) and uv.is_cuda and uv.dtype == torch.float32 and uv.dim() == 3 and tuple(uv.shape[1:]) == (3, 2)):
+        raise ValueError("uv must be an [F, 3, 2] float32 GPU tensor")
+    if not (isinstance(texture, torch.Tensor) and texture.is_cuda and texture.dtype == torch.float32 and texture.dim() == 3 and
+            texture.shape[2] == 3 and min(texture.shape[:2]) >= 1 and max(texture.shape[:2]) <= 16384):
+        raise ValueError("texture must be a [Th, Tw, 3] float32 GPU tensor of at most 16384 texels a side")
+    H, W = int(cams[0].image_height), int(cams[0].image_width)
+    if any((int(c.image_height), int(c.image_width)) != (H, W) for c in cams):
+        raise ValueError("render_mesh: the cameras of one batch must share an image size")
+    if not (isinstance(faces, torch.Tensor) and faces.dim() == 2 and uv.shape[0] == faces.shape[0]):
+        raise ValueError("uv must have one [3, 2] entry per face")
+    if bg_color is None:
+        bg = torch.zeros(3, dtype=torch.float32, device=dev)
+    else:
+        bg = torch.as_tensor(bg_color, dtype=torch.float32).to(dev).reshape(-1).contiguous()
+        if bg.numel() != 3:
+            raise ValueError("bg_color must have 3 values")
+    mvp = torch.stack([c.full_proj_transform.to(dev).float() for c in cams])               # [B, 4, 4], row-vector convention
+    verts_h = torch.cat((vertices, torch.ones_like(vertices[:, :1])), 1)
+    pos = torch.matmul(verts_h[None], mvp).contiguous()                                     # [B, V, 4]
+    rast = _rasterize(pos, faces, (H, W), cull_backfaces, validate)
+    shaded = _Shade.apply(texture.contiguous(), uv.contiguous(), rast, bg, 1)
+    out = {"image": shaded[..., :3].permute(0, 3, 1, 2), "alpha": shaded[..., 3:].permute(0, 3, 1, 2),
+           "depth": rast[..., 2:3].permute(0, 3, 1, 2), "rast": rast}
+    return out if many else {k: v[0] for k, v in out.items()}

@@ -185,6 +185,42 @@ int gip_texture_bake(const float* xyz, const float* opacity, const float* scalin
                      const float* vertices, int64_t V, const int32_t* faces, int64_t F, const int32_t* face_order,
                      const int32_t* block_start, int32_t T, int32_t cell, int32_t slices, void* workspace, size_t workspace_bytes,
                      float* density, float* color_sum, void* stream);
+/* Rendering the textured mesh (csrc/mesh_raster.hip, whose header states the definition of coverage, visibility, interpolation and
+ * lookup; gaussianip_amd/utils/rasterize.py).  All tensors float32 and contiguous, indices int32, everything on the device.
+ *   gip_mesh_rasterize  pos [B, V, 4] clip space, tri [F, 3], one topology for all views -> rast [B, H, W, 4] = (u, v, depth z/w,
+ *       triangle index + 1), zeros at an empty pixel; u, v the perspective-correct weights of corners 0 and 1.  Pixel (px, py) has its
+ *       centre at NDC ((2 px + 1) / W - 1, (2 py + 1) / H - 1); no polygon clipping: a triangle with a vertex at w <= 0 or beyond the
+ *       guard band is dropped whole.  cull_backfaces != 0 drops triangles of negative area.  Bit-reproducible.  F == 0 or V == 0 only
+ *       zero-fills rast.  The workspace (gip_mesh_raster_workspace_size: the key buffer and the list of large triangles) is the caller's.
+ *   gip_mesh_interpolate  out [B, H, W, C] = the rows idx[f][0..2] of attr [attr_batch, N, C] (attr_batch 1 or B) weighted by
+ *       (u, v, 1 - u - v) of rast; idx [F, 3], or NULL for face-varying attributes (N == 3 F, row 3 f + corner).  Zeros at empty pixels.
+ *   gip_mesh_interpolate_backward  g_attr [attr_batch, N, C] from g_out [B, H, W, C]; zero-filled here, then float atomic adds.
+ *   gip_mesh_texture  out [B, H, W, C] = the bilinear lookup of tex [tex_batch, Th, Tw, C] (tex_batch 1 or B) at uv [B, H, W, 2]; uv
+ *       (0, 0) is the corner of tex[0, 0], texel centres at (i + 0.5) / T, indices clamped at the border.
+ *   gip_mesh_texture_backward  g_tex (zero-filled here, then float atomic adds; or NULL) and g_uv [B, H, W, 2] (or NULL).
+ *   gip_mesh_shade  the fused forward: shaded [B, H, W, 4] = (r, g, b, alpha) with the colour the lookup of tex [Th, Tw, 3] at the
+ *       interpolated face-varying uv [F, 3, 2] and alpha 1 at a covered pixel, (bg[0..2], 0) at an empty one.  flip_v != 0: uv is in the
+ *       OBJ convention and every corner's v is replaced by 1 - v before it is interpolated (g_uv is then the gradient to the OBJ uv).
+ *   gip_mesh_shade_backward  g_tex [Th, Tw, 3] and g_uv [F, 3, 2] (either may be NULL) from g_shaded [B, H, W, 4] (its alpha is
+ *       ignored: coverage has no gradient); zero-filled here, then float atomic adds, so not bit-reproducible.
+ * No gradient reaches pos.  Status 1: a NULL required pointer, B, H, W < 1, H or W > 16384, B H W > 2^31 - 1, F > 2^24 - 1 (the index
+ * is stored in a float), B F > 2^31 - 1, a batch that is neither 1 nor B, a texture above 16384 a side, a short workspace.
+ * Status 3: a launch error. */
+int gip_mesh_raster_workspace_size(int32_t B, int32_t H, int32_t W, int64_t F, size_t* bytes);
+int gip_mesh_rasterize(const float* pos, const int32_t* tri, int32_t B, int64_t V, int64_t F, int32_t H, int32_t W,
+                       int32_t cull_backfaces, void* workspace, size_t workspace_bytes, float* rast, void* stream);
+int gip_mesh_interpolate(const float* attr, int32_t attr_batch, int64_t N, int32_t C, const int32_t* idx, int64_t F, const float* rast,
+                         int32_t B, int32_t H, int32_t W, float* out, void* stream);
+int gip_mesh_interpolate_backward(const float* g_out, int32_t attr_batch, int64_t N, int32_t C, const int32_t* idx, int64_t F,
+                                  const float* rast, int32_t B, int32_t H, int32_t W, float* g_attr, void* stream);
+int gip_mesh_texture(const float* tex, int32_t tex_batch, int32_t Th, int32_t Tw, int32_t C, const float* uv, int32_t B, int32_t H,
+                     int32_t W, float* out, void* stream);
+int gip_mesh_texture_backward(const float* tex, int32_t tex_batch, int32_t Th, int32_t Tw, int32_t C, const float* uv, const float* g_out,
+                              int32_t B, int32_t H, int32_t W, float* g_tex, float* g_uv, void* stream);
+int gip_mesh_shade(const float* rast, const float* uv, int64_t F, int32_t flip_v, const float* tex, int32_t Th, int32_t Tw, const float* bg, int32_t B,
+                   int32_t H, int32_t W, float* shaded, void* stream);
+int gip_mesh_shade_backward(const float* rast, const float* uv, int64_t F, int32_t flip_v, const float* tex, int32_t Th, int32_t Tw, const float* g_shaded,
+                            int32_t B, int32_t H, int32_t W, float* g_tex, float* g_uv, void* stream);
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,181 @@
+#!/usr/bin/env python3
+"""Times the mesh renderer (csrc/mesh_raster.hip, gaussianip_amd/utils/rasterize.py): the blob cloud of tests/sample_inputs.py extracted
+at resolution 256 with its baked texture, rendered from 4 orbit cameras at 1024 x 1024 as one batch, forward and forward + backward
+(the gradient of a fixed random upstream gradient to the texture).
+
+Times are device events around windows of --iters renders: the median of --windows windows after --warmup windows, per render.
+Kernel times come from a kernel trace taken in a run of its own and are merged afterwards:
+    python tools/bench_mesh_render.py [--out profiles/mesh_render.json]
+    rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/bench_mesh_render.py --once 20
+    python tools/bench_mesh_render.py --kernel-stats DIR/*/*_kernel_stats.csv [--out profiles/mesh_render.json]
+Beside every kernel's time stand the bytes it must move (computed here from the shapes and the counts of the scene, not measured)
+and the share of the HBM roofline that makes: those bytes over the time, over 8.0 TB/s (the float atomic adds of the backward over the
+1.3 TB/s at which the chip adds)."""
+import argparse
+import csv
+import json
+import math
+import os
+import statistics
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+HBM_PEAK = 8.0e12            # bytes per second, the specified peak
+ATOMIC_RATE = 1.3e12         # added bytes per second of float atomic adds, chip-wide
+SIZE, VIEWS, RESOLUTION = 1024, 4, 256
+KERNELS = ("mesh_setup_kernel", "mesh_large_kernel", "mesh_resolve_kernel", "mesh_shade_kernel", "mesh_shade_backward_kernel")
+
+
+def make_scene():
+    import sample_inputs
+    import scenes
+    from gaussianip_amd.scene import Camera, GaussianModel
+    from gaussianip_amd.utils.sh import C0
+    cl = sample_inputs.blob_cloud()
+    P = cl["xyz"].shape[0]
+    gm = GaussianModel(0)
+    gm._xyz, gm._opacity = torch.from_numpy(cl["xyz"]).cuda(), torch.from_numpy(cl["opacity"]).cuda()
+    gm._scaling, gm._rotation = torch.from_numpy(cl["scaling"]).cuda(), torch.from_numpy(cl["rotation"]).cuda()
+    gm._features_dc = ((torch.from_numpy(sample_inputs.colors(P, 9)).cuda() - 0.5) / C0).reshape(P, 1, 3).contiguous()
+    gm._features_rest = torch.zeros((P, 0, 3), device="cuda")
+    cams = [Camera(c2w=scenes.orbit_c2w(15.0, -180.0 + 90.0 * i, 1.6).cuda(), FoVy=math.radians(50.0), height=SIZE, width=SIZE)
+            for i in range(VIEWS)]
+    mesh = gm.extract_textured_mesh(density_thresh=1.0, resolution=RESOLUTION, num_blocks=16)
+    return gm, cams, mesh
+
+
+def windows(fn, iters, count, warmup):
+    for _ in range(warmup):
+        for _ in range(iters):
+            fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(count):
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        for _ in range(iters):
+            fn()
+        t1.record()
+        t1.synchronize()
+        ms.append(t0.elapsed_time(t1) / iters)
+    return {"median_ms": statistics.median(ms), "min_ms": min(ms), "max_ms": max(ms)}
+
+
+def required_bytes(counts):
+    """The bytes every kernel must move at least, from the shapes: name -> (bytes, what they are)."""
+    px, F, V, T = counts["pixels"], counts["faces"], counts["vertices"], counts["texture_size"]
+    covered, frags = counts["covered_pixels"], counts["fragments_at_least"]
+    return {
+        "mesh_setup_kernel": (VIEWS * (F * 12 + V * 16) + frags * 8,
+                              "per view the index triples and every vertex once, an 8-byte atomic minimum per fragment (at least one per covered pixel)"),
+        "mesh_large_kernel": (4, "the list's count; this scene lists no triangle"),
+        "mesh_resolve_kernel": (px * 24 + covered * 0, "8-byte key in, 16-byte rast out per pixel (the winning triangle's vertices come from cache)"),
+        "mesh_shade_kernel": (px * 32 + counts["visible_faces"] * 24, "16-byte rast in, 16 bytes out per pixel, the visible faces' uv once (texels come from cache)"),
+        "mesh_shade_backward_kernel": (px * 32 + counts["visible_faces"] * 24 + covered * 48,
+                                       "rast and the upstream gradient in, 12 float atomic adds per covered pixel; its memset of the %d x %d x 3 "
+                                       "gradient (%d bytes) is a launch of its own" % (T, T, T * T * 12)),
+    }
+
+
+def measure(args):
+    from gaussianip_amd.arguments import PipelineParams
+    from gaussianip_amd.renderer import render
+    from gaussianip_amd.utils.rasterize import render_mesh
+    gm, cams, (v, f, _, uv, texture) = make_scene()
+    tex = texture.clone().requires_grad_(True)
+    g = torch.randn((VIEWS, 3, SIZE, SIZE), device="cuda", generator=torch.Generator(device="cuda").manual_seed(0))
+
+    def forward():
+        with torch.no_grad():
+            return render_mesh(cams, v, f, uv, texture, validate=False)
+
+    def both():
+        tex.grad = None
+        (render_mesh(cams, v, f, uv, tex, validate=False)["image"] * g).sum().backward()
+
+    out = forward()
+    ids = out["rast"][..., 3].long() - 1
+    covered = int((ids >= 0).sum())
+    visible = sum(int(torch.unique(ids[b][ids[b] >= 0]).numel()) for b in range(VIEWS))
+    counts = {"faces": int(f.shape[0]), "vertices": int(v.shape[0]), "texture_size": int(texture.shape[0]), "views": VIEWS, "image": SIZE,
+              "pixels": VIEWS * SIZE * SIZE, "covered_pixels": covered, "visible_faces": visible, "fragments_at_least": covered}
+    with torch.no_grad():
+        bg = torch.zeros(3, device="cuda")
+        gauss = render(cams[0], gm, PipelineParams(argparse.ArgumentParser()), bg)["render"]
+        psnr = -10 * math.log10(float(((gauss - out["image"][0]) ** 2).mean()))
+    result = {"device": "%s (%s)" % (torch.cuda.get_device_name(0), torch.cuda.get_device_properties(0).gcnArchName),
+              "scene": "blob_cloud extracted at resolution %d, %d orbit cameras at %d x %d as one batch" % (RESOLUTION, VIEWS, SIZE, SIZE),
+              "counts": counts, "psnr_db_mesh_vs_gaussians_view0": psnr,
+              "timing": "device events, median of %d windows of %d renders after %d warm-up windows, ms per render of the batch" % (
+                  args.windows, args.iters, args.warmup),
+              "forward": windows(forward, args.iters, args.windows, args.warmup),
+              "forward_backward": windows(both, args.iters, args.windows, args.warmup)}
+    return result
+
+
+def merge_kernel_stats(result, path):
+    """Per-kernel average times of a `rocprofv3 --kernel-trace --stats` run of `--once`, with the bytes each kernel must move."""
+    need = required_bytes(result["counts"])
+    kernels = {}
+    with open(path, newline="") as fh:
+        for row in csv.DictReader(fh):
+            name = row.get("Name", "")
+            for k in KERNELS:
+                if name.startswith(k):
+                    avg_ns = float(row["AverageNs"])
+                    nbytes, what = need[k]
+                    atomics = result["counts"]["covered_pixels"] * 48 if k == "mesh_shade_backward_kernel" else 0
+                    floor_s = max(nbytes / HBM_PEAK, atomics / ATOMIC_RATE)
+                    kernels[k] = {"calls": int(row["Calls"]), "average_us": avg_ns / 1e3, "min_us": float(row["MinNs"]) / 1e3,
+                                  "max_us": float(row["MaxNs"]) / 1e3, "required_bytes": nbytes, "required_bytes_are": what,
+                                  "achieved_TB_per_s": nbytes / avg_ns / 1e3, "hbm_roofline_fraction": nbytes / HBM_PEAK / (avg_ns * 1e-9),
+                                  "bound_fraction_with_atomic_rate": floor_s / (avg_ns * 1e-9)}
+    result["kernels"] = kernels
+    result["kernel_times_from"] = "rocprofv3 --kernel-trace --stats of --once, a run of its own"
+    return result
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--windows", type=int, default=11)
+    ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--once", type=int, default=0)
+    ap.add_argument("--kernel-stats", default=None)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mesh_render.json"))
+    args = ap.parse_args()
+    if args.kernel_stats:
+        with open(args.out) as fh:
+            result = json.load(fh)
+        result = merge_kernel_stats(result, args.kernel_stats)
+    elif args.once:
+        from gaussianip_amd.utils.rasterize import render_mesh
+        _, cams, (v, f, _, uv, texture) = make_scene()
+        tex = texture.clone().requires_grad_(True)
+        g = torch.randn((VIEWS, 3, SIZE, SIZE), device="cuda", generator=torch.Generator(device="cuda").manual_seed(0))
+        for _ in range(args.once):
+            tex.grad = None
+            (render_mesh(cams, v, f, uv, tex, validate=False)["image"] * g).sum().backward()
+        torch.cuda.synchronize()
+        return
+    else:
+        assert torch.cuda.is_available(), "bench_mesh_render needs a GPU"
+        result = measure(args)
+        if os.path.exists(args.out):      # what tests/test_gpu_mesh_render.py added to the file stays
+            with open(args.out) as fh:
+                kept = json.load(fh).get("alignment_test_128")
+            if kept is not None:
+                result["alignment_test_128"] = kept
+    text = json.dumps(result, indent=1, sort_keys=True)
+    print(text)
+    with open(args.out, "w") as fh:
+        fh.write(text + "\n")
+
+
+if __name__ == "__main__":
+    main()
