@@ -229,6 +229,16 @@ def model_lib():
         lib.gip_mesh_shade.argtypes = [_vp, _vp, _i64, _i32, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _vp, _vp]
         lib.gip_mesh_shade_backward.restype = ctypes.c_int
         lib.gip_mesh_shade_backward.argtypes = [_vp, _vp, _i64, _i32, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp]
+        lib.gip_mesh_rasterize_backward.restype = ctypes.c_int
+        lib.gip_mesh_rasterize_backward.argtypes = [_vp, _vp, _i32, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp]
+        lib.gip_mesh_interpolate_backward_rast.restype = ctypes.c_int
+        lib.gip_mesh_interpolate_backward_rast.argtypes = [_vp, _vp, _i32, _i64, _i32, _vp, _i64, _vp, _i32, _i32, _i32, _vp, _vp]
+        lib.gip_mesh_shade_backward_rast.restype = ctypes.c_int
+        lib.gip_mesh_shade_backward_rast.argtypes = [_vp, _vp, _i64, _i32, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _vp, _vp]
+        lib.gip_mesh_antialias.restype = ctypes.c_int
+        lib.gip_mesh_antialias.argtypes = [_vp, _i32, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i32, _i32, _vp, _vp]
+        lib.gip_mesh_antialias_backward.restype = ctypes.c_int
+        lib.gip_mesh_antialias_backward.argtypes = [_vp, _i32, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp]
         _model = _Counted(lib)
     return _model
 
@@ -376,3 +386,5 @@ SAMPLE_SYMBOLS = ["gip_field_sample_workspace_size", "gip_field_sample"]
 TEXTURE_SYMBOLS = ["gip_texture_bake_workspace_size", "gip_texture_bake"]
 MESH_SYMBOLS = ["gip_mesh_raster_workspace_size", "gip_mesh_rasterize", "gip_mesh_interpolate", "gip_mesh_interpolate_backward",
                 "gip_mesh_texture", "gip_mesh_texture_backward", "gip_mesh_shade", "gip_mesh_shade_backward"]
+MESH_GRAD_SYMBOLS = ["gip_mesh_rasterize_backward", "gip_mesh_interpolate_backward_rast", "gip_mesh_shade_backward_rast", "gip_mesh_antialias",
+                     "gip_mesh_antialias_backward"]

@@ -466,14 +466,15 @@ class GaussianModel:
         return vertices, faces, normals, baked["uv"], baked["texture"]
 
     @torch.no_grad()
-    def render_textured_mesh(self, camera, bg_color=None, **extract_kwargs):
+    def render_textured_mesh(self, camera, bg_color=None, position_gradients=False, antialias=False, **extract_kwargs):
         """utils.rasterize.render_mesh of extract_textured_mesh(**extract_kwargs) from `camera` (or a list of cameras): the exported
         mesh on the pixel grid of the Gaussian render of the same camera.  The dict of render_mesh plus "mesh": the tuple that
-        extract_textured_mesh returned."""
+        extract_textured_mesh returned.  position_gradients and antialias are render_mesh's keywords."""
         from ..utils.rasterize import render_mesh
         mesh = self.extract_textured_mesh(**extract_kwargs)
         vertices, faces, _, uv, texture = mesh
-        out = render_mesh(camera, vertices, faces, uv, texture, bg_color=bg_color, validate=False)      # the extraction's own faces
+        out = render_mesh(camera, vertices, faces, uv, texture, bg_color=bg_color, validate=False,      # the extraction's own faces
+                          position_gradients=position_gradients, antialias=antialias)
         out["mesh"] = mesh
         return out
 

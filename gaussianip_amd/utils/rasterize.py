@@ -7,9 +7,14 @@ centre at NDC ((2 px + 1) / W - 1, (2 py + 1) / H - 1) and the row index grows w
 `verts_h @ camera.full_proj_transform` lands pixel for pixel on the Gaussian render.  rast [B, H, W, 4] = (u, v, z/w, triangle index
 + 1), zeros where nothing is drawn.  There is no polygon clipping: a triangle with a vertex at w <= 0 (behind the camera) or beyond the
 guard band is dropped whole, which an orbit camera around an avatar never meets.  The forward is bit-reproducible.  Gradients reach
-attributes and textures through float atomic adds, so the backward is not bit-reproducible.  Three things nvdiffrast has are not
-built: gradients to vertex positions (rast carries none, rast_db is None), antialiasing, and mipmaps (the only filter mode is
-"linear"); the functions raise NotImplementedError naming the argument when asked for them.
+attributes and textures through float atomic adds, so the backward is not bit-reproducible.
+
+Gradients to vertex positions and the antialias pass (csrc/mesh_grad.hip) are opt-in: DiffMeshRasterizerContext, and the keywords
+position_gradients / antialias of render_mesh.  There rast carries a gradient to pos (the snapping is straight-through), interpolate
+and the fused shade are differentiable in rast, and antialias blends across silhouette edges, which is the one route by which a loss
+on coverage reaches the geometry.  The default MeshRasterizerContext and the default keywords behave as they always did and raise
+NotImplementedError when asked for either.  One piece of nvdiffrast is still missing: mipmaps (rast_db, diff_attrs, uv_da, mip, any
+filter mode but "linear"); the functions raise NotImplementedError naming the argument when asked for them.
 """
 import ctypes
 
@@ -17,7 +22,7 @@ import torch
 
 from .. import _lib
 
-__all__ = ["MeshRasterizerContext", "render_mesh"]
+__all__ = ["MeshRasterizerContext", "DiffMeshRasterizerContext", "edge_topology", "render_mesh"]
 
 
 def _p(t):
@@ -77,8 +82,11 @@ def _no_position_gradient(t, what):
         raise NotImplementedError("%s requires a gradient, and no gradient reaches vertex positions: pass %s.detach()" % (what, what))
 
 
-def _rasterize(pos, tri, resolution, cull_backfaces=False, validate=True):
-    _no_position_gradient(pos, "pos")
+def _rasterize(pos, tri, resolution, cull_backfaces=False, validate=True, differentiable=False):
+    """rast of the forward kernels.  differentiable: a pos that requires a gradient goes through _RasterizeGrad (the same launch)."""
+    given = pos
+    if not differentiable:
+        _no_position_gradient(pos, "pos")
     pos = _gpu_float(pos, "pos", (3,), 4)
     if pos.shape[0] < 1:
         raise ValueError("pos must be [B, V, 4] with B >= 1")
@@ -92,6 +100,13 @@ def _rasterize(pos, tri, resolution, cull_backfaces=False, validate=True):
         return torch.zeros((B, H, W, 4), dtype=torch.float32, device=pos.device)
     if B * H * W > 2 ** 31 - 1 or F > 2 ** 24 - 1 or B * F > 2 ** 31 - 1:
         raise ValueError("rasterize: %d views of %d x %d with %d triangles are outside the limits of gip_mesh_rasterize" % (B, H, W, F))
+    if differentiable and given.requires_grad and torch.is_grad_enabled():
+        return _RasterizeGrad.apply(given, tri, H, W, bool(cull_backfaces))
+    return _rasterize_launch(pos, tri, H, W, cull_backfaces)
+
+
+def _rasterize_launch(pos, tri, H, W, cull_backfaces):
+    B, V, F = int(pos.shape[0]), int(pos.shape[1]), int(tri.shape[0])
     need = _workspace_bytes(B, H, W, F)
     ws = torch.empty(need, dtype=torch.uint8, device=pos.device)
     rast = torch.empty((B, H, W, 4), dtype=torch.float32, device=pos.device)
@@ -99,6 +114,29 @@ def _rasterize(pos, tri, resolution, cull_backfaces=False, validate=True):
         _check(_lib.model_lib().gip_mesh_rasterize(_p(pos), _p(tri), B, V, F, H, W, int(bool(cull_backfaces)), _p(ws), need, _p(rast),
                                                    _stream(pos.device)), "gip_mesh_rasterize")
     return rast
+
+
+class _RasterizeGrad(torch.autograd.Function):
+    """The same launch, so the same rast bit for bit, with gip_mesh_rasterize_backward as its backward."""
+
+    @staticmethod
+    def forward(ctx, pos, tri, H, W, cull_backfaces):
+        pos = pos.detach().contiguous()
+        rast = _rasterize_launch(pos, tri, H, W, cull_backfaces)
+        ctx.save_for_backward(pos, rast, tri)
+        return rast
+
+    @staticmethod
+    def backward(ctx, g):
+        pos, rast, tri = ctx.saved_tensors
+        B, H, W, _ = rast.shape
+        V, F = int(pos.shape[1]), int(tri.shape[0])
+        g = g.contiguous().float()
+        g_pos = torch.zeros_like(pos)
+        with torch.cuda.device(pos.device):
+            _check(_lib.model_lib().gip_mesh_rasterize_backward(_p(pos), _p(tri), B, V, F, H, W, _p(rast), _p(g), _p(g_pos),
+                                                                _stream(pos.device)), "gip_mesh_rasterize_backward")
+        return g_pos, None, None, None, None
 
 
 def _rast_tensor(rast):
@@ -114,21 +152,28 @@ class _Interpolate(torch.autograd.Function):
         with torch.cuda.device(rast.device):
             _check(_lib.model_lib().gip_mesh_interpolate(_p(attr), nb, N, C, _p(idx), F, _p(rast), B, H, W, _p(out), _stream(rast.device)),
                    "gip_mesh_interpolate")
-        ctx.save_for_backward(rast, idx)
+        ctx.save_for_backward(rast, idx, attr)
         ctx.shape, ctx.F = (nb, N, C), F
         return out
 
     @staticmethod
     def backward(ctx, g):
-        rast, idx = ctx.saved_tensors
+        rast, idx, attr = ctx.saved_tensors
         nb, N, C = ctx.shape
         B, H, W, _ = rast.shape
         g = g.contiguous().float()
-        g_attr = torch.empty((nb, N, C), dtype=torch.float32, device=rast.device)
+        g_attr = g_rast = None
         with torch.cuda.device(rast.device):
-            _check(_lib.model_lib().gip_mesh_interpolate_backward(_p(g), nb, N, C, _p(idx), ctx.F, _p(rast), B, H, W, _p(g_attr),
-                                                                  _stream(rast.device)), "gip_mesh_interpolate_backward")
-        return g_attr, None, None, None
+            if ctx.needs_input_grad[0]:
+                g_attr = torch.empty((nb, N, C), dtype=torch.float32, device=rast.device)
+                _check(_lib.model_lib().gip_mesh_interpolate_backward(_p(g), nb, N, C, _p(idx), ctx.F, _p(rast), B, H, W, _p(g_attr),
+                                                                      _stream(rast.device)), "gip_mesh_interpolate_backward")
+            if ctx.needs_input_grad[1]:      # only a rast of DiffMeshRasterizerContext carries a gradient
+                g_rast = torch.empty_like(rast)
+                _check(_lib.model_lib().gip_mesh_interpolate_backward_rast(_p(g), _p(attr), nb, N, C, _p(idx), ctx.F, _p(rast), B, H, W,
+                                                                           _p(g_rast), _stream(rast.device)),
+                       "gip_mesh_interpolate_backward_rast")
+        return g_attr, g_rast, None, None
 
 
 class _Texture(torch.autograd.Function):
@@ -181,16 +226,134 @@ class _Shade(torch.autograd.Function):
         g = g.contiguous().float()
         g_tex = torch.empty_like(tex) if ctx.needs_input_grad[0] else None
         g_uv = torch.empty_like(uv) if ctx.needs_input_grad[1] else None
+        g_rast = torch.empty_like(rast) if ctx.needs_input_grad[2] else None      # render_mesh(position_gradients=True) only
         if F == 0:      # nothing was drawn: no launch
-            return (None if g_tex is None else torch.zeros_like(tex)), (None if g_uv is None else torch.zeros_like(uv)), None, None, None
+            return ((None if g_tex is None else torch.zeros_like(tex)), (None if g_uv is None else torch.zeros_like(uv)),
+                    (None if g_rast is None else torch.zeros_like(rast)), None, None)
         with torch.cuda.device(rast.device):
-            _check(_lib.model_lib().gip_mesh_shade_backward(_p(rast), _p(uv), F, ctx.flip_v, _p(tex), Th, Tw, _p(g), B, H, W, _p(g_tex),
-                                                            _p(g_uv), _stream(rast.device)), "gip_mesh_shade_backward")
-        return g_tex, g_uv, None, None, None
+            if g_tex is not None or g_uv is not None:
+                _check(_lib.model_lib().gip_mesh_shade_backward(_p(rast), _p(uv), F, ctx.flip_v, _p(tex), Th, Tw, _p(g), B, H, W, _p(g_tex),
+                                                                _p(g_uv), _stream(rast.device)), "gip_mesh_shade_backward")
+            if g_rast is not None:
+                _check(_lib.model_lib().gip_mesh_shade_backward_rast(_p(rast), _p(uv), F, ctx.flip_v, _p(tex), Th, Tw, _p(g), B, H, W,
+                                                                     _p(g_rast), _stream(rast.device)), "gip_mesh_shade_backward_rast")
+        return g_tex, g_uv, g_rast, None, None
+
+
+def edge_topology(tri, num_vertices):
+    """topo [F, 3] int32 on tri's device (GPU or CPU), the table the antialias pass reads: for edge k of face f, the edge opposite
+    corner k (from tri[f, k + 1] to tri[f, k + 2], indices mod 3), the vertex of the one other face at that edge that does not lie on
+    it; -1 where no other face has the edge (a boundary); -2 where more than two faces share it (never a silhouette).
+
+    Built from torch operations of static shape, so nothing is read back to the host: the 3 F undirected edges as 64-bit keys
+    min * num_vertices + max, sorted, every key compared with its two neighbours on each side in the sorted order.  A face with a
+    repeated index is not drawn (its area is zero) but is counted like any other: its two coinciding edges count as two faces at that
+    edge (alone they name each other's corner, with a real neighbour the edge reads -2 for all of them), and its edge from a vertex
+    to itself is a key of its own."""
+    if not (isinstance(tri, torch.Tensor) and tri.dtype == torch.int32 and tri.dim() == 2 and tri.shape[1] == 3):
+        raise ValueError("tri must be an [F, 3] int32 tensor")
+    V = int(num_vertices)
+    if V < 1 or V > 2 ** 31 - 1:
+        raise ValueError("num_vertices must lie in 1 .. 2^31 - 1")
+    F = int(tri.shape[0])
+    if F == 0:
+        return torch.zeros((0, 3), dtype=torch.int32, device=tri.device)
+    t = tri.detach().long()
+    a, b = t[:, [1, 2, 0]].reshape(-1), t[:, [2, 0, 1]].reshape(-1)              # edge k of face f at 3 f + k
+    key = torch.minimum(a, b) * V + torch.maximum(a, b)
+    skey, order = torch.sort(key)
+    pad = skey.new_full((2,), -1)
+    k = torch.cat((pad, skey, pad))                                                 # k[i + 2] = skey[i]
+    n = skey.shape[0]
+    prev1, prev2 = k[1:n + 1] == skey, k[0:n] == skey
+    next1, next2 = k[3:n + 3] == skey, k[4:n + 4] == skey
+    alone = ~prev1 & ~next1
+    with_next = next1 & ~prev1 & ~next2                                             # a run of exactly two, this one first
+    with_prev = prev1 & ~next1 & ~prev2
+    opposite = t.reshape(-1)[order]                                                 # corner k of face f: the vertex not on the edge
+    o = torch.cat((opposite[:1], opposite, opposite[-1:]))
+    value = torch.where(with_next, o[2:n + 2], torch.where(with_prev, o[0:n], torch.full_like(opposite, -2)))
+    value = torch.where(alone, torch.full_like(value, -1), value)
+    out = torch.empty_like(value)
+    out[order] = value
+    return out.reshape(F, 3).to(torch.int32)
+
+
+class _Antialias(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, color, pos, rast, tri, topo):
+        B, H, W, C = color.shape
+        V, F = int(pos.shape[1]), int(tri.shape[0])
+        color, pos = color.detach().contiguous(), pos.detach().contiguous()
+        out = torch.empty_like(color)
+        with torch.cuda.device(color.device):
+            _check(_lib.model_lib().gip_mesh_antialias(_p(color), C, _p(rast), _p(pos), _p(tri), _p(topo), B, V, F, H, W, _p(out),
+                                                       _stream(color.device)), "gip_mesh_antialias")
+        ctx.save_for_backward(color, pos, rast, tri, topo)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        color, pos, rast, tri, topo = ctx.saved_tensors
+        B, H, W, C = color.shape
+        V, F = int(pos.shape[1]), int(tri.shape[0])
+        g = g.contiguous().float()
+        g_color = torch.empty_like(color) if ctx.needs_input_grad[0] else None
+        g_pos = torch.zeros_like(pos) if ctx.needs_input_grad[1] else None
+        with torch.cuda.device(color.device):
+            _check(_lib.model_lib().gip_mesh_antialias_backward(_p(color), C, _p(rast), _p(pos), _p(tri), _p(topo), B, V, F, H, W, _p(g),
+                                                                _p(g_color), _p(g_pos), _stream(color.device)),
+                   "gip_mesh_antialias_backward")
+        return g_color, g_pos, None, None, None
+
+
+class _TopologyCache:
+    """edge_topology of the last tri: the tensor object itself is kept and its version counter compared, so neither a tensor edited in
+    place nor a new one at a freed one's address is served the old table."""
+
+    def __init__(self):
+        self.tri = self.topo = None
+        self.key = None
+
+    def get(self, tri, V):
+        key = (tri._version, tuple(tri.shape), V)
+        if self.tri is not tri or self.key != key:
+            self.topo, self.tri, self.key = edge_topology(tri, V), tri, key
+        return self.topo
+
+
+def _antialias(color, rast, pos, tri, topology, cache):
+    for t, what in ((color, "color"), (rast, "rast"), (pos, "pos")):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32):
+            raise ValueError("%s must be a float32 GPU tensor" % what)
+    if pos.dim() == 2:
+        pos = pos[None]
+    if pos.dim() != 3 or pos.shape[-1] != 4:
+        raise ValueError("pos must be [B, V, 4] (or [V, 4])")
+    if rast.dim() != 4 or rast.shape[-1] != 4 or rast.shape[0] != pos.shape[0]:
+        raise ValueError("rast must be [B, H, W, 4] with pos's B")
+    if color.dim() != 4 or tuple(color.shape[:3]) != tuple(rast.shape[:3]) or color.shape[3] < 1:
+        raise ValueError("color must be [B, H, W, C] with rast's B, H, W and at least one channel")
+    if color.numel() > 2 ** 31 - 1:
+        raise ValueError("color: at most 2^31 - 1 values")
+    V = int(pos.shape[1])
+    if not (isinstance(tri, torch.Tensor) and tri.is_cuda and tri.dtype == torch.int32 and tri.dim() == 2 and tri.shape[1] == 3):
+        raise ValueError("tri must be an [F, 3] int32 GPU tensor")
+    if tri.shape[0] == 0 or V == 0:      # nothing is drawn: nothing to blend, no launch
+        return color
+    if topology is None:
+        topology = cache.get(tri, V)
+    elif not (isinstance(topology, torch.Tensor) and topology.is_cuda and topology.dtype == torch.int32 and
+              tuple(topology.shape) == tuple(tri.shape)):
+        raise ValueError("topology must be what edge_topology(tri, V) returned: an [F, 3] int32 GPU tensor")
+    return _Antialias.apply(color, pos, rast.detach().contiguous(), tri.detach().contiguous(), topology.contiguous())
 
 
 class MeshRasterizerContext:
-    """The interface of the reference's NVDiffRasterizerContext.  context_type is accepted and ignored (there is one rasterizer)."""
+    """The interface of the reference's NVDiffRasterizerContext.  context_type is accepted and ignored (there is one rasterizer).
+    This default context sends no gradient to positions and has no antialias pass; DiffMeshRasterizerContext has both."""
+
+    _rast_input = staticmethod(_rast_tensor)      # rast is detached here: this context sends no gradient through it
 
     def __init__(self, context_type=None, device="cuda"):
         self.device = torch.device(device)
@@ -226,7 +389,7 @@ class MeshRasterizerContext:
             raise NotImplementedError("interpolate: diff_attrs (attribute pixel differentials) is not supported")
         if not (isinstance(attr, torch.Tensor) and attr.is_cuda and attr.dtype == torch.float32 and attr.dim() in (2, 3)):
             raise ValueError("attr must be a float32 GPU tensor, [N, C] or [1 or B, N, C]")
-        rast = _rast_tensor(rast)
+        rast = self._rast_input(rast)
         a = attr[None] if attr.dim() == 2 else attr
         if a.shape[0] not in (1, rast.shape[0]) or a.shape[2] < 1:
             raise ValueError("attr must have a batch of 1 or B and at least one channel")
@@ -254,7 +417,45 @@ class MeshRasterizerContext:
         return _Texture.apply(t.contiguous(), uv.contiguous())
 
 
-def render_mesh(camera, vertices, faces, uv, texture, bg_color=None, cull_backfaces=False, validate=True):
+def _rast_with_gradient(rast):
+    _rast_tensor(rast)
+    return rast.contiguous()
+
+
+class DiffMeshRasterizerContext(MeshRasterizerContext):
+    """MeshRasterizerContext with what a loss on the geometry needs (csrc/mesh_grad.hip): the class to alias to the reference's
+    NVDiffRasterizerContext wherever antialias or a gradient to vertex positions is used.  The forward results are those of the
+    default context bit for bit.  Mipmaps (rast_db, diff_attrs, uv_da, mip) stay unsupported."""
+
+    _rast_input = staticmethod(_rast_with_gradient)
+
+    def __init__(self, context_type=None, device="cuda"):
+        super().__init__(context_type, device)
+        self._topology = _TopologyCache()
+
+    def rasterize(self, pos, tri, resolution, cull_backfaces=False, validate=True):
+        """As MeshRasterizerContext.rasterize, and differentiable in pos: dL/dpos from dL/d(u, v, depth) of rast with float atomic adds
+        (gip_mesh_rasterize_backward; the snapping to the sub-pixel grid is straight-through).  rast_db stays None."""
+        return _rasterize(pos, tri, resolution, cull_backfaces, validate, differentiable=True), None
+
+    def rasterize_one(self, pos, tri, resolution, cull_backfaces=False, validate=True):
+        if not (isinstance(pos, torch.Tensor) and pos.dim() == 2):
+            raise ValueError("rasterize_one needs pos as [V, 4]")
+        return _rasterize(pos[None, ...], tri, resolution, cull_backfaces, validate, differentiable=True)[0], None
+
+    def antialias(self, color, rast, pos, tri, topology=None):
+        """[B, H, W, C]: color with every pixel pair that a silhouette edge of the nearer pixel's triangle crosses blended by where
+        the edge crosses (nvdiffrast's rule; csrc/mesh_grad.hip states it).  Differentiable in color and in pos [B, V, 4]; rast and tri
+        are those of rasterize.  topology: what edge_topology(tri, V) returned; None builds it and keeps it on the context for this
+        tri (the same tensor object, not edited in place since)."""
+        return _antialias(color, rast, pos, tri, topology, self._topology)
+
+
+_render_topology = _TopologyCache()
+
+
+def render_mesh(camera, vertices, faces, uv, texture, bg_color=None, cull_backfaces=False, validate=True, position_gradients=False,
+                antialias=False):
     """{"image": [3, H, W], "alpha": [1, H, W], "depth": [1, H, W], "rast": [H, W, 4]} of the textured mesh that
     GaussianModel.extract_textured_mesh returns (vertices [V, 3] float32 world coordinates, faces [F, 3] int32, uv [F, 3, 2], texture
     [T, T, 3], all on the GPU), seen from `camera` (its full_proj_transform and image size): the same pixel grid as the Gaussian
@@ -264,14 +465,26 @@ def render_mesh(camera, vertices, faces, uv, texture, bg_color=None, cull_backfa
     skips the host read that checks the faces' indices (GaussianModel.render_textured_mesh does: its faces come from the extraction).  alpha is coverage (0 / 1),
     depth is z/w of the projection (0 where nothing is drawn), bg_color [3] defaults to black.  image, alpha and depth are views of
     the kernels' interleaved outputs (`.contiguous()` copies them).  Differentiable in texture (and in uv): float atomic adds, so the
-    backward is not bit-reproducible; the forward is.  No gradient reaches the vertices, nothing is antialiased, and a triangle with a
-    vertex behind the camera is dropped whole (no clipping).  Two calls into the library: rasterize and shade."""
+    backward is not bit-reproducible; the forward is.  A triangle with a vertex behind the camera is dropped whole (no clipping).  Two
+    calls into the library: rasterize and shade.
+
+    By default no gradient reaches the vertices and nothing is antialiased.  position_gradients=True lets one reach `vertices`:
+    through the colour (the fused shade's gradient to rast, then the rasterizer's to positions) and through depth (rast[..., 2]).
+    antialias=True passes (r, g, b, alpha) through one antialias call (depth and rast are not antialiased): alpha then takes values
+    between 0 and 1 at silhouettes, and with position_gradients a loss on it moves the vertices.  The edge table is built once per
+    `faces` tensor."""
     many = isinstance(camera, (list, tuple))
     cams = list(camera) if many else [camera]
     if not cams:
         raise ValueError("render_mesh needs at least one camera")
-    _no_position_gradient(vertices, "vertices")
-    vertices = _gpu_float(vertices, "vertices", (2,), 3)
+    if position_gradients:
+        given = vertices
+        vertices = _gpu_float(vertices, "vertices", (2,), 3)
+        if given.requires_grad and torch.is_grad_enabled():
+            vertices = given.contiguous()
+    else:
+        _no_position_gradient(vertices, "vertices")
+        vertices = _gpu_float(vertices, "vertices", (2,), 3)
     dev = vertices.device
     if not (isinstance(uv, torch.Tensor) and uv.is_cuda and uv.dtype == torch.float32 and uv.dim() == 3 and tuple(uv.shape[1:]) == (3, 2)):
         raise ValueError("uv must be an [F, 3, 2] float32 GPU tensor")
@@ -292,8 +505,10 @@ def render_mesh(camera, vertices, faces, uv, texture, bg_color=None, cull_backfa
     mvp = torch.stack([c.full_proj_transform.to(dev).float() for c in cams])               # [B, 4, 4], row-vector convention
     verts_h = torch.cat((vertices, torch.ones_like(vertices[:, :1])), 1)
     pos = torch.matmul(verts_h[None], mvp).contiguous()                                     # [B, V, 4]
-    rast = _rasterize(pos, faces, (H, W), cull_backfaces, validate)
+    rast = _rasterize(pos, faces, (H, W), cull_backfaces, validate, differentiable=bool(position_gradients))
     shaded = _Shade.apply(texture.contiguous(), uv.contiguous(), rast, bg, 1)
+    if antialias:
+        shaded = _antialias(shaded, rast, pos, faces, None, _render_topology)
     out = {"image": shaded[..., :3].permute(0, 3, 1, 2), "alpha": shaded[..., 3:].permute(0, 3, 1, 2),
            "depth": rast[..., 2:3].permute(0, 3, 1, 2), "rast": rast}
     return out if many else {k: v[0] for k, v in out.items()}

@@ -203,7 +203,7 @@ int gip_texture_bake(const float* xyz, const float* opacity, const float* scalin
  *       OBJ convention and every corner's v is replaced by 1 - v before it is interpolated (g_uv is then the gradient to the OBJ uv).
  *   gip_mesh_shade_backward  g_tex [Th, Tw, 3] and g_uv [F, 3, 2] (either may be NULL) from g_shaded [B, H, W, 4] (its alpha is
  *       ignored: coverage has no gradient); zero-filled here, then float atomic adds, so not bit-reproducible.
- * No gradient reaches pos.  Status 1: a NULL required pointer, B, H, W < 1, H or W > 16384, B H W > 2^31 - 1, F > 2^24 - 1 (the index
+ * None of these sends a gradient to pos (the next block does).  Status 1: a NULL required pointer, B, H, W < 1, H or W > 16384, B H W > 2^31 - 1, F > 2^24 - 1 (the index
  * is stored in a float), B F > 2^31 - 1, a batch that is neither 1 nor B, a texture above 16384 a side, a short workspace.
  * Status 3: a launch error. */
 int gip_mesh_raster_workspace_size(int32_t B, int32_t H, int32_t W, int64_t F, size_t* bytes);
@@ -221,6 +221,32 @@ int gip_mesh_shade(const float* rast, const float* uv, int64_t F, int32_t flip_v
                    int32_t H, int32_t W, float* shaded, void* stream);
 int gip_mesh_shade_backward(const float* rast, const float* uv, int64_t F, int32_t flip_v, const float* tex, int32_t Th, int32_t Tw, const float* g_shaded,
                             int32_t B, int32_t H, int32_t W, float* g_tex, float* g_uv, void* stream);
+/* Gradients to vertex positions and the antialias pass (csrc/mesh_grad.hip, whose header states the definitions; the opt-in
+ * DiffMeshRasterizerContext and render_mesh(position_gradients=, antialias=) of gaussianip_amd/utils/rasterize.py).
+ *   gip_mesh_rasterize_backward  nvdiffrast's rasterize backward (dr.rasterize differentiated in pos, without rast_db): dL/dpos of the
+ *       three corners of every covered pixel from g_rast [B, H, W, 4] (channels 0..2 = dL/d(u, v, depth); channel 3 is ignored), added
+ *       with float atomic adds into g_pos [B, V, 4], WHICH THE CALLER HAS ZEROED (several calls may accumulate into one buffer).
+ *   gip_mesh_interpolate_backward_rast  the rast half of dr.interpolate's backward: g_rast [B, H, W, 4] = (g_u, g_v, 0, 0) from g_out
+ *       [B, H, W, C] and attr; every pixel is written (zeros at an empty one), no atomics.  idx may be NULL as in gip_mesh_interpolate.
+ *   gip_mesh_shade_backward_rast  the same for the fused shade (dr.interpolate of the uv followed by dr.texture, differentiated in
+ *       rast): the arguments of gip_mesh_shade_backward with g_rast [B, H, W, 4] in place of g_tex / g_uv.
+ *   gip_mesh_antialias  dr.antialias: out [B, H, W, C] from color [B, H, W, C], rast, pos and tri, with topo [F, 3] the table of
+ *       edge_topology (per edge: the opposite vertex of the neighbouring face, -1 without a neighbour, -2 with more than one) in place of
+ *       nvdiffrast's topology hash.  A gather: bit-reproducible.
+ *   gip_mesh_antialias_backward  dr.antialias's backward: g_color [B, H, W, C] (every pixel written, a gather; or NULL) and g_pos
+ *       [B, V, 4] (float atomic adds into what THE CALLER HAS ZEROED; or NULL) from g_out [B, H, W, C].
+ * Status as above; additionally 1 for C < 1 or B H W C > 2^31 - 1 in the antialias pair. */
+int gip_mesh_rasterize_backward(const float* pos, const int32_t* tri, int32_t B, int64_t V, int64_t F, int32_t H, int32_t W, const float* rast,
+                                const float* g_rast, float* g_pos, void* stream);
+int gip_mesh_interpolate_backward_rast(const float* g_out, const float* attr, int32_t attr_batch, int64_t N, int32_t C, const int32_t* idx,
+                                       int64_t F, const float* rast, int32_t B, int32_t H, int32_t W, float* g_rast, void* stream);
+int gip_mesh_shade_backward_rast(const float* rast, const float* uv, int64_t F, int32_t flip_v, const float* tex, int32_t Th, int32_t Tw,
+                                 const float* g_shaded, int32_t B, int32_t H, int32_t W, float* g_rast, void* stream);
+int gip_mesh_antialias(const float* color, int32_t C, const float* rast, const float* pos, const int32_t* tri, const int32_t* topo, int32_t B,
+                       int64_t V, int64_t F, int32_t H, int32_t W, float* out, void* stream);
+int gip_mesh_antialias_backward(const float* color, int32_t C, const float* rast, const float* pos, const int32_t* tri, const int32_t* topo,
+                                int32_t B, int64_t V, int64_t F, int32_t H, int32_t W, const float* g_out, float* g_color, float* g_pos,
+                                void* stream);
 #ifdef __cplusplus
 }
 #endif
