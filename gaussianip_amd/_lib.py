@@ -239,6 +239,17 @@ def model_lib():
         lib.gip_mesh_antialias.argtypes = [_vp, _i32, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i32, _i32, _vp, _vp]
         lib.gip_mesh_antialias_backward.restype = ctypes.c_int
         lib.gip_mesh_antialias_backward.argtypes = [_vp, _i32, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp]
+        _f32 = ctypes.c_float
+        lib.gip_mesh_components_rounds.restype = ctypes.c_int
+        lib.gip_mesh_components_rounds.argtypes = [_vp, _i64, _i64, _vp, _vp, _i32, _vp]
+        lib.gip_mesh_component_stats.restype = ctypes.c_int
+        lib.gip_mesh_component_stats.argtypes = [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp]
+        lib.gip_mesh_cluster_keys.restype = ctypes.c_int
+        lib.gip_mesh_cluster_keys.argtypes = [_vp, _i64, _f32, _f32, _f32, _f32, _i32, _vp, _vp]
+        lib.gip_mesh_cluster_count.restype = ctypes.c_int
+        lib.gip_mesh_cluster_count.argtypes = [_vp, _i64, _vp, _i64, _f32, _f32, _f32, _f32, _i32, _vp, _vp]
+        lib.gip_mesh_cluster_place.restype = ctypes.c_int
+        lib.gip_mesh_cluster_place.argtypes = [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _f32, _f32, _f32, _f32, _i32, _i32, _vp, _vp]
         _model = _Counted(lib)
     return _model
 
@@ -388,3 +399,5 @@ MESH_SYMBOLS = ["gip_mesh_raster_workspace_size", "gip_mesh_rasterize", "gip_mes
                 "gip_mesh_texture", "gip_mesh_texture_backward", "gip_mesh_shade", "gip_mesh_shade_backward"]
 MESH_GRAD_SYMBOLS = ["gip_mesh_rasterize_backward", "gip_mesh_interpolate_backward_rast", "gip_mesh_shade_backward_rast", "gip_mesh_antialias",
                      "gip_mesh_antialias_backward"]
+MESH_CLEAN_SYMBOLS = ["gip_mesh_components_rounds", "gip_mesh_component_stats", "gip_mesh_cluster_keys", "gip_mesh_cluster_count",
+                      "gip_mesh_cluster_place"]

@@ -211,20 +211,42 @@ class GaussianModel:
         return occ
 
     @torch.no_grad()
-    def extract_mesh(self, path=None, density_thresh=1.0, resolution=128, num_blocks=16, relax_ratio=1.5):
+    def extract_mesh(self, path=None, density_thresh=1.0, resolution=128, num_blocks=16, relax_ratio=1.5, *, clean=False, min_faces=8,
+                     min_diameter=0.05, decimate_target=0):
         """(vertices [V, 3] float32 in world coordinates, faces [F, 3] int32) of the surface density == density_thresh, written as a
-        Wavefront OBJ when `path` is given.  gs_renderer.py:333-344 without the third-party cleaning and decimation; the surface is
-        extracted by marching tetrahedra on the GPU (utils/mesh.py) instead of mcubes, so it is closed by construction."""
+        Wavefront OBJ when `path` is given.  gs_renderer.py:333-350; the surface is extracted by marching tetrahedra on the GPU
+        (utils/mesh.py) instead of mcubes, so it is closed by construction.  clean=True drops the floaters (utils.mesh.clean_mesh with
+        min_faces and min_diameter, the reference's clean_mesh without its remeshing); decimate_target > 0 then reduces the mesh to at
+        most that many faces (utils.mesh.decimate_mesh: vertex clustering, which does not preserve manifoldness in parts thinner than
+        a cell; the reference's decimate_target is 1e5).  With the defaults neither runs and the result is the plain surface."""
         from ..utils import mesh
         occ = self.extract_fields(resolution, num_blocks, relax_ratio)
         vertices, faces = mesh.extract_surface(occ, density_thresh)
         if vertices.shape[0]:
             vertices = vertices / (resolution - 1.0) * 2 - 1
             vertices = vertices / self.scale + self.center       # back to the original space, :344
+        if clean or decimate_target:
+            vertices, faces, _, _ = self._clean_decimate(vertices, faces, clean, min_faces, min_diameter, decimate_target)
         if path is not None:
             os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
             mesh.write_obj(path, vertices, faces)
         return vertices, faces
+
+    @staticmethod
+    def _clean_decimate(vertices, faces, clean, min_faces, min_diameter, decimate_target):
+        """The reference's order (gs_renderer.py:346-350): clean, then decimate.  (vertices, faces, vertex_map or None, moved):
+        vertex_map [V_in] int32 of the cleaning alone (None without it); moved: the decimation replaced the vertices."""
+        from ..utils import mesh
+        if not decimate_target >= 0:
+            raise ValueError("decimate_target must not be negative (0: no decimation)")
+        vertex_map, moved = None, False
+        if clean and faces.shape[0]:
+            vertices, faces, info = mesh.clean_mesh(vertices, faces, min_faces, min_diameter, validate=False)      # the extraction's own faces
+            vertex_map = info["vertex_map"]
+        if decimate_target and faces.shape[0] > int(decimate_target):
+            vertices, faces, _, grid = mesh.decimate_mesh(vertices, faces, int(decimate_target))
+            moved = grid != 0
+        return vertices, faces, vertex_map, moved
 
     def _sample(self, what, u, block, colors, resolution, num_blocks, relax_ratio):
         """density [V], gradient [V, 3] (normalised space) and colour sum [V, 3] at the normalised points u [V, 3], each evaluated in
@@ -306,12 +328,16 @@ class GaussianModel:
         return {"density": out["density"], "gradient": out["gradient"] * scale, "color": self._blend(out["color_sum"], out["density"])}
 
     @torch.no_grad()
-    def extract_mesh_with_attributes(self, path=None, density_thresh=1.0, resolution=128, num_blocks=16, relax_ratio=1.5, colors=None):
+    def extract_mesh_with_attributes(self, path=None, density_thresh=1.0, resolution=128, num_blocks=16, relax_ratio=1.5, colors=None, *,
+                                     clean=False, min_faces=8, min_diameter=0.05, decimate_target=0):
         """(vertices [V, 3] float32, faces [F, 3] int32, normals [V, 3] float32, colors [V, 3] float32 in [0, 1]): extract_mesh's
         vertices and faces, bit for bit, with the Gaussians sampled at the vertices (sample_fields' sums; a vertex is evaluated in the
         block of the grid point that owns its edge).  normals = -gradient / |gradient|: analytic, toward decreasing density like the
         faces' winding, zero where the gradient is zero.  colors: the blend of `colors` (default: the base colour), which must lie
-        in [0, 1] for the result to.  `path` ending in .ply writes a binary PLY, any other path a Wavefront OBJ."""
+        in [0, 1] for the result to.  `path` ending in .ply writes a binary PLY, any other path a Wavefront OBJ.
+        clean, min_faces, min_diameter, decimate_target: extract_mesh's.  After cleaning alone the normals and colours are the kept
+        vertices' rows of the uncleaned result, bit for bit; a decimation moves the vertices, so normals and colours are then
+        sample_fields' at the new vertices (evaluated in the block that holds each).  The written file follows the final mesh."""
         from ..utils import mesh
         resolution, num_blocks = self._field_geometry("extract_mesh_with_attributes", resolution, num_blocks)
         occ = self.extract_fields(resolution, num_blocks, relax_ratio)
@@ -330,6 +356,17 @@ class GaussianModel:
             vcolors = self._blend(out["color_sum"], out["density"])
         else:
             normals, vcolors = torch.zeros_like(v), torch.zeros_like(v)
+        if clean or decimate_target:
+            vertices, faces, vertex_map, moved = self._clean_decimate(vertices, faces, clean, min_faces, min_diameter, decimate_target)
+            if moved:
+                out = self.sample_fields(vertices, colors, resolution, num_blocks, relax_ratio)
+                g = out["gradient"].double()
+                n = g.norm(dim=1, keepdim=True)
+                normals = torch.where(n > 0, -g / n.clamp_min(1e-300), torch.zeros_like(g)).float()
+                vcolors = out["color"]
+            elif vertex_map is not None:
+                rows = torch.nonzero(vertex_map >= 0).reshape(-1)      # ascending: the kept vertices keep their order
+                normals, vcolors = normals[rows], vcolors[rows]
         if path is not None:
             os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
             if str(path).lower().endswith(".ply"):
@@ -452,13 +489,17 @@ class GaussianModel:
 
     @torch.no_grad()
     def extract_textured_mesh(self, path=None, density_thresh=1.0, resolution=128, num_blocks=16, relax_ratio=1.5, texture_size=None,
-                              colors=None):
+                              colors=None, *, clean=False, min_faces=8, min_diameter=0.05, decimate_target=0):
         """(vertices [V, 3], faces [F, 3] int32, normals [V, 3], uv [F, 3, 2], texture [T, T, 3]): the mesh and normals of
         extract_mesh_with_attributes, bit for bit, with bake_texture's atlas and texture in place of vertex colours — the reference's
         export_obj_with_mtl (threestudio/models/exporters/mesh_exporter.py:53-137) without its third-party unwrapping, rasterising
-        and inpainting.  With path = dir/name.obj it writes name.obj, name.mtl and name_kd.png (utils.mesh.write_obj_textured)."""
+        and inpainting.  With path = dir/name.obj it writes name.obj, name.mtl and name_kd.png (utils.mesh.write_obj_textured).
+        clean, min_faces, min_diameter, decimate_target: extract_mesh_with_attributes'; the texture is baked on the cleaned and
+        decimated mesh (fewer faces: larger atlas cells at the same texture size), and the files follow it."""
         from ..utils import mesh
-        vertices, faces, normals, _ = self.extract_mesh_with_attributes(None, density_thresh, resolution, num_blocks, relax_ratio, colors)
+        vertices, faces, normals, _ = self.extract_mesh_with_attributes(None, density_thresh, resolution, num_blocks, relax_ratio, colors,
+                                                                        clean=clean, min_faces=min_faces, min_diameter=min_diameter,
+                                                                        decimate_target=decimate_target)
         baked = self.bake_texture(vertices, faces, texture_size, colors, resolution, num_blocks, relax_ratio)
         if path is not None:
             os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
@@ -466,11 +507,15 @@ class GaussianModel:
         return vertices, faces, normals, baked["uv"], baked["texture"]
 
     @torch.no_grad()
-    def render_textured_mesh(self, camera, bg_color=None, position_gradients=False, antialias=False, **extract_kwargs):
+    def render_textured_mesh(self, camera, bg_color=None, position_gradients=False, antialias=False, *, clean=False, min_faces=8,
+                             min_diameter=0.05, decimate_target=0, **extract_kwargs):
         """utils.rasterize.render_mesh of extract_textured_mesh(**extract_kwargs) from `camera` (or a list of cameras): the exported
         mesh on the pixel grid of the Gaussian render of the same camera.  The dict of render_mesh plus "mesh": the tuple that
-        extract_textured_mesh returned.  position_gradients and antialias are render_mesh's keywords."""
+        extract_textured_mesh returned.  position_gradients and antialias are render_mesh's keywords; clean, min_faces, min_diameter and
+        decimate_target are extract_textured_mesh's."""
         from ..utils.rasterize import render_mesh
+        if clean or decimate_target:
+            extract_kwargs.update(clean=clean, min_faces=min_faces, min_diameter=min_diameter, decimate_target=decimate_target)
         mesh = self.extract_textured_mesh(**extract_kwargs)
         vertices, faces, _, uv, texture = mesh
         out = render_mesh(camera, vertices, faces, uv, texture, bg_color=bg_color, validate=False,      # the extraction's own faces

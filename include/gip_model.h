@@ -247,6 +247,34 @@ int gip_mesh_antialias(const float* color, int32_t C, const float* rast, const f
 int gip_mesh_antialias_backward(const float* color, int32_t C, const float* rast, const float* pos, const int32_t* tri, const int32_t* topo,
                                 int32_t B, int64_t V, int64_t F, int32_t H, int32_t W, const float* g_out, float* g_color, float* g_pos,
                                 void* stream);
+/* Cleaning and decimating the extracted mesh (csrc/mesh_clean.hip, whose header states the definitions; gaussianip_amd/utils/mesh.py
+ * connected_components, clean_mesh, cluster_decimate, decimate_mesh).  In place of the reference's third-party clean_mesh and
+ * decimate_mesh (gs_renderer.py:346-350).  vertices [V, 3] float32, faces [F, 3] int32, everything on the device; a face with an index
+ * outside [0, V) is skipped by every kernel.  No kernel waits on another workgroup; the loop over rounds is the caller's.
+ *   gip_mesh_components_rounds  `rounds` (1 .. 64) rounds of hook + compress on labels [V] int32, WHICH THE CALLER HAS SET TO 0 .. V - 1
+ *       before the first call; *changed (device int32, zeroed by the caller) is raised when a label moved.  At the fixed point
+ *       labels[v] is the smallest vertex index of v's component (two vertices are connected when a face names both).
+ *   gip_mesh_component_stats  per label l: face_count [V] int32 = the faces of component l, box [V, 6] float32 = (min x, y, z, max x, y,
+ *       z) over the corners of its faces; integer atomics on order-preserving keys, so order-independent.  Rows of labels without a
+ *       face: count 0, box undefined.  Both are initialised here.
+ *   gip_mesh_cluster_keys  keys [V] int64 = (iz n + iy) n + ix with i = min((int) floorf((p - lo) / h), n - 1) per axis in float32.
+ *   gip_mesh_cluster_count  *count (device int32, zeroed here) = the faces whose three corners have three different keys.
+ *   gip_mesh_cluster_place  out [C, 3]: the quadric-optimal vertex of each of the C occupied cells (cell_key [C] int64 ascending),
+ *       clamped to its cell.  corner_order [3 F] int32: the face corners 3 f + k stably sorted by the cell of their vertex, corner_start
+ *       [C + 1] int32 the cells' offsets into it; member_order [V] int32 / member_start [C + 1] the same for the vertices.  `lanes` (16,
+ *       32 or 64) lanes walk a cell's runs in order and add their partial sums in a fixed tree: a gather, no float atomics, bitwise
+ *       equal from run to run (the last bits depend on `lanes`).
+ * Status 1: a NULL required pointer, V > 2^31 - 1, 3 F > 2^31 - 1, n outside 1 .. 2048, h not a positive finite number, C > V, lanes
+ * not 16, 32 or 64, rounds outside 1 .. 64; a call that fails so launches nothing.  Status 3: a launch error. */
+int gip_mesh_components_rounds(const int32_t* faces, int64_t F, int64_t V, int32_t* labels, int32_t* changed, int32_t rounds, void* stream);
+int gip_mesh_component_stats(const float* vertices, const int32_t* faces, int64_t F, int64_t V, const int32_t* labels, int32_t* face_count,
+                             float* box, void* stream);
+int gip_mesh_cluster_keys(const float* vertices, int64_t V, float lo_x, float lo_y, float lo_z, float h, int32_t n, int64_t* keys, void* stream);
+int gip_mesh_cluster_count(const float* vertices, int64_t V, const int32_t* faces, int64_t F, float lo_x, float lo_y, float lo_z, float h,
+                           int32_t n, int32_t* count, void* stream);
+int gip_mesh_cluster_place(const float* vertices, int64_t V, const int32_t* faces, int64_t F, const int64_t* cell_key, int64_t C,
+                           const int32_t* corner_order, const int32_t* corner_start, const int32_t* member_order, const int32_t* member_start,
+                           float lo_x, float lo_y, float lo_z, float h, int32_t n, int32_t lanes, float* out, void* stream);
 #ifdef __cplusplus
 }
 #endif

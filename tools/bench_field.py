@@ -12,7 +12,11 @@ hipEvent timing around each call, warm-up runs first, the median of the timed ru
     python tools/bench_field.py --texture       bake_texture (csrc/texture.hip) on the mesh of R 128 / 16 blocks at the default texture
                                                 size and at 2048: the whole call, gip_texture_bake alone, and the route without it on
                                                 the same texels — texel_points materialised, sorted by block, gip_field_sample, the
-                                                sums scattered into the texture (--out defaults to profiles/texture_bake.txt)"""
+                                                sums scattered into the texture (--out defaults to profiles/texture_bake.txt)
+    python tools/bench_field.py --decimate      clean_mesh and decimate_mesh (csrc/mesh_clean.hip) on the mesh of R 128 / 16 blocks: the
+                                                cleaning, the decimation to 1e5 and to 2e4 faces, the placement kernel alone at 16, 32
+                                                and 64 lanes per cell, and the atlas cell at T = 4096 before and after (--out defaults to
+                                                profiles/mesh_clean.txt)"""
 import argparse
 import os
 import statistics
@@ -218,6 +222,37 @@ def texture(gm, args):
     return lines
 
 
+def decimate(gm, args):
+    """clean_mesh, decimate_mesh to 1e5 and 2e4 faces and gip_mesh_cluster_place alone, on the mesh of the default geometry."""
+    from gaussianip_amd.utils import mesh
+    from gaussianip_amd.utils import texture as tex
+    R, nb, T = 128, 16, 4096
+    v, f = gm.extract_mesh(resolution=R, num_blocks=nb)
+    cv, cf, info = mesh.clean_mesh(v, f, validate=False)
+    c = timed(lambda: mesh.clean_mesh(v, f, validate=False), args.warmup, args.runs)
+    k = timed(lambda: mesh.connected_components(f, int(v.shape[0])), args.warmup, args.runs)
+    lines = ["R %3d  %d vertices, %d faces; atlas cell at T = %d: %d" % (R, v.shape[0], f.shape[0], T, tex.atlas_layout(int(f.shape[0]), T)[0]),
+             "       clean_mesh %9.3f [%.3f, %.3f]   connected_components alone %9.3f [%.3f, %.3f]" % (c + k),
+             "       %d components, %d kept (min_faces 8, min_diameter 0.05): %d vertices, %d faces; atlas cell %d" % (
+                 info["num_components"], info["num_kept"], cv.shape[0], cf.shape[0], tex.atlas_layout(int(cf.shape[0]), T)[0])]
+    for target in (100000, 20000):
+        dv, df, _, grid = mesh.decimate_mesh(cv, cf, target)
+        d = timed(lambda: mesh.decimate_mesh(cv, cf, target), args.warmup, args.runs)
+        lines.append("       decimate_mesh to %6d: %9.3f [%.3f, %.3f]   grid %d, %d vertices, %d faces; atlas cell %d" % (
+            (target,) + d + (grid, dv.shape[0], df.shape[0], tex.atlas_layout(int(df.shape[0]), T)[0])))
+        if grid == 0:
+            continue
+        one = timed(lambda: mesh.cluster_decimate(cv, cf, grid), args.warmup, args.runs)
+        runs = mesh._cluster_runs(cv, cf, grid)
+        cells = int(runs["cell_key"].shape[0])
+        lines.append("           cluster_decimate at that grid %9.3f [%.3f, %.3f]   %d occupied cells, %.1f corner entries and %.1f vertices per cell" % (
+            one + (cells, 3.0 * cf.shape[0] / cells, cv.shape[0] / cells)))
+        for lanes in (16, 32, 64):
+            p = timed(lambda: mesh._cluster_place(cv, cf, runs, lanes), args.warmup, args.runs)
+            lines.append("           gip_mesh_cluster_place alone, %2d lanes per cell %9.3f [%.3f, %.3f]" % ((lanes,) + p))
+    return lines
+
+
 def timed(fn, warmup, runs):
     for _ in range(warmup):
         fn()
@@ -242,10 +277,11 @@ def main():
     ap.add_argument("--once", type=int, default=0)
     ap.add_argument("--attributes", action="store_true")
     ap.add_argument("--texture", action="store_true")
+    ap.add_argument("--decimate", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "texture_bake.txt" if args.texture else "field_sample.txt" if args.attributes else
+        args.out = os.path.join(ROOT, "profiles", "mesh_clean.txt" if args.decimate else "texture_bake.txt" if args.texture else "field_sample.txt" if args.attributes else
                                 "field_extract.txt")
     gm = make_model(args.points)
     if args.once:
@@ -254,11 +290,13 @@ def main():
         return
     lines = ["tools/bench_field.py: %d Gaussians (human cloud, trained look), %s, median [min, max] of %d runs after %d warm-up, ms" % (
         args.points, "%s (%s)" % (torch.cuda.get_device_name(0), torch.cuda.get_device_properties(0).gcnArchName), args.runs, args.warmup)]
-    if args.texture:
+    if args.decimate:
+        lines += decimate(gm, args)
+    elif args.texture:
         lines += texture(gm, args)
     elif args.attributes:
         lines += attributes(gm, args)
-    for R in (() if args.attributes or args.texture else (128, 256)):
+    for R in (() if args.attributes or args.texture or args.decimate else (128, 256)):
         field = gm.extract_fields(resolution=R)
         chain, pairs = op_chain(gm, R, count_pairs=True)
         diff = float((field - chain).abs().max() / chain.abs().max())
