@@ -239,6 +239,23 @@ def model_lib():
         lib.gip_mesh_antialias.argtypes = [_vp, _i32, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i32, _i32, _vp, _vp]
         lib.gip_mesh_antialias_backward.restype = ctypes.c_int
         lib.gip_mesh_antialias_backward.argtypes = [_vp, _i32, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp]
+        lib.gip_mesh_rast_db.restype = ctypes.c_int
+        lib.gip_mesh_rast_db.argtypes = [_vp, _vp, _i32, _i64, _i64, _i32, _i32, _vp, _vp, _vp]
+        lib.gip_mesh_interpolate_da.restype = ctypes.c_int
+        lib.gip_mesh_interpolate_da.argtypes = [_vp, _i32, _i64, _i32, _vp, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]
+        lib.gip_mesh_interpolate_da_backward.restype = ctypes.c_int
+        lib.gip_mesh_interpolate_da_backward.argtypes = [_vp, _i32, _i64, _i32, _vp, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]
+        lib.gip_mesh_mip_levels.restype = ctypes.c_int
+        lib.gip_mesh_mip_levels.argtypes = [_i32, _i32, _i32, ctypes.POINTER(_i32), ctypes.POINTER(_i64)]
+        lib.gip_mesh_mip_build.restype = ctypes.c_int
+        lib.gip_mesh_mip_build.argtypes = [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp]
+        lib.gip_mesh_mip_fold.restype = ctypes.c_int
+        lib.gip_mesh_mip_fold.argtypes = [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp]
+        lib.gip_mesh_texture_mip.restype = ctypes.c_int
+        lib.gip_mesh_texture_mip.argtypes = [_vp, _i32, _i32, _i32, _i32, _vp, _i64, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]
+        lib.gip_mesh_texture_mip_backward.restype = ctypes.c_int
+        lib.gip_mesh_texture_mip_backward.argtypes = [_vp, _i32, _i32, _i32, _i32, _vp, _i64, _i32, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _i32,
+                                                      _vp, _vp, _vp, _vp, _vp, _vp]
         _f32 = ctypes.c_float
         lib.gip_mesh_components_rounds.restype = ctypes.c_int
         lib.gip_mesh_components_rounds.argtypes = [_vp, _i64, _i64, _vp, _vp, _i32, _vp]
@@ -399,5 +416,7 @@ MESH_SYMBOLS = ["gip_mesh_raster_workspace_size", "gip_mesh_rasterize", "gip_mes
                 "gip_mesh_texture", "gip_mesh_texture_backward", "gip_mesh_shade", "gip_mesh_shade_backward"]
 MESH_GRAD_SYMBOLS = ["gip_mesh_rasterize_backward", "gip_mesh_interpolate_backward_rast", "gip_mesh_shade_backward_rast", "gip_mesh_antialias",
                      "gip_mesh_antialias_backward"]
+MESH_MIP_SYMBOLS = ["gip_mesh_rast_db", "gip_mesh_interpolate_da", "gip_mesh_interpolate_da_backward", "gip_mesh_mip_levels",
+                    "gip_mesh_mip_build", "gip_mesh_mip_fold", "gip_mesh_texture_mip", "gip_mesh_texture_mip_backward"]
 MESH_CLEAN_SYMBOLS = ["gip_mesh_components_rounds", "gip_mesh_component_stats", "gip_mesh_cluster_keys", "gip_mesh_cluster_count",
                       "gip_mesh_cluster_place"]

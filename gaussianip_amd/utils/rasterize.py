@@ -13,8 +13,12 @@ Gradients to vertex positions and the antialias pass (csrc/mesh_grad.hip) are op
 position_gradients / antialias of render_mesh.  There rast carries a gradient to pos (the snapping is straight-through), interpolate
 and the fused shade are differentiable in rast, and antialias blends across silhouette edges, which is the one route by which a loss
 on coverage reaches the geometry.  The default MeshRasterizerContext and the default keywords behave as they always did and raise
-NotImplementedError when asked for either.  One piece of nvdiffrast is still missing: mipmaps (rast_db, diff_attrs, uv_da, mip, any
-filter mode but "linear"); the functions raise NotImplementedError naming the argument when asked for them.
+NotImplementedError when asked for either.
+
+Pixel differentials and mipmaps (csrc/mesh_mip.hip) are opt-in in the same way: MipMeshRasterizerContext returns rast_db from
+rasterize, takes rast_db / diff_attrs in interpolate and uv_da / mip_level_bias / mip / max_mip_level and the mipmap filter modes in
+texture, with their gradients.  The two other contexts raise NotImplementedError naming the argument when asked for any of them, and
+render_mesh stays bilinear: the baked atlas gives every face its own cell, and a mip level above 0 would mix unrelated faces.
 """
 import ctypes
 
@@ -22,7 +26,7 @@ import torch
 
 from .. import _lib
 
-__all__ = ["MeshRasterizerContext", "DiffMeshRasterizerContext", "edge_topology", "render_mesh"]
+__all__ = ["MeshRasterizerContext", "DiffMeshRasterizerContext", "MipMeshRasterizerContext", "MipStack", "edge_topology", "render_mesh"]
 
 
 def _p(t):
@@ -351,7 +355,8 @@ def _antialias(color, rast, pos, tri, topology, cache):
 
 class MeshRasterizerContext:
     """The interface of the reference's NVDiffRasterizerContext.  context_type is accepted and ignored (there is one rasterizer).
-    This default context sends no gradient to positions and has no antialias pass; DiffMeshRasterizerContext has both."""
+    This default context sends no gradient to positions and has no antialias pass; DiffMeshRasterizerContext has both, and
+    MipMeshRasterizerContext adds pixel differentials and mipmaps."""
 
     _rast_input = staticmethod(_rast_tensor)      # rast is detached here: this context sends no gradient through it
 
@@ -425,7 +430,7 @@ def _rast_with_gradient(rast):
 class DiffMeshRasterizerContext(MeshRasterizerContext):
     """MeshRasterizerContext with what a loss on the geometry needs (csrc/mesh_grad.hip): the class to alias to the reference's
     NVDiffRasterizerContext wherever antialias or a gradient to vertex positions is used.  The forward results are those of the
-    default context bit for bit.  Mipmaps (rast_db, diff_attrs, uv_da, mip) stay unsupported."""
+    default context bit for bit.  Pixel differentials and mipmaps (rast_db, diff_attrs, uv_da, mip) are MipMeshRasterizerContext's."""
 
     _rast_input = staticmethod(_rast_with_gradient)
 
@@ -449,6 +454,235 @@ class DiffMeshRasterizerContext(MeshRasterizerContext):
         are those of rasterize.  topology: what edge_topology(tri, V) returned; None builds it and keeps it on the context for this
         tri (the same tensor object, not edited in place since)."""
         return _antialias(color, rast, pos, tri, topology, self._topology)
+
+
+# ---------------------------------------------------------------------------------------------------------------- differentials, mipmaps
+def _rast_db_launch(pos, tri, rast):
+    B, H, W, _ = rast.shape
+    V, F = int(pos.shape[1]), int(tri.shape[0])
+    rast_db = torch.empty_like(rast)
+    with torch.cuda.device(rast.device):
+        _check(_lib.model_lib().gip_mesh_rast_db(_p(pos), _p(tri), B, V, F, H, W, _p(rast), _p(rast_db), _stream(rast.device)),
+               "gip_mesh_rast_db")
+    return rast_db
+
+
+class _InterpolateDa(torch.autograd.Function):
+    """out_da of gip_mesh_interpolate_da; differentiable in attr alone (it does not depend on u, v, and rast_db carries no gradient)."""
+
+    @staticmethod
+    def forward(ctx, attr, rast, rast_db, idx, channels, K, F):
+        B, H, W, _ = rast.shape
+        nb, N, C = attr.shape
+        out = torch.empty((B, H, W, 2 * K), dtype=torch.float32, device=rast.device)
+        with torch.cuda.device(rast.device):
+            _check(_lib.model_lib().gip_mesh_interpolate_da(_p(attr), nb, N, C, _p(idx), F, _p(rast), _p(rast_db), _p(channels), K, B, H, W,
+                                                            _p(out), _stream(rast.device)), "gip_mesh_interpolate_da")
+        ctx.save_for_backward(rast, rast_db, idx, channels)
+        ctx.shape, ctx.K, ctx.F = (nb, N, C), K, F
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        rast, rast_db, idx, channels = ctx.saved_tensors
+        nb, N, C = ctx.shape
+        B, H, W, _ = rast.shape
+        g = g.contiguous().float()
+        g_attr = torch.empty((nb, N, C), dtype=torch.float32, device=rast.device)
+        with torch.cuda.device(rast.device):
+            _check(_lib.model_lib().gip_mesh_interpolate_da_backward(_p(g), nb, N, C, _p(idx), ctx.F, _p(rast), _p(rast_db), _p(channels),
+                                                                     ctx.K, B, H, W, _p(g_attr), _stream(rast.device)),
+                   "gip_mesh_interpolate_da_backward")
+        return g_attr, None, None, None, None, None, None
+
+
+def _mip_levels(Th, Tw, max_mip_level):
+    """(max_level as the library takes it, L, the texels of levels 1 .. L) of gip_mesh_mip_levels."""
+    if max_mip_level is None:
+        cap = -1
+    else:
+        cap = int(max_mip_level)
+        if cap < 0:
+            raise ValueError("max_mip_level must be None or >= 0")
+    L, texels = ctypes.c_int32(0), ctypes.c_int64(0)
+    _check(_lib.model_lib().gip_mesh_mip_levels(Th, Tw, cap, ctypes.byref(L), ctypes.byref(texels)), "gip_mesh_mip_levels")
+    return cap, int(L.value), int(texels.value)
+
+
+def _texture_tensor(tex):
+    if not (isinstance(tex, torch.Tensor) and tex.is_cuda and tex.dtype == torch.float32 and tex.dim() in (3, 4)):
+        raise ValueError("tex must be a float32 GPU tensor, [1 or B, Th, Tw, C] or [Th, Tw, C]")
+    t = tex[None] if tex.dim() == 3 else tex
+    if min(t.shape) < 1 or max(t.shape[1:3]) > 16384 or t.numel() > 2 ** 31 - 1:
+        raise ValueError("tex must have at least one texel and channel, at most 16384 texels a side and at most 2^31 - 1 values")
+    return t
+
+
+class MipStack:
+    """The mip levels of one texture, what MipMeshRasterizerContext.texture_construct_mip returns and texture takes as mip=.  Level 0 is
+    the texture itself; `buffer` [nb, texels, C] holds levels 1 .. L one after the other (csrc/mesh_mip.hip states the rule), and
+    levels() returns all of them as [nb, h, w, C] views.  The stack is a constant: gradients reach the `tex` given to texture."""
+
+    def __init__(self, shape, max_level, L, texels, buffer):
+        self.shape, self.max_level, self.L, self.texels, self.buffer = tuple(shape), max_level, L, texels, buffer
+
+    def levels(self, tex=None):
+        nb, h, w, C = self.shape
+        out, off = ([] if tex is None else [tex.reshape(self.shape)]), 0
+        for _ in range(self.L):
+            h, w = max(h // 2, 1), max(w // 2, 1)
+            out.append(self.buffer[:, off:off + h * w].reshape(nb, h, w, C))
+            off += h * w
+        return out
+
+
+def _construct_mip(t, max_mip_level):
+    nb, Th, Tw, C = (int(x) for x in t.shape)
+    cap, L, texels = _mip_levels(Th, Tw, max_mip_level)
+    buffer = torch.empty((nb, texels, C), dtype=torch.float32, device=t.device)
+    if L:
+        with torch.cuda.device(t.device):
+            _check(_lib.model_lib().gip_mesh_mip_build(_p(t), nb, Th, Tw, C, cap, _p(buffer), texels, _stream(t.device)), "gip_mesh_mip_build")
+    return MipStack((nb, Th, Tw, C), cap, L, texels, buffer)
+
+
+class _TextureMip(torch.autograd.Function):
+    """gip_mesh_texture_mip; uv_da and bias may be None.  The gradient to tex goes through the gradient stack and its fold."""
+
+    @staticmethod
+    def forward(ctx, tex, uv, uv_da, bias, stack, nearest):
+        nb, Th, Tw, C = tex.shape
+        B, H, W, _ = uv.shape
+        out = torch.empty((B, H, W, C), dtype=torch.float32, device=uv.device)
+        with torch.cuda.device(uv.device):
+            _check(_lib.model_lib().gip_mesh_texture_mip(_p(tex), nb, Th, Tw, C, _p(stack.buffer), stack.texels, stack.max_level, _p(uv), _p(uv_da),
+                                                         _p(bias), int(nearest), B, H, W, _p(out), _stream(uv.device)), "gip_mesh_texture_mip")
+        ctx.save_for_backward(tex, uv, uv_da, bias)
+        ctx.stack, ctx.nearest = stack, int(nearest)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        tex, uv, uv_da, bias = ctx.saved_tensors
+        stack = ctx.stack
+        nb, Th, Tw, C = tex.shape
+        B, H, W, _ = uv.shape
+        g = g.contiguous().float()
+        g_tex = torch.empty_like(tex) if ctx.needs_input_grad[0] else None
+        g_mip = torch.empty_like(stack.buffer) if g_tex is not None and stack.L else None
+        g_uv = torch.empty_like(uv) if ctx.needs_input_grad[1] else None
+        g_da = torch.empty_like(uv_da) if uv_da is not None and ctx.needs_input_grad[2] else None
+        g_bias = torch.empty_like(bias) if bias is not None and ctx.needs_input_grad[3] else None
+        lib = _lib.model_lib()
+        with torch.cuda.device(uv.device):
+            _check(lib.gip_mesh_texture_mip_backward(_p(tex), nb, Th, Tw, C, _p(stack.buffer), stack.texels, stack.max_level, _p(uv), _p(uv_da),
+                                                     _p(bias), ctx.nearest, _p(g), B, H, W, _p(g_tex), _p(g_mip), _p(g_uv), _p(g_da), _p(g_bias),
+                                                     _stream(uv.device)), "gip_mesh_texture_mip_backward")
+            if g_mip is not None:
+                _check(lib.gip_mesh_mip_fold(_p(g_tex), nb, Th, Tw, C, stack.max_level, _p(g_mip), stack.texels, _stream(uv.device)),
+                       "gip_mesh_mip_fold")
+        return g_tex, g_uv, g_da, g_bias, None, None
+
+
+class MipMeshRasterizerContext(DiffMeshRasterizerContext):
+    """DiffMeshRasterizerContext with pixel differentials and mipmaps (csrc/mesh_mip.hip): the class to alias to the reference's
+    NVDiffRasterizerContext wherever rast_db, diff_attrs or a mipmapped texture lookup is used.  rasterize returns (rast, rast_db) as
+    the reference's wrapper does; rast, interpolate's first value and a "linear" lookup are the parent's, bit for bit.
+
+    rast_db carries no gradient to pos (nvdiffrast's grad_db=False; the reference's wrapper asks for grad_db=True): a loss reaches the
+    positions through rast and through antialias, as in the parent, but not through the level of detail."""
+
+    def rasterize(self, pos, tri, resolution, cull_backfaces=False, validate=True):
+        """(rast [B, H, W, 4], rast_db [B, H, W, 4]): rast as DiffMeshRasterizerContext.rasterize gives it, rast_db = (du/dX, du/dY,
+        dv/dX, dv/dY) of its (u, v) in pixels (Y grows with the row index), zeros at empty pixels.  rast_db.requires_grad is False."""
+        rast = _rasterize(pos, tri, resolution, cull_backfaces, validate, differentiable=True)
+        if int(tri.shape[0]) == 0:      # nothing is drawn: no launch
+            return rast, torch.zeros_like(rast)
+        return rast, _rast_db_launch(pos.detach().contiguous(), tri.detach().contiguous(), rast.detach())
+
+    def rasterize_one(self, pos, tri, resolution, cull_backfaces=False, validate=True):
+        """rasterize of one view: pos [V, 4] -> (rast [H, W, 4], rast_db [H, W, 4])."""
+        if not (isinstance(pos, torch.Tensor) and pos.dim() == 2):
+            raise ValueError("rasterize_one needs pos as [V, 4]")
+        rast, rast_db = self.rasterize(pos[None, ...], tri, resolution, cull_backfaces, validate)
+        return rast[0], rast_db[0]
+
+    def interpolate(self, attr, rast, tri, rast_db=None, diff_attrs=None):
+        """(out, out_da).  Without rast_db and diff_attrs: the parent's (out, None).  With both: out is the parent's, bit for bit, and
+        out_da [B, H, W, 2 K] holds (da/dX, da/dY) per pixel for the K channels of diff_attrs ("all", or a list of channel indices, in
+        the list's order); zeros at empty pixels.  out_da is differentiable in attr (float atomic adds); nothing reaches rast or rast_db
+        through it.  ValueError for one of the two without the other, an index outside [0, C) or a wrong shape."""
+        if rast_db is None and diff_attrs is None:
+            return super().interpolate(attr, rast, tri)
+        if rast_db is None or diff_attrs is None:
+            raise ValueError("interpolate: rast_db and diff_attrs go together (got only %s)" % ("diff_attrs" if rast_db is None else "rast_db"))
+        out, _ = super().interpolate(attr, rast, tri)
+        r = _rast_tensor(rast)
+        db = _gpu_float(rast_db, "rast_db", (4,), 4)
+        if tuple(db.shape) != tuple(r.shape) or db.device != r.device:
+            raise ValueError("rast_db must have rast's shape [B, H, W, 4] and device")
+        a = (attr[None] if attr.dim() == 2 else attr).contiguous()
+        C = int(a.shape[2])
+        if isinstance(diff_attrs, str):
+            if diff_attrs != "all":
+                raise ValueError("diff_attrs must be 'all' or a list of channel indices")
+            channels, K = None, C
+        else:
+            chosen = [int(c) for c in diff_attrs]
+            if not chosen or min(chosen) < 0 or max(chosen) >= C:
+                raise ValueError("diff_attrs: channel indices must lie in [0, %d) and there must be at least one" % C)
+            channels, K = torch.tensor(chosen, dtype=torch.int32, device=r.device), len(chosen)
+        if r.numel() // 4 * 2 * K > 2 ** 31 - 1:
+            raise ValueError("interpolate: out_da would hold more than 2^31 - 1 values")
+        idx = _index_tensor(tri, "tri", int(a.shape[1]), validate=False)      # the parent's call has checked it
+        return out, _InterpolateDa.apply(a, r, db, idx, channels, K, int(idx.shape[0]))
+
+    def texture_construct_mip(self, tex, max_mip_level=None):
+        """The MipStack of tex [1 or B, Th, Tw, C] (or [Th, Tw, C]) to pass as texture(..., mip=): level l + 1 averages the 2 x 2
+        blocks of level l, while every side above 1 is even, down to 1 x 1 or max_mip_level.  One call into the library."""
+        return _construct_mip(_texture_tensor(tex).detach().contiguous(), max_mip_level)
+
+    def texture(self, tex, uv, filter_mode="auto", uv_da=None, mip_level_bias=None, mip=None, max_mip_level=None, boundary_mode="clamp"):
+        """[B, H, W, C]: the lookup of tex [1 or B, Th, Tw, C] (or [Th, Tw, C]) at uv [B, H, W, 2].  filter_mode "auto" is
+        "linear-mipmap-linear" when uv_da or mip_level_bias is given and "linear" otherwise; "linear" is the parent's lookup;
+        "linear-mipmap-nearest" takes the one nearest level.  uv_da [B, H, W, 4] = (ds/dX, ds/dY, dt/dX, dt/dY) is what
+        interpolate(uv, ..., rast_db, "all") returns; mip_level_bias [B, H, W] is added to the level.  mip: a MipStack of this tex
+        (texture_construct_mip), else the stack is built here, capped at max_mip_level.  Differentiable in tex, uv, uv_da and
+        mip_level_bias (float atomic adds to tex); with mip= given the gradient still reaches `tex`, the stack is a constant."""
+        if boundary_mode != "clamp":
+            raise NotImplementedError("texture: boundary_mode %r is not supported, only 'clamp'" % (boundary_mode,))
+        if filter_mode == "auto":
+            filter_mode = "linear-mipmap-linear" if uv_da is not None or mip_level_bias is not None else "linear"
+        if filter_mode == "linear":
+            if uv_da is not None or mip_level_bias is not None or mip is not None:
+                raise ValueError("texture: filter_mode 'linear' takes no uv_da, mip_level_bias or mip")
+            return super().texture(tex, uv)
+        if filter_mode not in ("linear-mipmap-linear", "linear-mipmap-nearest"):
+            raise NotImplementedError("texture: filter_mode %r is not supported" % (filter_mode,))
+        if isinstance(mip, (list, tuple)):
+            raise NotImplementedError("texture: mip as a list of tensors is not supported, pass what texture_construct_mip returned")
+        t = _texture_tensor(tex)
+        if not (isinstance(uv, torch.Tensor) and uv.is_cuda and uv.dtype == torch.float32 and uv.dim() == 4 and uv.shape[-1] == 2):
+            raise ValueError("uv must be a float32 GPU tensor [B, H, W, 2]")
+        if t.shape[0] not in (1, uv.shape[0]) or t.device != uv.device:
+            raise ValueError("tex must have a batch of 1 or B and live on uv's device")
+        for extra, what, shape in ((uv_da, "uv_da", tuple(uv.shape[:3]) + (4,)), (mip_level_bias, "mip_level_bias", tuple(uv.shape[:3]))):
+            if extra is not None and not (isinstance(extra, torch.Tensor) and extra.is_cuda and extra.dtype == torch.float32 and
+                                          tuple(extra.shape) == shape and extra.device == uv.device):
+                raise ValueError("%s must be a float32 GPU tensor of shape %s" % (what, list(shape)))
+        t = t.contiguous()
+        if mip is None:
+            stack = _construct_mip(t.detach(), max_mip_level)
+        elif not isinstance(mip, MipStack):
+            raise ValueError("mip must be what texture_construct_mip returned")
+        else:
+            stack = mip
+            if stack.shape != tuple(t.shape) or stack.buffer.device != t.device:
+                raise ValueError("mip was built from a texture of shape %s, tex has %s" % (list(stack.shape), list(t.shape)))
+            if max_mip_level is not None and _mip_levels(int(t.shape[1]), int(t.shape[2]), max_mip_level)[1] != stack.L:
+                raise ValueError("max_mip_level does not match the given mip (%d levels above 0)" % stack.L)
+        return _TextureMip.apply(t, uv.contiguous(), None if uv_da is None else uv_da.contiguous(),
+                                 None if mip_level_bias is None else mip_level_bias.contiguous(), stack, filter_mode == "linear-mipmap-nearest")
 
 
 _render_topology = _TopologyCache()

@@ -247,6 +247,48 @@ int gip_mesh_antialias(const float* color, int32_t C, const float* rast, const f
 int gip_mesh_antialias_backward(const float* color, int32_t C, const float* rast, const float* pos, const int32_t* tri, const int32_t* topo,
                                 int32_t B, int64_t V, int64_t F, int32_t H, int32_t W, const float* g_out, float* g_color, float* g_pos,
                                 void* stream);
+/* Pixel differentials and the mipmapped lookup (csrc/mesh_mip.hip, whose header states the definitions; the opt-in
+ * MipMeshRasterizerContext of gaussianip_amd/utils/rasterize.py).  The reference lines are those of threestudio/utils/rasterize.py.
+ *   gip_mesh_rast_db  the second value of dr.rasterize(..., grad_db=True) (rasterize.py:37, rasterize_one's rast_db[0] at :47): rast_db
+ *       [B, H, W, 4] = (du/dX, du/dY, dv/dX, dv/dY) in pixels from pos, tri and the rast of gip_mesh_rasterize; zeros at an empty
+ *       pixel.  F == 0 or V == 0 only zero-fills.  No gradient to pos is defined through it (nvdiffrast's grad_db = False).
+ *   gip_mesh_interpolate_da  dr.interpolate(..., rast_db=, diff_attrs=) (rasterize.py:66-68): out_da [B, H, W, 2 K] = (da/dX, da/dY) of
+ *       the K channels `channels` [K] int32 lists on the device (NULL: K == C, all channels in order); a listed channel outside [0, C)
+ *       reads nothing and gives zeros.  The other arguments are those of gip_mesh_interpolate.
+ *   gip_mesh_interpolate_da_backward  its backward to attr: g_attr [attr_batch, N, C] from g_da [B, H, W, 2 K]; zero-filled here, then
+ *       float atomic adds.  Nothing reaches rast or rast_db.
+ *   gip_mesh_mip_levels  host only: *levels = L, the index of the last level of the stack of a Th x Tw texture (max_level < 0: no cap),
+ *       *texels = the texels of levels 1 .. L together, which is what `mip` holds per texture (times C floats).
+ *   gip_mesh_mip_build  dr.texture_construct_mip: levels 1 .. L of tex [tex_batch, Th, Tw, C] into mip [tex_batch, mip_texels, C], one
+ *       launch per level; L == 0 launches nothing.  mip_texels must be what gip_mesh_mip_levels gives (status 1 otherwise).
+ *   gip_mesh_mip_fold  the build's transpose: the gradient stack g_mip (levels L .. 1, edited in place) folded into g_tex, a gather
+ *       per level, bit-reproducible.
+ *   gip_mesh_texture_mip  dr.texture(..., uv_da=, mip_level_bias=, mip=, filter_mode='linear-mipmap-linear' or, nearest != 0,
+ *       'linear-mipmap-nearest', boundary_mode='clamp'): out [B, H, W, C]; uv_da [B, H, W, 4] and bias [B, H, W] may each be NULL.
+ *   gip_mesh_texture_mip_backward  g_tex [tex_batch, Th, Tw, C] and g_mip [tex_batch, mip_texels, C] (both zero-filled here, then float
+ *       atomic adds; g_mip is needed with g_tex when L > 0, and gip_mesh_mip_fold then completes g_tex), g_uv [B, H, W, 2], g_uv_da
+ *       [B, H, W, 4] (needs uv_da), g_bias [B, H, W] (needs bias); each may be NULL.
+ * Status as above; additionally 1 for K < 1, B H W 2 K > 2^31 - 1, tex_batch Th Tw C > 2^31 - 1 or a mip_texels that does not match. */
+int gip_mesh_rast_db(const float* pos, const int32_t* tri, int32_t B, int64_t V, int64_t F, int32_t H, int32_t W, const float* rast,
+                     float* rast_db, void* stream);
+int gip_mesh_interpolate_da(const float* attr, int32_t attr_batch, int64_t N, int32_t C, const int32_t* idx, int64_t F, const float* rast,
+                            const float* rast_db, const int32_t* channels, int32_t K, int32_t B, int32_t H, int32_t W, float* out_da,
+                            void* stream);
+int gip_mesh_interpolate_da_backward(const float* g_da, int32_t attr_batch, int64_t N, int32_t C, const int32_t* idx, int64_t F,
+                                     const float* rast, const float* rast_db, const int32_t* channels, int32_t K, int32_t B, int32_t H,
+                                     int32_t W, float* g_attr, void* stream);
+int gip_mesh_mip_levels(int32_t Th, int32_t Tw, int32_t max_level, int32_t* levels, int64_t* texels);
+int gip_mesh_mip_build(const float* tex, int32_t tex_batch, int32_t Th, int32_t Tw, int32_t C, int32_t max_level, float* mip,
+                       int64_t mip_texels, void* stream);
+int gip_mesh_mip_fold(float* g_tex, int32_t tex_batch, int32_t Th, int32_t Tw, int32_t C, int32_t max_level, float* g_mip,
+                      int64_t mip_texels, void* stream);
+int gip_mesh_texture_mip(const float* tex, int32_t tex_batch, int32_t Th, int32_t Tw, int32_t C, const float* mip, int64_t mip_texels,
+                         int32_t max_level, const float* uv, const float* uv_da, const float* bias, int32_t nearest, int32_t B, int32_t H,
+                         int32_t W, float* out, void* stream);
+int gip_mesh_texture_mip_backward(const float* tex, int32_t tex_batch, int32_t Th, int32_t Tw, int32_t C, const float* mip,
+                                  int64_t mip_texels, int32_t max_level, const float* uv, const float* uv_da, const float* bias,
+                                  int32_t nearest, const float* g_out, int32_t B, int32_t H, int32_t W, float* g_tex, float* g_mip,
+                                  float* g_uv, float* g_uv_da, float* g_bias, void* stream);
 /* Cleaning and decimating the extracted mesh (csrc/mesh_clean.hip, whose header states the definitions; gaussianip_amd/utils/mesh.py
  * connected_components, clean_mesh, cluster_decimate, decimate_mesh).  In place of the reference's third-party clean_mesh and
  * decimate_mesh (gs_renderer.py:346-350).  vertices [V, 3] float32, faces [F, 3] int32, everything on the device; a face with an index

@@ -10,7 +10,13 @@ Kernel times come from a kernel trace taken in a run of its own and are merged a
     python tools/bench_mesh_render.py --kernel-stats DIR/*/*_kernel_stats.csv [--out profiles/mesh_render.json]
 Beside every kernel's time stand the bytes it must move (computed here from the shapes and the counts of the scene, not measured)
 and the share of the HBM roofline that makes: those bytes over the time, over 8.0 TB/s (the float atomic adds of the backward over the
-1.3 TB/s at which the chip adds)."""
+1.3 TB/s at which the chip adds).
+
+--mip times the pieces of MipMeshRasterizerContext (csrc/mesh_mip.hip) on the same scene, each entry point on its own with device
+events: gip_mesh_rast_db, the build of the mip stack of a 4096 x 4096 x 3 texture, gip_mesh_texture_mip forward and backward (the
+backward with its fold), and beside them the bilinear gip_mesh_texture forward and backward at the same uv as the yardstick.  The uv
+are per vertex (its x, y inside the mesh's bounding box), interpolated per pixel with their differentials:
+    python tools/bench_mesh_render.py --mip [--out profiles/mesh_mip.json]"""
 import argparse
 import csv
 import json
@@ -118,6 +124,83 @@ def measure(args):
     return result
 
 
+MIP_TEXTURE = 4096
+
+
+def measure_mip(args):
+    """Every piece as one call through the context, timed alone.  The texture is random (the lookup's cost does not depend on its
+    values).  The baked atlas has no continuous layout, so the uv here are per vertex: its x and y inside the mesh's bounding box,
+    which spreads 4096 texels over the few hundred pixels the mesh covers, at a density that changes with the surface's angle."""
+    from gaussianip_amd.utils.rasterize import MipMeshRasterizerContext
+    _, cams, (v, f, _, uv, texture) = make_scene()
+    ctx = MipMeshRasterizerContext()
+    gen = torch.Generator(device="cuda").manual_seed(0)
+    mvp = torch.stack([c.full_proj_transform.float() for c in cams])
+    pos = torch.matmul(torch.cat((v, torch.ones_like(v[:, :1])), 1)[None], mvp).contiguous()
+    rast, rast_db = ctx.rasterize(pos, f, SIZE, validate=False)
+    # per-vertex texture coordinates with a continuous layout: the vertex's position in its bounding box, x and y
+    lo, hi = v.min(0).values, v.max(0).values
+    attr = ((v - lo) / (hi - lo))[:, :2].contiguous()
+    st, st_da = ctx.interpolate(attr, rast, f, rast_db=rast_db, diff_attrs="all")
+    # An empty pixel interpolates to uv (0, 0): left there, the 2.4 M empty pixels of this scene would all add their gradient to the one
+    # texel (0, 0), and the backward would time that contention (362 ms, against 1 ms without it) and not the lookup.  They look up a
+    # screen-aligned background instead: their own position, 4 texels a pixel.
+    empty = (rast[..., 3:] == 0)
+    ramp = (torch.arange(SIZE, device="cuda", dtype=torch.float32) + 0.5) / SIZE
+    screen = torch.stack(torch.meshgrid(ramp, ramp, indexing="xy"), -1)[None].expand(VIEWS, SIZE, SIZE, 2)
+    st = torch.where(empty, screen, st).contiguous()
+    st_da = torch.where(empty, torch.tensor([1.0 / SIZE, 0.0, 0.0, 1.0 / SIZE], device="cuda"), st_da).contiguous()
+    tex = torch.rand((MIP_TEXTURE, MIP_TEXTURE, 3), device="cuda", generator=gen)
+    g = torch.randn((VIEWS, SIZE, SIZE, 3), device="cuda", generator=gen)
+    stack = ctx.texture_construct_mip(tex)
+    covered = rast[..., 3] > 0
+    with torch.no_grad():
+        sx, sy, tx, ty = (st_da[..., k] * MIP_TEXTURE for k in range(4))
+        A, B, C = sx * sx + tx * tx, sy * sy + ty * ty, sx * sy + tx * ty
+        level = 0.5 * torch.log2(0.5 * (A + B) + torch.sqrt(0.25 * (A - B) ** 2 + C * C))[covered]
+        lc = level.clamp(0, stack.L)
+    tex_g, st_g = tex.clone().requires_grad_(True), st.clone().requires_grad_(True)
+    da_g = st_da.clone().requires_grad_(True)
+
+    def backward_of(fn):
+        def run():
+            tex_g.grad = st_g.grad = da_g.grad = None
+            fn().backward(g)
+        return run
+
+    timed = {
+        "gip_mesh_rast_db": lambda: ctx.rasterize(pos, f, SIZE, validate=False),
+        "gip_mesh_rasterize_alone": lambda: super(MipMeshRasterizerContext, ctx).rasterize(pos, f, SIZE, validate=False),
+        "mip_build_4096": lambda: ctx.texture_construct_mip(tex),
+        "gip_mesh_texture_mip_forward": lambda: ctx.texture(tex, st, uv_da=st_da, mip=stack),
+        "gip_mesh_texture_mip_forward_backward": backward_of(lambda: ctx.texture(tex_g, st_g, uv_da=da_g, mip=stack)),
+        "gip_mesh_texture_forward": lambda: ctx.texture(tex, st),
+        "gip_mesh_texture_forward_backward": backward_of(lambda: ctx.texture(tex_g, st_g)),
+    }
+    with torch.no_grad():
+        times = {k: windows(fn, args.iters, args.windows, args.warmup) for k, fn in timed.items() if "backward" not in k}
+    times.update({k: windows(fn, args.iters, args.windows, args.warmup) for k, fn in timed.items() if "backward" in k})
+    med = lambda k: times[k]["median_ms"]  # noqa: E731
+    derived = {
+        "rast_db_ms": med("gip_mesh_rast_db") - med("gip_mesh_rasterize_alone"),
+        "texture_mip_backward_ms": med("gip_mesh_texture_mip_forward_backward") - med("gip_mesh_texture_mip_forward"),
+        "texture_backward_ms": med("gip_mesh_texture_forward_backward") - med("gip_mesh_texture_forward"),
+        "forward_ratio_to_bilinear": med("gip_mesh_texture_mip_forward") / med("gip_mesh_texture_forward"),
+        "forward_backward_ratio_to_bilinear": med("gip_mesh_texture_mip_forward_backward") / med("gip_mesh_texture_forward_backward"),
+    }
+    return {"device": "%s (%s)" % (torch.cuda.get_device_name(0), torch.cuda.get_device_properties(0).gcnArchName),
+            "scene": "blob_cloud extracted at resolution %d, %d orbit cameras at %d x %d as one batch, a random %d x %d x 3 texture looked up "
+                     "at per-vertex uv (the vertex's x, y in the mesh's bounding box) with their pixel differentials; empty pixels look up their screen position, 4 texels a pixel" % (
+                         RESOLUTION, VIEWS, SIZE, SIZE, MIP_TEXTURE, MIP_TEXTURE),
+            "counts": {"pixels": VIEWS * SIZE * SIZE, "covered_pixels": int(covered.sum()), "faces": int(f.shape[0]), "levels": stack.L,
+                       "level_of_detail_quartiles_covered": [float(x) for x in torch.quantile(level.float(), torch.tensor([0.0, 0.25, 0.5, 0.75, 1.0], device="cuda"))],
+                       "share_of_covered_pixels_reading_two_levels": float(((lc > 0) & (lc < stack.L)).float().mean())},
+            "timing": "device events, median of %d windows of %d calls after %d warm-up windows, ms per call through the Python context; "
+                      "the backward rows are forward + backward, the derived rows their difference; rast_db_ms is rasterize with rast_db "
+                      "minus rasterize alone; the mip backward includes both memsets and the fold" % (args.windows, args.iters, args.warmup),
+            "times": times, "derived": derived}
+
+
 def merge_kernel_stats(result, path):
     """Per-kernel average times of a `rocprofv3 --kernel-trace --stats` run of `--once`, with the bytes each kernel must move."""
     need = required_bytes(result["counts"])
@@ -147,9 +230,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--once", type=int, default=0)
     ap.add_argument("--kernel-stats", default=None)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mesh_render.json"))
+    ap.add_argument("--mip", action="store_true", help="time the pieces of MipMeshRasterizerContext instead")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    if args.kernel_stats:
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "mesh_mip.json" if args.mip else "mesh_render.json")
+    if args.mip:
+        assert torch.cuda.is_available(), "bench_mesh_render needs a GPU"
+        result = measure_mip(args)
+    elif args.kernel_stats:
         with open(args.out) as fh:
             result = json.load(fh)
         result = merge_kernel_stats(result, args.kernel_stats)
