@@ -212,6 +212,10 @@ def model_lib():
         lib.gip_texture_bake.argtypes = [_vp, _vp, _vp, _vp, _vp, ctypes.c_int64, _vp, ctypes.c_float, _vp, ctypes.c_int32, ctypes.c_int32,
                                          ctypes.c_float, _vp, ctypes.c_int64, _vp, ctypes.c_int64, _vp, _vp, ctypes.c_int32, ctypes.c_int32,
                                          ctypes.c_int32, _vp, ctypes.c_size_t, _vp, _vp, _vp]
+        lib.gip_texture_project.restype = ctypes.c_int
+        lib.gip_texture_project.argtypes = [_vp, ctypes.c_int64, _vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp,
+                                            ctypes.c_int32, ctypes.c_int32, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_int32,
+                                            ctypes.c_int32, _vp, _vp, _vp, _vp]
         _i32, _i64 = ctypes.c_int32, ctypes.c_int64
         lib.gip_mesh_raster_workspace_size.restype = ctypes.c_int
         lib.gip_mesh_raster_workspace_size.argtypes = [_i32, _i32, _i32, _i64, ctypes.POINTER(ctypes.c_size_t)]
@@ -412,6 +416,7 @@ RASTER_SYMBOLS = ["gip_abi_version", "gip_status_string", "gip_raster_state_byte
 FIELD_SYMBOLS = ["gip_field_workspace_size", "gip_density_field", "gip_surface_count", "gip_surface_emit"]
 SAMPLE_SYMBOLS = ["gip_field_sample_workspace_size", "gip_field_sample"]
 TEXTURE_SYMBOLS = ["gip_texture_bake_workspace_size", "gip_texture_bake"]
+TEXTURE_PROJECT_SYMBOLS = ["gip_texture_project"]
 MESH_SYMBOLS = ["gip_mesh_raster_workspace_size", "gip_mesh_rasterize", "gip_mesh_interpolate", "gip_mesh_interpolate_backward",
                 "gip_mesh_texture", "gip_mesh_texture_backward", "gip_mesh_shade", "gip_mesh_shade_backward"]
 MESH_GRAD_SYMBOLS = ["gip_mesh_rasterize_backward", "gip_mesh_interpolate_backward_rast", "gip_mesh_shade_backward_rast", "gip_mesh_antialias",

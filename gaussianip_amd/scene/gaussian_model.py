@@ -488,19 +488,86 @@ class GaussianModel:
         return out
 
     @torch.no_grad()
+    def bake_texture_from_views(self, vertices, faces, cameras, pipe=None, texture_size=None, images=None, alphas=None, depth_tolerance=None,
+                                *, min_cos=0.2, min_alpha=0.5, two_sided=True, unpremultiply=None, colors=None, resolution=128,
+                                num_blocks=16, relax_ratio=1.5):
+        """{"texture": [T, T, 3] float32, "count": [T, T] int32, "weight_sum": [T, T], "uv": [F, 3, 2], "cell": c}: the texture of the
+        mesh (vertices [V, 3] float32 world coordinates, faces [F, 3] int32, on the GPU) baked from what `cameras` see — the way
+        the reference's exporter textures its mesh, gathered per texel instead of scattered and inpainted.  The views are projected
+        onto the atlas of bake_texture by utils.texture.project_views behind the visibility of utils.texture.visible_depth; a texel
+        that at least one view passes (count > 0) is color_sum / weight_sum, the views blended by cos^2 of the viewing angle; every
+        other texel is bake_texture's value, bit for bit (`colors`, resolution, num_blocks, relax_ratio are that method's).
+        images=None: the Gaussians are rendered here with render_views over a black background (camera by camera when
+        pipe.convert_SHs_python forbids the batched call), the looked-up colour is divided by the looked-up alpha
+        (unpremultiply=None reads as True) and a view counts where that alpha is >= min_alpha.  images [K, 3, H, W] with optional
+        alphas [K, 1, H, W] (for example refined views with their cameras) skip the render; `pipe` may then be None and
+        unpremultiply=None reads as False.  depth_tolerance=None: one grid spacing of the extraction in world units.  min_cos,
+        min_alpha, two_sided: project_views'.  Raises like bake_texture and project_views."""
+        from ..utils import texture as tex
+        cams = list(cameras) if isinstance(cameras, (list, tuple)) else [cameras]
+        tex._view_size("bake_texture_from_views", cams)
+        if unpremultiply is None:
+            unpremultiply = images is None
+        if unpremultiply and not float(min_alpha) > 0:
+            raise ValueError("bake_texture_from_views: unpremultiply needs min_alpha > 0")
+        field = self.bake_texture(vertices, faces, texture_size, colors, resolution, num_blocks, relax_ratio)
+        T = int(field["texture"].shape[0])
+        dev = field["texture"].device
+        if images is None:
+            from ..renderer import render, render_views
+            if pipe is None:
+                raise ValueError("bake_texture_from_views needs `pipe` to render the views (or images=)")
+            bg = torch.zeros(3, dtype=torch.float32, device=dev)
+            if getattr(pipe, "convert_SHs_python", False):
+                pkgs = [render(c, self, pipe, bg) for c in cams]
+                images = torch.stack([p["render"] for p in pkgs])
+                alphas = torch.stack([p["alpha_3dgs"] for p in pkgs])
+            else:
+                from .._lib import GIP_MAX_VIEWS as step      # render_views' limit per call
+                pkgs = [render_views(cams[i:i + step], self, pipe, bg) for i in range(0, len(cams), step)]
+                images = torch.cat([p["render"] for p in pkgs])
+                alphas = torch.cat([p["alpha_3dgs"] for p in pkgs])
+            images, alphas = images.detach().float().contiguous(), alphas.detach().float().contiguous()
+        if depth_tolerance is None:
+            scale = float(self.scale) if self._field_sources() is not None else 1.0
+            depth_tolerance = 2.0 / max(int(resolution) - 1, 1) / scale
+        vertices, faces = vertices.detach().to(dev).contiguous(), faces.detach().to(dev).contiguous()
+        vis = tex.visible_depth(cams, vertices, faces, validate=False)       # bake_texture has checked the indices
+        out = tex.project_views(vertices, faces, T, cams, images, vis, depth_tolerance=depth_tolerance, alphas=alphas, min_cos=min_cos,
+                                min_alpha=min_alpha, two_sided=two_sided, unpremultiply=unpremultiply)
+        seen = (out["count"] > 0).unsqueeze(2)
+        texture = torch.where(seen, out["color_sum"] / out["weight_sum"].clamp_min(torch.finfo(torch.float32).tiny).unsqueeze(2),
+                              field["texture"])
+        return {"texture": texture, "count": out["count"], "weight_sum": out["weight_sum"], "uv": out["uv"], "cell": out["cell"]}
+
+    @torch.no_grad()
     def extract_textured_mesh(self, path=None, density_thresh=1.0, resolution=128, num_blocks=16, relax_ratio=1.5, texture_size=None,
-                              colors=None, *, clean=False, min_faces=8, min_diameter=0.05, decimate_target=0):
+                              colors=None, *, clean=False, min_faces=8, min_diameter=0.05, decimate_target=0, bake="field", cameras=None,
+                              pipe=None, **view_kwargs):
         """(vertices [V, 3], faces [F, 3] int32, normals [V, 3], uv [F, 3, 2], texture [T, T, 3]): the mesh and normals of
         extract_mesh_with_attributes, bit for bit, with bake_texture's atlas and texture in place of vertex colours — the reference's
         export_obj_with_mtl (threestudio/models/exporters/mesh_exporter.py:53-137) without its third-party unwrapping, rasterising
         and inpainting.  With path = dir/name.obj it writes name.obj, name.mtl and name_kd.png (utils.mesh.write_obj_textured).
         clean, min_faces, min_diameter, decimate_target: extract_mesh_with_attributes'; the texture is baked on the cleaned and
-        decimated mesh (fewer faces: larger atlas cells at the same texture size), and the files follow it."""
+        decimated mesh (fewer faces: larger atlas cells at the same texture size), and the files follow it.
+        bake="views": the texture is bake_texture_from_views' from `cameras` (ValueError without any) with `pipe` and the further
+        keywords of that method (images, alphas, depth_tolerance, min_cos, min_alpha, two_sided, unpremultiply); the default
+        bake="field" takes none of them."""
         from ..utils import mesh
+        if bake not in ("field", "views"):
+            raise ValueError("extract_textured_mesh: bake must be 'field' or 'views', not %r" % (bake,))
+        if bake == "views" and (cameras is None or (isinstance(cameras, (list, tuple)) and len(cameras) == 0)):
+            raise ValueError("extract_textured_mesh: bake='views' needs cameras")
+        if bake == "field" and (cameras is not None or pipe is not None or view_kwargs):
+            raise ValueError("extract_textured_mesh: cameras, pipe and %s belong to bake='views'" % (sorted(view_kwargs) or "its keywords"))
         vertices, faces, normals, _ = self.extract_mesh_with_attributes(None, density_thresh, resolution, num_blocks, relax_ratio, colors,
                                                                         clean=clean, min_faces=min_faces, min_diameter=min_diameter,
                                                                         decimate_target=decimate_target)
-        baked = self.bake_texture(vertices, faces, texture_size, colors, resolution, num_blocks, relax_ratio)
+        if bake == "views":
+            baked = self.bake_texture_from_views(vertices, faces, cameras, pipe, texture_size, colors=colors, resolution=resolution,
+                                                 num_blocks=num_blocks, relax_ratio=relax_ratio, **view_kwargs)
+        else:
+            baked = self.bake_texture(vertices, faces, texture_size, colors, resolution, num_blocks, relax_ratio)
         if path is not None:
             os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
             mesh.write_obj_textured(path, vertices, faces, baked["uv"], baked["texture"], normals=normals)

@@ -1,4 +1,5 @@
-"""The UV atlas of a baked texture (csrc/texture.hip, GaussianModel.bake_texture) and an 8-bit RGB PNG writer / reader.
+"""The UV atlas of a baked texture (csrc/texture.hip, GaussianModel.bake_texture), the projection of rendered views onto it
+(csrc/texture_project.hip: visible_depth, project_views) and an 8-bit RGB PNG writer / reader.
 
 The atlas is a pure function of the number of faces F and the texture size T; no unwrapping library is involved.  Every face owns a
 right-isosceles triangle of texels, two faces share a square cell:
@@ -81,6 +82,125 @@ def texel_points(vertices_normalised, faces, size):
     leg = torch.full((li.shape[0],), float(b), dtype=torch.float32, device=v.device)      # a tensor: a true division, as the kernel's
     a, bb = (li.float() / leg).unsqueeze(1), (lj.float() / leg).unsqueeze(1)
     return v0 + a * (v1 - v0) + bb * (v2 - v0), face, x, y
+
+
+# ---------------------------------------------------------------------------------------------------------------- views
+MAX_VIEWS = 64            # gip_texture_project's limit
+VIEW_FLOATS = 20          # a row of the view table: full_proj_transform (16, row-major, row-vector convention), camera_center (3), pad
+
+
+def pack_views(cameras, device=None):
+    """[K, 20] float32: the view table of gip_texture_project, one row per camera (its full_proj_transform, its camera_center, 0)."""
+    rows = []
+    for cam in cameras:
+        m = torch.as_tensor(cam.full_proj_transform).detach().float().reshape(-1)
+        c = torch.as_tensor(cam.camera_center).detach().float().reshape(-1)
+        if m.numel() != 16 or c.numel() != 3:
+            raise ValueError("pack_views: a camera needs a 4 x 4 full_proj_transform and a camera_center of 3 values")
+        dev = m.device if device is None else device
+        rows.append(torch.cat((m.to(dev), c.to(dev), torch.zeros(1, dtype=torch.float32, device=dev))))
+    if not rows:
+        raise ValueError("pack_views needs at least one camera")
+    return torch.stack(rows).contiguous()
+
+
+def _view_size(what, cameras):
+    """(K, H, W) of a list of cameras that share an image size; ValueError for K outside 1 .. 64."""
+    cams = list(cameras) if isinstance(cameras, (list, tuple)) else [cameras]
+    K = len(cams)
+    if not 1 <= K <= MAX_VIEWS:
+        raise ValueError("%s takes 1 .. %d views, not %d" % (what, MAX_VIEWS, K))
+    H, W = int(cams[0].image_height), int(cams[0].image_width)
+    if any((int(c.image_height), int(c.image_width)) != (H, W) for c in cams):
+        raise ValueError("%s: the cameras must share an image size" % what)
+    if H < 1 or W < 1 or H > 16384 or W > 16384:
+        raise ValueError("%s: the image size must lie in 1 .. 16384" % what)
+    return cams, K, H, W
+
+
+def _mesh_tensors(what, vertices, faces):
+    if not (isinstance(vertices, torch.Tensor) and vertices.is_cuda and vertices.dtype == torch.float32 and vertices.dim() == 2 and
+            vertices.shape[1] == 3):
+        raise ValueError("%s needs a [V, 3] float32 GPU tensor of vertices" % what)
+    if not (isinstance(faces, torch.Tensor) and faces.is_cuda and faces.dtype == torch.int32 and faces.dim() == 2 and
+            faces.shape[1] == 3 and faces.device == vertices.device):
+        raise ValueError("%s needs an [F, 3] int32 GPU tensor of faces on the vertices' device" % what)
+    return vertices.detach().contiguous(), faces.detach().contiguous()
+
+
+@torch.no_grad()
+def visible_depth(cameras, vertices, faces, validate=True):
+    """[K, H, W] float32: the clip-space w of the mesh surface (vertices [V, 3] float32 world coordinates, faces [F, 3] int32, on the
+    GPU) visible at every pixel centre of every camera, 0 where nothing is drawn: the mesh rasterizer's visibility, then the per-view
+    clip w interpolated as a one-channel attribute (perspective-correct interpolation reproduces w exactly on a plane).  What
+    project_views tests a texel's own w against.  Two calls into the library."""
+    from .rasterize import MeshRasterizerContext
+    cams, K, H, W = _view_size("visible_depth", cameras)
+    vertices, faces = _mesh_tensors("visible_depth", vertices, faces)
+    dev = vertices.device
+    if faces.shape[0] == 0 or vertices.shape[0] == 0:
+        return torch.zeros((K, H, W), dtype=torch.float32, device=dev)
+    mvp = torch.stack([c.full_proj_transform.to(dev).float() for c in cams])               # [K, 4, 4], row-vector convention
+    pos = torch.matmul(torch.cat((vertices, torch.ones_like(vertices[:, :1])), 1)[None], mvp).contiguous()
+    ctx = MeshRasterizerContext(device=dev)
+    rast, _ = ctx.rasterize(pos, faces, (H, W), validate=validate)
+    w, _ = ctx.interpolate(pos[..., 3:4].contiguous(), rast, faces)
+    return w[..., 0].contiguous()
+
+
+@torch.no_grad()
+def project_views(vertices, faces, texture_size, cameras, images, vis_depth, *, depth_tolerance, alphas=None, min_cos=0.2, min_alpha=0.5,
+                  two_sided=True, unpremultiply=False):
+    """{"color_sum": [T, T, 3], "weight_sum": [T, T], "count": [T, T] int32, "uv": [F, 3, 2], "cell": c}: the K `images` ([K, 3, H, W]
+    float32, render_views' layout, with `alphas` [K, 1, H, W], ones if omitted) of `cameras` projected onto the atlas of the mesh
+    (vertices [V, 3] float32 in world coordinates, faces [F, 3] int32, on the GPU).  csrc/texture_project.hip states the definition:
+    a texel takes a view when its point projects inside the image, lies no further than depth_tolerance (clip w, world units for a
+    camera of this project) behind vis_depth ([K, H, W], visible_depth's result) there, is seen at cos >= min_cos (|cos| when
+    two_sided) and the bilinear lookup of the view's alpha is >= min_alpha; the view weighs cos^2.  unpremultiply divides the
+    looked-up colour by the looked-up alpha (for renders over a black background) and needs min_alpha > 0.  The sums are raw:
+    colour = color_sum / weight_sum where count > 0.  Unowned texels stay 0.  One host read (the faces' index range) and exactly one
+    call of gip_texture_project.  ValueError for K outside 1 .. 64, tensors of the wrong dtype, device or shape, cameras of different
+    sizes, faces that do not fit the texture or index outside [0, V)."""
+    import ctypes
+
+    from .. import _lib
+    cams, K, H, W = _view_size("project_views", cameras)
+    min_alpha, min_cos, depth_tolerance = float(min_alpha), float(min_cos), float(depth_tolerance)
+    if unpremultiply and not min_alpha > 0:
+        raise ValueError("project_views: unpremultiply needs min_alpha > 0 (the colour is divided by the alpha)")
+    if not depth_tolerance >= 0:
+        raise ValueError("project_views: depth_tolerance must be >= 0")
+    vertices, faces = _mesh_tensors("project_views", vertices, faces)
+    dev = vertices.device
+
+    def on_device(t, shape, what):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == dev and t.dtype == torch.float32 and tuple(t.shape) == shape):
+            raise ValueError("project_views: %s must be a float32 tensor of shape %s on the vertices' device" % (what, list(shape)))
+        return t.detach()
+    images = on_device(images, (K, 3, H, W), "images")
+    vis_depth = on_device(vis_depth, (K, H, W), "vis_depth").contiguous()
+    alphas = torch.ones((K, 1, H, W), dtype=torch.float32, device=dev) if alphas is None else on_device(alphas, (K, 1, H, W), "alphas")
+    V, F, T = int(vertices.shape[0]), int(faces.shape[0]), int(texture_size)
+    if T < 4 or T > 16384:
+        raise ValueError("project_views: texture_size must lie in 4 .. 16384")
+    c, _, _ = atlas_layout(F, T)
+    out = {"color_sum": torch.zeros((T, T, 3), dtype=torch.float32, device=dev), "weight_sum": torch.zeros((T, T), dtype=torch.float32, device=dev),
+           "count": torch.zeros((T, T), dtype=torch.int32, device=dev), "uv": torch.from_numpy(atlas_uv(F, T)).to(dev), "cell": c}
+    if F == 0:
+        return out
+    lo, hi = (int(x) for x in torch.stack((faces.min(), faces.max())).cpu())      # the one host read
+    if lo < 0 or hi >= V:
+        raise ValueError("project_views: face indices must lie in [0, %d)" % V)
+    packed = torch.cat((images, alphas), 1).permute(0, 2, 3, 1).contiguous()      # [K, H, W, 4]: a bilinear tap is one 16-byte load
+    table = pack_views(cams, dev)
+    p = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+    with torch.cuda.device(dev):
+        rc = _lib.model_lib().gip_texture_project(p(vertices), V, p(faces), F, T, c, K, p(table), p(packed), p(vis_depth), H, W, depth_tolerance,
+                                                  min_cos, min_alpha, int(bool(two_sided)), int(bool(unpremultiply)), p(out["color_sum"]),
+                                                  p(out["weight_sum"]), p(out["count"]), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    if rc != 0:
+        raise RuntimeError("gip_texture_project failed with status %d" % rc)
+    return out
 
 
 # ---------------------------------------------------------------------------------------------------------------- PNG

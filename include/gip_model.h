@@ -185,6 +185,28 @@ int gip_texture_bake(const float* xyz, const float* opacity, const float* scalin
                      const float* vertices, int64_t V, const int32_t* faces, int64_t F, const int32_t* face_order,
                      const int32_t* block_start, int32_t T, int32_t cell, int32_t slices, void* workspace, size_t workspace_bytes,
                      float* density, float* color_sum, void* stream);
+/* Rendered views projected onto the same atlas (csrc/texture_project.hip, whose header states the definition with its float32
+ * operand order): the other source of a texture's colours, what a camera sees instead of the field's volumetric blend.
+ *   gip_texture_project  for every owned texel of a T x T texture, at the point p of gip_texture_bake's formula on vertices [V, 3] in
+ *       WORLD coordinates (faces [F, 3] int32), and for the views k = 0 .. K - 1 in that order (1 <= K <= 64; views [K, 20]: the
+ *       camera's full_proj_transform, 16 values in the row-vector convention clip = (p, 1) M, its camera_center, one pad):
+ *           skip unless clip w > 0;   (sx, sy) = ((x / w) 0.5 + 0.5) W, ((y / w) 0.5 + 0.5) H, pixel (ix, iy) has its centre at
+ *           (ix + 0.5, iy + 0.5);   skip unless 0 <= sx < W and 0 <= sy < H;   wp = vis_depth[k, floor(sy), floor(sx)] (vis_depth
+ *           [K, H, W]: the clip w of the mesh surface visible at each pixel centre, <= 0 where nothing is drawn): skip unless wp > 0
+ *           and w - wp <= depth_tolerance;   cos of the angle between the face's normal (v1 - v0) x (v2 - v0) and camera_center - p,
+ *           its absolute value when two_sided: skip unless cos >= min_cos (a face with a zero normal contributes nothing);   the
+ *           bilinear lookup of images[k] ([K, H, W, 4] interleaved r, g, b, a; 16-byte aligned) at (sx - 0.5, sy - 0.5), indices
+ *           clamped: skip unless a >= min_alpha;   unpremultiply: rgb / a;
+ *           weight_sum [T, T] += cos^2     color_sum [T, T, 3] += cos^2 * rgb     count [T, T] int32 += 1
+ *       Owned texels are written (zeros when no view passes), unowned ones are not: the caller zero-fills all three.  One lane per
+ *       texel, no atomics: two runs are bitwise equal.  F == 0 is a successful no-op.  No workspace, no host read.
+ * Status 1: K outside 1 .. 64, T < 4 or T > 16384, cell < 4, cell > T or 2 (T / cell)^2 < F, H or W outside 1 .. 16384, F or V above
+ * 2^31 - 1, a NULL pointer, faces without vertices, images not 16-byte aligned, unpremultiply with min_alpha <= 0.  Status 3: a
+ * launch error. */
+int gip_texture_project(const float* vertices, int64_t V, const int32_t* faces, int64_t F, int32_t T, int32_t cell, int32_t K,
+                        const float* views, const float* images, const float* vis_depth, int32_t H, int32_t W, float depth_tolerance,
+                        float min_cos, float min_alpha, int32_t two_sided, int32_t unpremultiply, float* color_sum, float* weight_sum,
+                        int32_t* count, void* stream);
 /* Rendering the textured mesh (csrc/mesh_raster.hip, whose header states the definition of coverage, visibility, interpolation and
  * lookup; gaussianip_amd/utils/rasterize.py).  All tensors float32 and contiguous, indices int32, everything on the device.
  *   gip_mesh_rasterize  pos [B, V, 4] clip space, tri [F, 3], one topology for all views -> rast [B, H, W, 4] = (u, v, depth z/w,

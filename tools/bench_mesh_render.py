@@ -16,7 +16,13 @@ and the share of the HBM roofline that makes: those bytes over the time, over 8.
 events: gip_mesh_rast_db, the build of the mip stack of a 4096 x 4096 x 3 texture, gip_mesh_texture_mip forward and backward (the
 backward with its fold), and beside them the bilinear gip_mesh_texture forward and backward at the same uv as the yardstick.  The uv
 are per vertex (its x, y inside the mesh's bounding box), interpolated per pixel with their differentials:
-    python tools/bench_mesh_render.py --mip [--out profiles/mesh_mip.json]"""
+    python tools/bench_mesh_render.py --mip [--out profiles/mesh_mip.json]
+
+--texture-project times the bake of the texture from rendered views (csrc/texture_project.hip, GaussianModel.bake_texture_from_views) on
+the same cloud extracted at resolution 128, with 8 and with 32 orbit cameras at 1024 x 1024: render_views, visible_depth, the packing
+of the images and the view table, gip_texture_project itself (with the bytes it must move, from the shapes), and the field bake
+(GaussianModel.bake_texture) beside them:
+    python tools/bench_mesh_render.py --texture-project --iters 2 [--out profiles/texture_project.json]"""
 import argparse
 import csv
 import json
@@ -201,6 +207,81 @@ def measure_mip(args):
             "times": times, "derived": derived}
 
 
+PROJECT_RESOLUTION, PROJECT_VIEWS = 128, (8, 32)
+
+
+def measure_texture_project(args):
+    import ctypes
+
+    import sample_inputs
+    import scenes
+    from gaussianip_amd import _lib
+    from gaussianip_amd.arguments import PipelineParams
+    from gaussianip_amd.renderer import render_views
+    from gaussianip_amd.scene import Camera, GaussianModel
+    from gaussianip_amd.utils import texture as tex
+    from gaussianip_amd.utils.sh import C0
+    cl = sample_inputs.blob_cloud()
+    P = cl["xyz"].shape[0]
+    gm = GaussianModel(0)
+    gm._xyz, gm._opacity = torch.from_numpy(cl["xyz"]).cuda(), torch.from_numpy(cl["opacity"]).cuda()
+    gm._scaling, gm._rotation = torch.from_numpy(cl["scaling"]).cuda(), torch.from_numpy(cl["rotation"]).cuda()
+    gm._features_dc = ((torch.from_numpy(sample_inputs.colors(P, 9)).cuda() - 0.5) / C0).reshape(P, 1, 3).contiguous()
+    gm._features_rest = torch.zeros((P, 0, 3), device="cuda")
+    pipe, bg = PipelineParams(argparse.ArgumentParser()), torch.zeros(3, device="cuda")
+    kw = dict(resolution=PROJECT_RESOLUTION, num_blocks=16)
+    with torch.no_grad():
+        v, f = gm.extract_mesh(density_thresh=1.0, **kw)
+    F, V = int(f.shape[0]), int(v.shape[0])
+    T = gm._default_texture_size(F)
+    c = tex.atlas_layout(F, T)[0]
+    owned = int((tex.texel_owner(F, T) >= 0).sum())
+    tol = 2.0 / (PROJECT_RESOLUTION - 1) / float(gm.scale)
+    result = {"device": "%s (%s)" % (torch.cuda.get_device_name(0), torch.cuda.get_device_properties(0).gcnArchName),
+              "scene": "blob_cloud extracted at resolution %d: %d faces, texture %d (cell %d, %d owned texels); orbit cameras at %d x %d" % (
+                  PROJECT_RESOLUTION, F, T, c, owned, SIZE, SIZE),
+              "timing": "device events, median of %d windows of %d calls after %d warm-up windows, ms per call" % (args.windows, args.iters, args.warmup),
+              "field_bake": windows(lambda: gm.bake_texture(v, f, T, **kw), args.iters, args.windows, args.warmup)}
+    lib = _lib.model_lib()
+    p = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+    for K in PROJECT_VIEWS:
+        cams = [Camera(c2w=scenes.orbit_c2w(15.0 if i % 2 else -15.0, -180.0 + 360.0 * i / K, 1.6).cuda(), FoVy=math.radians(50.0), height=SIZE,
+                       width=SIZE) for i in range(K)]
+
+        def render_all():
+            with torch.no_grad():
+                pkgs = [render_views(cams[i:i + _lib.GIP_MAX_VIEWS], gm, pipe, bg) for i in range(0, K, _lib.GIP_MAX_VIEWS)]
+            return torch.cat([q["render"] for q in pkgs]).detach(), torch.cat([q["alpha_3dgs"] for q in pkgs]).detach()
+        images, alphas = render_all()
+        vis = tex.visible_depth(cams, v, f, validate=False)
+
+        def pack():
+            return torch.cat((images, alphas), 1).permute(0, 2, 3, 1).contiguous(), tex.pack_views(cams, v.device)
+        packed, table = pack()
+        sums = [torch.zeros((T, T, 3), device="cuda"), torch.zeros((T, T), device="cuda"), torch.zeros((T, T), dtype=torch.int32, device="cuda")]
+        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+        def kernel():
+            rc = lib.gip_texture_project(p(v), V, p(f), F, T, c, K, p(table), p(packed), p(vis), SIZE, SIZE, tol, 0.2, 0.5, 1, 1, p(sums[0]), p(sums[1]),
+                                         p(sums[2]), stream)
+            assert rc == 0, rc
+        kernel()
+        covered = int((vis > 0).sum())
+        need = owned * 20 + F * 12 + V * 12 + K * 80 + covered * 20
+        entry = {"render_views": windows(render_all, args.iters, args.windows, args.warmup),
+                 "visible_depth": windows(lambda: tex.visible_depth(cams, v, f, validate=False), args.iters, args.windows, args.warmup),
+                 "pack": windows(pack, args.iters, args.windows, args.warmup),
+                 "gip_texture_project": windows(kernel, args.iters, args.windows, args.warmup),
+                 "bake_texture_from_views": windows(lambda: gm.bake_texture_from_views(v, f, cams, pipe, T, **kw), args.iters, args.windows, args.warmup),
+                 "texels_seen": int((sums[2] > 0).sum()), "texels_owned": owned, "covered_pixels": covered,
+                 "kernel_required_bytes": need,
+                 "kernel_required_bytes_note": "20 bytes written per owned texel, the faces and vertices once, the view table, and 20 bytes "
+                                               "(one 16-byte tap and one depth) per covered pixel of every view; neighbouring taps come from cache"}
+        entry["kernel_share_of_hbm_peak"] = need / (entry["gip_texture_project"]["median_ms"] * 1e-3) / HBM_PEAK
+        result["views_%d" % K] = entry
+    return result
+
+
 def merge_kernel_stats(result, path):
     """Per-kernel average times of a `rocprofv3 --kernel-trace --stats` run of `--once`, with the bytes each kernel must move."""
     need = required_bytes(result["counts"])
@@ -231,11 +312,15 @@ def main():
     ap.add_argument("--once", type=int, default=0)
     ap.add_argument("--kernel-stats", default=None)
     ap.add_argument("--mip", action="store_true", help="time the pieces of MipMeshRasterizerContext instead")
+    ap.add_argument("--texture-project", action="store_true", help="time the bake of the texture from rendered views instead")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "mesh_mip.json" if args.mip else "mesh_render.json")
-    if args.mip:
+        args.out = os.path.join(ROOT, "profiles", "texture_project.json" if args.texture_project else "mesh_mip.json" if args.mip else "mesh_render.json")
+    if args.texture_project:
+        assert torch.cuda.is_available(), "bench_mesh_render needs a GPU"
+        result = measure_texture_project(args)
+    elif args.mip:
         assert torch.cuda.is_available(), "bench_mesh_render needs a GPU"
         result = measure_mip(args)
     elif args.kernel_stats:
