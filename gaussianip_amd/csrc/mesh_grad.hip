@@ -71,20 +71,12 @@ mesh_rasterize_backward_kernel(const float* __restrict__ pos, const int32_t* __r
   if (g >= (int64_t)B * H * W) return;
   const int f = (int)rast[g].w - 1;
   if (f < 0 || f >= F) return;
-  const int b = (int)(g / ((int64_t)H * W));
-  const int pix = (int)(g - (int64_t)b * H * W), py = pix / W, px = pix - py * W;
-  const float* view = pos + (int64_t)b * V * 4;
+  const MrPixel p = mr_pixel(g, H, W);
   MrTri t;
-  if (!mr_load(view, tri, f, V, H, W, 0, t)) return;
+  if (!mr_load(pos + (int64_t)p.b * V * 4, tri, f, V, H, W, 0, t)) return;
   const float4 go = g_rast[g];
-  const int i0 = tri[(int64_t)f * 3], i1 = tri[(int64_t)f * 3 + 1], i2 = tri[(int64_t)f * 3 + 2];
-  const float4 p0 = ((const float4*)view)[i0], p1 = ((const float4*)view)[i1], p2 = ((const float4*)view)[i2];
-  int64_t e0, e1, e2;
-  mr_edges(t, 256 * px + 128, 256 * py + 128, e0, e1, e2);
-  float b0, b1, b2;
-  mr_weights(t, e0, e1, e2, b0, b1, b2);
-  const float q0 = b0 / t.w0, q1 = b1 / t.w1, q2 = b2 / t.w2;
-  const float S = (q0 + q1) + q2;
+  const MrPersp w = mr_persp(t, p.px, p.py);
+  const float b0 = w.b0, b1 = w.b1, b2 = w.b2, q0 = w.q0, q1 = w.q1, q2 = w.q2, S = w.S;
   const float u = q0 / S, v = q1 / S;
   const float k = go.x * u + go.y * v;
   const float gq0 = (go.x - k) / S, gq1 = (go.y - k) / S, gq2 = -k / S;
@@ -92,10 +84,10 @@ mesh_rasterize_backward_kernel(const float* __restrict__ pos, const int32_t* __r
   const float sc = 256.f * (float)t.sgn / (float)t.area;
   const float Gx = ((gb0 * (float)(t.Y1 - t.Y2) + gb1 * (float)(t.Y2 - t.Y0)) + gb2 * (float)(t.Y0 - t.Y1)) * sc;
   const float Gy = ((gb0 * (float)(t.X2 - t.X1) + gb1 * (float)(t.X0 - t.X2)) + gb2 * (float)(t.X1 - t.X0)) * sc;
-  float* out = g_pos + (int64_t)b * V * 4;
-  mg_add(out, i0, p0, -b0 * Gx, -b0 * Gy, go.z * b0 / t.w0, -(gq0 * q0 + go.z * b0 * t.zw0) / t.w0, H, W);
-  mg_add(out, i1, p1, -b1 * Gx, -b1 * Gy, go.z * b1 / t.w1, -(gq1 * q1 + go.z * b1 * t.zw1) / t.w1, H, W);
-  mg_add(out, i2, p2, -b2 * Gx, -b2 * Gy, go.z * b2 / t.w2, -(gq2 * q2 + go.z * b2 * t.zw2) / t.w2, H, W);
+  float* out = g_pos + (int64_t)p.b * V * 4;
+  mg_add(out, t.i0, t.p0, -b0 * Gx, -b0 * Gy, go.z * b0 / t.w0, -(gq0 * q0 + go.z * b0 * t.zw0) / t.w0, H, W);
+  mg_add(out, t.i1, t.p1, -b1 * Gx, -b1 * Gy, go.z * b1 / t.w1, -(gq1 * q1 + go.z * b1 * t.zw1) / t.w1, H, W);
+  mg_add(out, t.i2, t.p2, -b2 * Gx, -b2 * Gy, go.z * b2 / t.w2, -(gq2 * q2 + go.z * b2 * t.zw2) / t.w2, H, W);
 }
 
 // ------------------------------------------------------------------------------------------------------------------ values -> rast
@@ -131,23 +123,15 @@ mesh_shade_backward_rast_kernel(const float4* __restrict__ rast, const float* __
   if (f >= 0 && f < F) {
     const float4 go = g_shaded[g];
     const float gc[3] = {go.x, go.y, go.z};
-    const float* a = uv + (int64_t)f * 6;
-    const float w = (1.f - r.x) - r.y;
-    const float v0 = flip_v ? 1.f - a[1] : a[1], v1 = flip_v ? 1.f - a[3] : a[3], v2 = flip_v ? 1.f - a[5] : a[5];
-    const MrBil q = mr_bilinear(mr_interp(r.x, r.y, w, a[0], a[2], a[4]), mr_interp(r.x, r.y, w, v0, v1, v2), Th, Tw);
-    const int64_t o00 = ((int64_t)q.y0 * Tw + q.x0) * 3, o01 = ((int64_t)q.y0 * Tw + q.x1) * 3, o10 = ((int64_t)q.y1 * Tw + q.x0) * 3,
-                  o11 = ((int64_t)q.y1 * Tw + q.x1) * 3;
+    const MrShade h = mr_shade(r, uv, f, flip_v);
+    const MrTap q = mr_tap(h.s, h.t, Th, Tw, 3, 0);
     float gs = 0.f, gt = 0.f;
 #pragma unroll
-    for (int c = 0; c < 3; c++) {
-      const float t00 = tex[o00 + c], t01 = tex[o01 + c], t10 = tex[o10 + c], t11 = tex[o11 + c];
-      gs += gc[c] * ((1.f - q.fy) * (t01 - t00) + q.fy * (t11 - t10));
-      gt += gc[c] * ((1.f - q.fx) * (t10 - t00) + q.fx * (t11 - t01));
-    }
+    for (int c = 0; c < 3; c++) mr_tap_slopes(q, tex, c, gc[c], gs, gt);
     gs *= (float)Tw;
     gt *= (float)Th;      // the gradient to the interpolated t, which is built from the flipped v
-    out.x = gs * (a[0] - a[4]) + gt * (v0 - v2);
-    out.y = gs * (a[2] - a[4]) + gt * (v1 - v2);
+    out.x = gs * (h.a[0] - h.a[4]) + gt * (h.v0 - h.v2);
+    out.y = gs * (h.a[2] - h.a[4]) + gt * (h.v1 - h.v2);
   }
   g_rast[g] = out;
 }
@@ -209,18 +193,17 @@ __device__ __forceinline__ void mg_pair(const float* __restrict__ view, const in
             C2 = axis ? T.X2 : T.Y2;
   const int na = (axis ? ay : ax) + (n_is_a ? 0 : 1), cr = axis ? ax : ay;
   const int Cn = 256 * na + 128, Cr = 256 * cr + 128;
-  const int i0 = tri[(int64_t)f * 3], i1 = tri[(int64_t)f * 3 + 1], i2 = tri[(int64_t)f * 3 + 2];
   const int32_t* nb = topo + (int64_t)f * 3;
   float t, lam, m;
   if (mg_edge(view, V, H, W, axis, nb[0], A1, C1, A2, C2, A0, C0, Cn, Cr, s, t, lam, m)) {
-    h.iP = i1;
-    h.iQ = i2;
+    h.iP = T.i1;
+    h.iQ = T.i2;
   } else if (mg_edge(view, V, H, W, axis, nb[1], A2, C2, A0, C0, A1, C1, Cn, Cr, s, t, lam, m)) {
-    h.iP = i2;
-    h.iQ = i0;
+    h.iP = T.i2;
+    h.iQ = T.i0;
   } else if (mg_edge(view, V, H, W, axis, nb[2], A0, C0, A1, C1, A2, C2, Cn, Cr, s, t, lam, m)) {
-    h.iP = i0;
-    h.iQ = i1;
+    h.iP = T.i0;
+    h.iQ = T.i1;
   } else {
     return;
   }
@@ -266,14 +249,13 @@ mesh_antialias_kernel(const float* __restrict__ color, int C, const float4* __re
                       float* __restrict__ out) {
   const int64_t g = (int64_t)blockIdx.x * MR_THREADS + threadIdx.x;
   if (g >= (int64_t)B * H * W) return;
-  const int b = (int)(g / ((int64_t)H * W));
-  const int pix = (int)(g - (int64_t)b * H * W), py = pix / W, px = pix - py * W;
+  const MrPixel p = mr_pixel(g, H, W);
   MgHit h[4];
   int64_t other[4];
   bool mine[4];
   const float* cx = color + g * C;
   float* o = out + g * C;
-  if (!mg_pairs(pos + (int64_t)b * V * 4, tri, topo, rast, g, px, py, V, F, H, W, h, other, mine)) {
+  if (!mg_pairs(pos + (int64_t)p.b * V * 4, tri, topo, rast, g, p.px, p.py, V, F, H, W, h, other, mine)) {
     for (int c = 0; c < C; c++) o[c] = cx[c];
     return;
   }
@@ -293,14 +275,13 @@ mesh_antialias_backward_kernel(const float* __restrict__ color, int C, const flo
                                const float* __restrict__ g_out, float* __restrict__ g_color, float* __restrict__ g_pos) {
   const int64_t g = (int64_t)blockIdx.x * MR_THREADS + threadIdx.x;
   if (g >= (int64_t)B * H * W) return;
-  const int b = (int)(g / ((int64_t)H * W));
-  const int pix = (int)(g - (int64_t)b * H * W), py = pix / W, px = pix - py * W;
+  const MrPixel p = mr_pixel(g, H, W);
   MgHit h[4];
   int64_t other[4];
   bool mine[4];
-  const float* view = pos + (int64_t)b * V * 4;
+  const float* view = pos + (int64_t)p.b * V * 4;
   const float* go = g_out + g * C;
-  if (!mg_pairs(view, tri, topo, rast, g, px, py, V, F, H, W, h, other, mine)) {
+  if (!mg_pairs(view, tri, topo, rast, g, p.px, p.py, V, F, H, W, h, other, mine)) {
     if (g_color)
       for (int c = 0; c < C; c++) g_color[g * C + c] = go[c];
     return;
@@ -316,7 +297,7 @@ mesh_antialias_backward_kernel(const float* __restrict__ color, int C, const flo
     }
   }
   if (!g_pos) return;
-  float* gp = g_pos + (int64_t)b * V * 4;
+  float* gp = g_pos + (int64_t)p.b * V * 4;
 #pragma unroll
   for (int k = 1; k < 4; k += 2) {      // the pairs in which this pixel is the first: right, down
     if (h[k].alpha == 0.f) continue;
@@ -339,13 +320,9 @@ mesh_antialias_backward_kernel(const float* __restrict__ color, int C, const flo
 }
 
 // ------------------------------------------------------------------------------------------------------------------ C-ABI
-static int mg_mesh_ok(int32_t B, int64_t V, int64_t F, int32_t H, int32_t W) {
-  return mr_image_ok(B, H, W) && V >= 0 && V <= INT32_MAX && F >= 0 && F <= MR_MAX_FACES;
-}
-
 extern "C" int gip_mesh_rasterize_backward(const float* pos, const int32_t* tri, int32_t B, int64_t V, int64_t F, int32_t H, int32_t W,
                                            const float* rast, const float* g_rast, float* g_pos, void* stream) {
-  if (!mg_mesh_ok(B, V, F, H, W) || !rast || !g_rast) return 1;
+  if (!mr_mesh_ok(B, V, F, H, W) || !rast || !g_rast) return 1;
   if (F == 0 || V == 0) return 0;
   if (!pos || !tri || !g_pos) return 1;
   const int64_t pixels = (int64_t)B * H * W;
@@ -357,13 +334,10 @@ extern "C" int gip_mesh_rasterize_backward(const float* pos, const int32_t* tri,
 extern "C" int gip_mesh_interpolate_backward_rast(const float* g_out, const float* attr, int32_t attr_batch, int64_t N, int32_t C,
                                                   const int32_t* idx, int64_t F, const float* rast, int32_t B, int32_t H, int32_t W,
                                                   float* g_rast, void* stream) {
-  if (!mr_image_ok(B, H, W) || (attr_batch != 1 && attr_batch != B) || N < 0 || N > INT32_MAX || C < 1 || F < 0 || F > MR_MAX_FACES ||
-      !rast || !g_out || !g_rast)
-    return 1;
-  if ((!idx && N != 3 * F) || N * C > INT32_MAX || (F > 0 && N > 0 && !attr)) return 1;
+  if (!mr_attr_ok(attr, attr_batch, N, C, idx, F, B, H, W) || !rast || !g_out || !g_rast) return 1;
   const int64_t pixels = (int64_t)B * H * W;
   hipLaunchKernelGGL(mesh_interpolate_backward_rast_kernel, dim3(mr_blocks(pixels)), dim3(MR_THREADS), 0, (hipStream_t)stream, g_out, attr,
-                     attr_batch == 1 ? (int64_t)0 : N * C, idx, (const float4*)rast, pixels, (int64_t)H * W, (int)F, (int)N, (int)C,
+                     mr_stride(attr_batch, N * C), idx, (const float4*)rast, pixels, (int64_t)H * W, (int)F, (int)N, (int)C,
                      (float4*)g_rast);
   return mr_done();
 }
@@ -380,7 +354,7 @@ extern "C" int gip_mesh_shade_backward_rast(const float* rast, const float* uv, 
 
 static int mg_antialias_ok(const float* color, int32_t C, const float* rast, const float* pos, const int32_t* tri, const int32_t* topo,
                            int32_t B, int64_t V, int64_t F, int32_t H, int32_t W) {
-  if (!mg_mesh_ok(B, V, F, H, W) || C < 1 || (int64_t)B * H * W * C > INT32_MAX || !color || !rast) return 0;
+  if (!mr_mesh_ok(B, V, F, H, W) || C < 1 || (int64_t)B * H * W * C > INT32_MAX || !color || !rast) return 0;
   return F == 0 || V == 0 || (pos && tri && topo);
 }
 

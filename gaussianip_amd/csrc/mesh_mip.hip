@@ -29,7 +29,7 @@
 //       R = sqrtf(0.25f * (D * D) + Cc * Cc),  m = 0.5f * (A + B) + R,  level = 0.5f * log2f(m) + bias
 //     (without uv_da: level = bias; without a bias: bias = 0).  lc = fminf(fmaxf(level, 0), L): a NaN counts as 0.
 //   * Trilinear: l0 = floorf(lc), f = lc - l0, l1 = min(l0 + 1, L), out = (1 - f) * bil_l0 + f * bil_l1 with bil_l the bilinear rule
-//     (mr_bilinear, mr_mix) on level l's sides; where f == 0 only level l0 is read and out = bil_l0 itself.  Mipmap-nearest:
+//     (mr_bilinear, mr_tap_mix) on level l's sides; where f == 0 only level l0 is read and out = bil_l0 itself.  Mipmap-nearest:
 //     l0 = min((int) floorf(lc + 0.5f), L), f = 0.
 //   * Gradients, per channel with upstream v: gv0 = (1 - f) * v and gv1 = f * v take the place of the upstream gradient in the
 //     bilinear rule's gradients at levels l0 and l1 (to the four texels: float atomic adds into a gradient stack of the same layout; to
@@ -63,20 +63,16 @@ mesh_rast_db_kernel(const float* __restrict__ pos, const int32_t* __restrict__ t
   float4 out = make_float4(0.f, 0.f, 0.f, 0.f);
   const int f = (int)r.w - 1;
   if (f >= 0 && f < F) {
-    const int b = (int)(g / ((int64_t)H * W));
-    const int pix = (int)(g - (int64_t)b * H * W), py = pix / W, px = pix - py * W;
+    const MrPixel p = mr_pixel(g, H, W);
     MrTri t;
-    if (mr_load(pos + (int64_t)b * V * 4, tri, f, V, H, W, 0, t)) {
-      int64_t e0, e1, e2;
-      mr_edges(t, 256 * px + 128, 256 * py + 128, e0, e1, e2);
-      float b0, b1, b2;
-      mr_weights(t, e0, e1, e2, b0, b1, b2);
+    if (mr_load(pos + (int64_t)p.b * V * 4, tri, f, V, H, W, 0, t)) {
+      const float S = mr_persp(t, p.px, p.py).S;
+      int64_t sx0, sy0, sx1, sy1, sx2, sy2;
+      mr_steps(t, sx0, sy0, sx1, sy1, sx2, sy2);
       const float fa = (float)t.area;
-      const float bx0 = (float)(-256 * (int64_t)(t.sgn * (t.Y2 - t.Y1))) / fa, by0 = (float)(256 * (int64_t)(t.sgn * (t.X2 - t.X1))) / fa;
-      const float bx1 = (float)(-256 * (int64_t)(t.sgn * (t.Y0 - t.Y2))) / fa, by1 = (float)(256 * (int64_t)(t.sgn * (t.X0 - t.X2))) / fa;
-      const float bx2 = (float)(-256 * (int64_t)(t.sgn * (t.Y1 - t.Y0))) / fa, by2 = (float)(256 * (int64_t)(t.sgn * (t.X1 - t.X0))) / fa;
-      const float q0 = b0 / t.w0, q1 = b1 / t.w1, q2 = b2 / t.w2;
-      const float S = (q0 + q1) + q2;
+      const float bx0 = (float)sx0 / fa, by0 = (float)sy0 / fa;
+      const float bx1 = (float)sx1 / fa, by1 = (float)sy1 / fa;
+      const float bx2 = (float)sx2 / fa, by2 = (float)sy2 / fa;
       const float qx0 = bx0 / t.w0, qx1 = bx1 / t.w1, qx2 = bx2 / t.w2;
       const float qy0 = by0 / t.w0, qy1 = by1 / t.w1, qy2 = by2 / t.w2;
       const float Sx = (qx0 + qx1) + qx2, Sy = (qy0 + qy1) + qy2;
@@ -259,25 +255,9 @@ __device__ __forceinline__ void mm_select(float level, int L, int nearest, int& 
   }
 }
 
-// the offsets (in floats, channel 0) of the four texels of a lookup at level l inside its buffer (tex for l == 0, mip above)
-struct MmTap {
-  MrBil q;
-  int64_t o00, o01, o10, o11;
-  int h, w;
-};
-
-__device__ __forceinline__ MmTap mm_tap(float2 st, int Th, int Tw, int l, int C, int64_t tex_base, int64_t mip_base) {
-  const MmLevel lv = mm_level(Th, Tw, l);
-  MmTap t;
-  t.h = lv.h;
-  t.w = lv.w;
-  t.q = mr_bilinear(st.x, st.y, lv.h, lv.w);
-  const int64_t base = l == 0 ? tex_base : mip_base + lv.off * C;
-  t.o00 = base + ((int64_t)t.q.y0 * lv.w + t.q.x0) * C;
-  t.o01 = base + ((int64_t)t.q.y0 * lv.w + t.q.x1) * C;
-  t.o10 = base + ((int64_t)t.q.y1 * lv.w + t.q.x0) * C;
-  t.o11 = base + ((int64_t)t.q.y1 * lv.w + t.q.x1) * C;
-  return t;
+// the lookup at level l, which is lv, inside its buffer (tex for l == 0, mip above)
+__device__ __forceinline__ MrTap mm_tap(float2 st, const MmLevel& lv, int l, int C, int64_t tex_base, int64_t mip_base) {
+  return mr_tap(st.x, st.y, lv.h, lv.w, C, l == 0 ? tex_base : mip_base + lv.off * C);
 }
 
 __global__ void __launch_bounds__(MR_THREADS)
@@ -292,18 +272,16 @@ mesh_texture_mip_kernel(const float* __restrict__ tex, int64_t tex_stride, const
   float f;
   mm_select(lod.level, L, nearest, l0, l1, f);
   const int64_t b = g / per_view;
-  const MmTap t0 = mm_tap(st, Th, Tw, l0, C, b * tex_stride, b * mip_stride);
+  const MrTap t0 = mm_tap(st, mm_level(Th, Tw, l0), l0, C, b * tex_stride, b * mip_stride);
   const float* p0 = l0 == 0 ? tex : mip;
   float* o = out + g * C;
   if (f == 0.f) {
-    for (int c = 0; c < C; c++) o[c] = mr_mix(t0.q, p0[t0.o00 + c], p0[t0.o01 + c], p0[t0.o10 + c], p0[t0.o11 + c]);
+    for (int c = 0; c < C; c++) o[c] = mr_tap_mix(t0, p0, c);
     return;
   }
-  const MmTap t1 = mm_tap(st, Th, Tw, l1, C, b * tex_stride, b * mip_stride);      // f != 0: l1 = l0 + 1 >= 1
+  const MrTap t1 = mm_tap(st, mm_level(Th, Tw, l1), l1, C, b * tex_stride, b * mip_stride);      // f != 0: l1 = l0 + 1 >= 1
   for (int c = 0; c < C; c++) {
-    const float v0 = mr_mix(t0.q, p0[t0.o00 + c], p0[t0.o01 + c], p0[t0.o10 + c], p0[t0.o11 + c]);
-    const float v1 = mr_mix(t1.q, mip[t1.o00 + c], mip[t1.o01 + c], mip[t1.o10 + c], mip[t1.o11 + c]);
-    o[c] = (1.f - f) * v0 + f * v1;
+    o[c] = (1.f - f) * mr_tap_mix(t0, p0, c) + f * mr_tap_mix(t1, mip, c);
   }
 }
 
@@ -324,43 +302,30 @@ mesh_texture_mip_backward_kernel(const float* __restrict__ tex, int64_t tex_stri
   const bool gate = !nearest && (g_uv_da || g_bias) && lod.level > 0.f && lod.level < (float)L;
   const bool second = f != 0.f || gate;      // then l1 = l0 + 1 <= L
   const int64_t b = g / per_view;
-  const MmTap t0 = mm_tap(st, Th, Tw, l0, C, b * tex_stride, b * mip_stride);
-  const MmTap t1 = mm_tap(st, Th, Tw, second ? l1 : l0, C, b * tex_stride, b * mip_stride);
+  const MmLevel v0 = mm_level(Th, Tw, l0), v1 = mm_level(Th, Tw, second ? l1 : l0);
+  const MrTap t0 = mm_tap(st, v0, l0, C, b * tex_stride, b * mip_stride);
+  const MrTap t1 = mm_tap(st, v1, second ? l1 : l0, C, b * tex_stride, b * mip_stride);
   const float* p0 = l0 == 0 ? tex : mip;
   float* a0 = l0 == 0 ? g_tex : g_mip;
   const float* go = g_out + g * C;
   const bool values = g_uv || gate;
   float gs0 = 0.f, gt0 = 0.f, gs1 = 0.f, gt1 = 0.f, dl = 0.f;
-  const float w00 = (1.f - t0.q.fy) * (1.f - t0.q.fx), w01 = (1.f - t0.q.fy) * t0.q.fx, w10 = t0.q.fy * (1.f - t0.q.fx), w11 = t0.q.fy * t0.q.fx;
-  const float x00 = (1.f - t1.q.fy) * (1.f - t1.q.fx), x01 = (1.f - t1.q.fy) * t1.q.fx, x10 = t1.q.fy * (1.f - t1.q.fx), x11 = t1.q.fy * t1.q.fx;
   for (int c = 0; c < C; c++) {
     const float v = go[c];
     const float gv0 = (1.f - f) * v, gv1 = f * v;
     if (g_tex) {
-      atomicAdd(a0 + t0.o00 + c, w00 * gv0);
-      atomicAdd(a0 + t0.o01 + c, w01 * gv0);
-      atomicAdd(a0 + t0.o10 + c, w10 * gv0);
-      atomicAdd(a0 + t0.o11 + c, w11 * gv0);
-      if (f != 0.f) {
-        atomicAdd(g_mip + t1.o00 + c, x00 * gv1);
-        atomicAdd(g_mip + t1.o01 + c, x01 * gv1);
-        atomicAdd(g_mip + t1.o10 + c, x10 * gv1);
-        atomicAdd(g_mip + t1.o11 + c, x11 * gv1);
-      }
+      mr_tap_scatter(t0, a0, c, gv0);
+      if (f != 0.f) mr_tap_scatter(t1, g_mip, c, gv1);
     }
     if (values) {
-      const float t00 = p0[t0.o00 + c], t01 = p0[t0.o01 + c], t10 = p0[t0.o10 + c], t11 = p0[t0.o11 + c];
-      gs0 += gv0 * ((1.f - t0.q.fy) * (t01 - t00) + t0.q.fy * (t11 - t10));
-      gt0 += gv0 * ((1.f - t0.q.fx) * (t10 - t00) + t0.q.fx * (t11 - t01));
+      mr_tap_slopes(t0, p0, c, gv0, gs0, gt0);
       if (second) {
-        const float s00 = mip[t1.o00 + c], s01 = mip[t1.o01 + c], s10 = mip[t1.o10 + c], s11 = mip[t1.o11 + c];
-        gs1 += gv1 * ((1.f - t1.q.fy) * (s01 - s00) + t1.q.fy * (s11 - s10));
-        gt1 += gv1 * ((1.f - t1.q.fx) * (s10 - s00) + t1.q.fx * (s11 - s01));
-        if (gate) dl += v * (mr_mix(t1.q, s00, s01, s10, s11) - mr_mix(t0.q, t00, t01, t10, t11));
+        mr_tap_slopes(t1, mip, c, gv1, gs1, gt1);
+        if (gate) dl += v * (mr_tap_mix(t1, mip, c) - mr_tap_mix(t0, p0, c));
       }
     }
   }
-  if (g_uv) g_uv[g] = make_float2(gs0 * (float)t0.w + gs1 * (float)t1.w, gt0 * (float)t0.h + gt1 * (float)t1.h);
+  if (g_uv) g_uv[g] = make_float2(gs0 * (float)v0.w + gs1 * (float)v1.w, gt0 * (float)v0.h + gt1 * (float)v1.h);
   if (g_bias) g_bias[g] = dl;
   if (g_uv_da) {
     float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -383,11 +348,9 @@ mesh_texture_mip_backward_kernel(const float* __restrict__ tex, int64_t tex_stri
 }
 
 // ------------------------------------------------------------------------------------------------------------------ C-ABI
-static int mm_batch_ok(int32_t B, int32_t H, int32_t W, int32_t batch) { return mr_image_ok(B, H, W) && (batch == 1 || batch == B); }
-
 extern "C" int gip_mesh_rast_db(const float* pos, const int32_t* tri, int32_t B, int64_t V, int64_t F, int32_t H, int32_t W, const float* rast,
                                 float* rast_db, void* stream) {
-  if (!mr_image_ok(B, H, W) || V < 0 || V > INT32_MAX || F < 0 || F > MR_MAX_FACES || !rast || !rast_db) return 1;
+  if (!mr_mesh_ok(B, V, F, H, W) || !rast || !rast_db) return 1;
   hipStream_t st = (hipStream_t)stream;
   const int64_t pixels = (int64_t)B * H * W;
   if (F == 0 || V == 0) return hipMemsetAsync(rast_db, 0, (size_t)pixels * 16, st) == hipSuccess ? 0 : 3;
@@ -397,19 +360,18 @@ extern "C" int gip_mesh_rast_db(const float* pos, const int32_t* tri, int32_t B,
   return mr_done();
 }
 
-static int mm_attr_ok(int32_t attr_batch, int64_t N, int32_t C, const int32_t* idx, int64_t F, int32_t K, int32_t B, int32_t H, int32_t W) {
-  if (!mm_batch_ok(B, H, W, attr_batch) || N < 0 || N > INT32_MAX || C < 1 || F < 0 || F > MR_MAX_FACES || K < 1) return 0;
-  if ((!idx && N != 3 * F) || N * C > INT32_MAX || (int64_t)B * H * W * K * 2 > INT32_MAX) return 0;
-  return 1;
+static int mm_attr_ok(const float* rows, int32_t attr_batch, int64_t N, int32_t C, const int32_t* idx, int64_t F, int32_t K, int32_t B, int32_t H,
+                      int32_t W) {
+  return mr_attr_ok(rows, attr_batch, N, C, idx, F, B, H, W) && K >= 1 && (int64_t)B * H * W * K * 2 <= INT32_MAX;
 }
 
 extern "C" int gip_mesh_interpolate_da(const float* attr, int32_t attr_batch, int64_t N, int32_t C, const int32_t* idx, int64_t F,
                                        const float* rast, const float* rast_db, const int32_t* channels, int32_t K, int32_t B, int32_t H,
                                        int32_t W, float* out_da, void* stream) {
-  if (!mm_attr_ok(attr_batch, N, C, idx, F, K, B, H, W) || !rast || !rast_db || !out_da || (F > 0 && N > 0 && !attr)) return 1;
+  if (!mm_attr_ok(attr, attr_batch, N, C, idx, F, K, B, H, W) || !rast || !rast_db || !out_da) return 1;
   const int64_t pixels = (int64_t)B * H * W;
   hipLaunchKernelGGL(mesh_interpolate_da_kernel, dim3(mr_blocks(pixels)), dim3(MR_THREADS), 0, (hipStream_t)stream, attr,
-                     attr_batch == 1 ? (int64_t)0 : N * C, idx, (const float4*)rast, (const float4*)rast_db, channels, (int)K, pixels,
+                     mr_stride(attr_batch, N * C), idx, (const float4*)rast, (const float4*)rast_db, channels, (int)K, pixels,
                      (int64_t)H * W, (int)F, (int)N, (int)C, (float2*)out_da);
   return mr_done();
 }
@@ -417,7 +379,7 @@ extern "C" int gip_mesh_interpolate_da(const float* attr, int32_t attr_batch, in
 extern "C" int gip_mesh_interpolate_da_backward(const float* g_da, int32_t attr_batch, int64_t N, int32_t C, const int32_t* idx, int64_t F,
                                                 const float* rast, const float* rast_db, const int32_t* channels, int32_t K, int32_t B,
                                                 int32_t H, int32_t W, float* g_attr, void* stream) {
-  if (!mm_attr_ok(attr_batch, N, C, idx, F, K, B, H, W) || !rast || !rast_db || !g_da) return 1;
+  if (!mm_attr_ok(g_attr, attr_batch, N, C, idx, F, K, B, H, W) || !rast || !rast_db || !g_da) return 1;
   if (N == 0) return 0;
   if (!g_attr) return 1;
   hipStream_t st = (hipStream_t)stream;
@@ -425,7 +387,7 @@ extern "C" int gip_mesh_interpolate_da_backward(const float* g_da, int32_t attr_
   const int64_t pixels = (int64_t)B * H * W;
   hipLaunchKernelGGL(mesh_interpolate_da_backward_kernel, dim3(mr_blocks(pixels)), dim3(MR_THREADS), 0, st, (const float2*)g_da, idx,
                      (const float4*)rast, (const float4*)rast_db, channels, (int)K, pixels, (int64_t)H * W, (int)F, (int)N, (int)C, g_attr,
-                     attr_batch == 1 ? (int64_t)0 : N * C);
+                     mr_stride(attr_batch, N * C));
   return mr_done();
 }
 
@@ -483,11 +445,11 @@ extern "C" int gip_mesh_texture_mip(const float* tex, int32_t tex_batch, int32_t
                                     int64_t mip_texels, int32_t max_level, const float* uv, const float* uv_da, const float* bias,
                                     int32_t nearest, int32_t B, int32_t H, int32_t W, float* out, void* stream) {
   int L;
-  if (!mm_batch_ok(B, H, W, tex_batch) || !mm_stack_ok(tex_batch, Th, Tw, C, max_level, mip_texels, L) || !tex || !uv || !out) return 1;
+  if (!mr_batch_ok(B, H, W, tex_batch) || !mm_stack_ok(tex_batch, Th, Tw, C, max_level, mip_texels, L) || !tex || !uv || !out) return 1;
   if (L > 0 && !mip) return 1;
   const int64_t pixels = (int64_t)B * H * W;
   hipLaunchKernelGGL(mesh_texture_mip_kernel, dim3(mr_blocks(pixels)), dim3(MR_THREADS), 0, (hipStream_t)stream, tex,
-                     tex_batch == 1 ? (int64_t)0 : (int64_t)Th * Tw * C, mip, tex_batch == 1 ? (int64_t)0 : mip_texels * C, (const float2*)uv,
+                     mr_stride(tex_batch, (int64_t)Th * Tw * C), mip, mr_stride(tex_batch, mip_texels * C), (const float2*)uv,
                      (const float4*)uv_da, bias, pixels, (int64_t)H * W, (int)Th, (int)Tw, (int)C, L, (int)(nearest != 0), out);
   return mr_done();
 }
@@ -497,7 +459,7 @@ extern "C" int gip_mesh_texture_mip_backward(const float* tex, int32_t tex_batch
                                              int32_t nearest, const float* g_out, int32_t B, int32_t H, int32_t W, float* g_tex, float* g_mip,
                                              float* g_uv, float* g_uv_da, float* g_bias, void* stream) {
   int L;
-  if (!mm_batch_ok(B, H, W, tex_batch) || !mm_stack_ok(tex_batch, Th, Tw, C, max_level, mip_texels, L) || !tex || !uv || !g_out) return 1;
+  if (!mr_batch_ok(B, H, W, tex_batch) || !mm_stack_ok(tex_batch, Th, Tw, C, max_level, mip_texels, L) || !tex || !uv || !g_out) return 1;
   if ((L > 0 && !mip) || (g_tex && L > 0 && !g_mip) || (g_uv_da && !uv_da) || (g_bias && !bias)) return 1;
   if (!g_tex && !g_uv && !g_uv_da && !g_bias) return 0;
   hipStream_t st = (hipStream_t)stream;
@@ -505,7 +467,7 @@ extern "C" int gip_mesh_texture_mip_backward(const float* tex, int32_t tex_batch
   if (g_tex && L > 0 && hipMemsetAsync(g_mip, 0, (size_t)tex_batch * mip_texels * C * sizeof(float), st) != hipSuccess) return 3;
   const int64_t pixels = (int64_t)B * H * W;
   hipLaunchKernelGGL(mesh_texture_mip_backward_kernel, dim3(mr_blocks(pixels)), dim3(MR_THREADS), 0, st, tex,
-                     tex_batch == 1 ? (int64_t)0 : (int64_t)Th * Tw * C, mip, tex_batch == 1 ? (int64_t)0 : mip_texels * C, (const float2*)uv,
+                     mr_stride(tex_batch, (int64_t)Th * Tw * C), mip, mr_stride(tex_batch, mip_texels * C), (const float2*)uv,
                      (const float4*)uv_da, bias, g_out, pixels, (int64_t)H * W, (int)Th, (int)Tw, (int)C, L, (int)(nearest != 0), g_tex,
                      L > 0 ? g_mip : (float*)nullptr, (float2*)g_uv, (float4*)g_uv_da, g_bias);
   return mr_done();

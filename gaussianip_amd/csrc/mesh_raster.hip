@@ -41,7 +41,8 @@
 //                               for): not bit-reproducible.  No gradient reaches vertex positions.
 //   mesh_interpolate_kernel / mesh_interpolate_backward_kernel / mesh_texture_kernel / mesh_texture_backward_kernel: the unfused
 //                               pieces with any channel count.
-// The triangle set-up and the lookup's set-up live in mesh_raster_common.h, which mesh_grad.hip (gradients to positions, antialias) shares.
+// The triangle set-up (mr_load), the perspective weights (mr_persp), the lookup with its gradients (mr_tap*) and the fused shade's set-up
+// (mr_shade) live in mesh_raster_common.h, which mesh_grad.hip (gradients to positions, antialias) and mesh_mip.hip (mipmaps) share.
 #include "mesh_raster_common.h"
 
 #define MR_SMALL_MAX 64        // pixel centres in the bounding box up to which the setup lane rasterizes the triangle itself (tuning)
@@ -106,10 +107,8 @@ mesh_setup_kernel(const float* __restrict__ pos, const int32_t* __restrict__ tri
   mr_biases(t, c0, c1, c2);
   int64_t r0, r1, r2;
   mr_edges(t, 256 * x_lo + 128, 256 * y_lo + 128, r0, r1, r2);
-  // E(Px + 256, Py) - E(Px, Py) = -256 dy,  E(Px, Py + 256) - E(Px, Py) = 256 dx
-  const int64_t sx0 = -256 * (int64_t)(t.sgn * (t.Y2 - t.Y1)), sy0 = 256 * (int64_t)(t.sgn * (t.X2 - t.X1));
-  const int64_t sx1 = -256 * (int64_t)(t.sgn * (t.Y0 - t.Y2)), sy1 = 256 * (int64_t)(t.sgn * (t.X0 - t.X2));
-  const int64_t sx2 = -256 * (int64_t)(t.sgn * (t.Y1 - t.Y0)), sy2 = 256 * (int64_t)(t.sgn * (t.X1 - t.X0));
+  int64_t sx0, sy0, sx1, sy1, sx2, sy2;
+  mr_steps(t, sx0, sy0, sx1, sy1, sx2, sy2);
   mr_key* view = keys + (int64_t)b * H * W;
   for (int py = y_lo; py <= y_hi; py++) {
     int64_t e0 = r0, e1 = r1, e2 = r2;
@@ -163,19 +162,13 @@ mesh_resolve_kernel(const float* __restrict__ pos, const int32_t* __restrict__ t
   float4 out = make_float4(0.f, 0.f, 0.f, 0.f);
   const uint32_t f = (uint32_t)key;
   if (key != ~0ull && f < (uint32_t)F) {
-    const int b = (int)(g / ((int64_t)H * W));
-    const int pix = (int)(g - (int64_t)b * H * W), py = pix / W, px = pix - py * W;
+    const MrPixel p = mr_pixel(g, H, W);
     MrTri t;
-    if (mr_load(pos + (int64_t)b * V * 4, tri, (int)f, V, H, W, 0, t)) {
+    if (mr_load(pos + (int64_t)p.b * V * 4, tri, (int)f, V, H, W, 0, t)) {
       const uint32_t u = (uint32_t)(key >> 32);
       const float d = __uint_as_float((u & 0x80000000u) ? (u ^ 0x80000000u) : ~u);
-      int64_t e0, e1, e2;
-      mr_edges(t, 256 * px + 128, 256 * py + 128, e0, e1, e2);
-      float b0, b1, b2;
-      mr_weights(t, e0, e1, e2, b0, b1, b2);
-      const float q0 = b0 / t.w0, q1 = b1 / t.w1, q2 = b2 / t.w2;
-      const float den = (q0 + q1) + q2;
-      out = make_float4(q0 / den, q1 / den, d, (float)(f + 1));
+      const MrPersp w = mr_persp(t, p.px, p.py);
+      out = make_float4(w.q0 / w.S, w.q1 / w.S, d, (float)(f + 1));
     }
   }
   rast[g] = out;
@@ -191,16 +184,9 @@ mesh_shade_kernel(const float4* __restrict__ rast, const float* __restrict__ uv,
   const int f = (int)r.w - 1;
   float4 out = make_float4(bg[0], bg[1], bg[2], 0.f);
   if (f >= 0 && f < F) {
-    const float* a = uv + (int64_t)f * 6;
-    const float w = (1.f - r.x) - r.y;
-    const float v0 = flip_v ? 1.f - a[1] : a[1], v1 = flip_v ? 1.f - a[3] : a[3], v2 = flip_v ? 1.f - a[5] : a[5];
-    const MrBil q = mr_bilinear(mr_interp(r.x, r.y, w, a[0], a[2], a[4]), mr_interp(r.x, r.y, w, v0, v1, v2), Th, Tw);
-    const float* t00 = tex + ((int64_t)q.y0 * Tw + q.x0) * 3;
-    const float* t01 = tex + ((int64_t)q.y0 * Tw + q.x1) * 3;
-    const float* t10 = tex + ((int64_t)q.y1 * Tw + q.x0) * 3;
-    const float* t11 = tex + ((int64_t)q.y1 * Tw + q.x1) * 3;
-    out = make_float4(mr_mix(q, t00[0], t01[0], t10[0], t11[0]), mr_mix(q, t00[1], t01[1], t10[1], t11[1]),
-                      mr_mix(q, t00[2], t01[2], t10[2], t11[2]), 1.f);
+    const MrShade h = mr_shade(r, uv, f, flip_v);
+    const MrTap q = mr_tap(h.s, h.t, Th, Tw, 3, 0);
+    out = make_float4(mr_tap_mix(q, tex, 0), mr_tap_mix(q, tex, 1), mr_tap_mix(q, tex, 2), 1.f);
   }
   shaded[g] = out;
 }
@@ -216,27 +202,13 @@ mesh_shade_backward_kernel(const float4* __restrict__ rast, const float* __restr
   if (f < 0 || f >= F) return;
   const float4 go = g_shaded[g];
   const float gc[3] = {go.x, go.y, go.z};
-  const float* a = uv + (int64_t)f * 6;
-  const float w = (1.f - r.x) - r.y;
-  const float v0 = flip_v ? 1.f - a[1] : a[1], v1 = flip_v ? 1.f - a[3] : a[3], v2 = flip_v ? 1.f - a[5] : a[5];
-  const MrBil q = mr_bilinear(mr_interp(r.x, r.y, w, a[0], a[2], a[4]), mr_interp(r.x, r.y, w, v0, v1, v2), Th, Tw);
-  const int64_t o00 = ((int64_t)q.y0 * Tw + q.x0) * 3, o01 = ((int64_t)q.y0 * Tw + q.x1) * 3, o10 = ((int64_t)q.y1 * Tw + q.x0) * 3,
-                o11 = ((int64_t)q.y1 * Tw + q.x1) * 3;
-  const float w00 = (1.f - q.fy) * (1.f - q.fx), w01 = (1.f - q.fy) * q.fx, w10 = q.fy * (1.f - q.fx), w11 = q.fy * q.fx;
+  const MrShade h = mr_shade(r, uv, f, flip_v);
+  const MrTap q = mr_tap(h.s, h.t, Th, Tw, 3, 0);
   float gs = 0.f, gt = 0.f;
 #pragma unroll
   for (int c = 0; c < 3; c++) {
-    if (g_tex) {
-      atomicAdd(g_tex + o00 + c, w00 * gc[c]);
-      atomicAdd(g_tex + o01 + c, w01 * gc[c]);
-      atomicAdd(g_tex + o10 + c, w10 * gc[c]);
-      atomicAdd(g_tex + o11 + c, w11 * gc[c]);
-    }
-    if (g_uv) {
-      const float t00 = tex[o00 + c], t01 = tex[o01 + c], t10 = tex[o10 + c], t11 = tex[o11 + c];
-      gs += gc[c] * ((1.f - q.fy) * (t01 - t00) + q.fy * (t11 - t10));
-      gt += gc[c] * ((1.f - q.fx) * (t10 - t00) + q.fx * (t11 - t01));
-    }
+    if (g_tex) mr_tap_scatter(q, g_tex, c, gc[c]);
+    if (g_uv) mr_tap_slopes(q, tex, c, gc[c], gs, gt);
   }
   if (g_uv) {
     gs *= (float)Tw;
@@ -246,8 +218,8 @@ mesh_shade_backward_kernel(const float4* __restrict__ rast, const float* __restr
     atomicAdd(o + 1, r.x * gt);
     atomicAdd(o + 2, r.y * gs);
     atomicAdd(o + 3, r.y * gt);
-    atomicAdd(o + 4, w * gs);
-    atomicAdd(o + 5, w * gt);
+    atomicAdd(o + 4, h.w * gs);
+    atomicAdd(o + 5, h.w * gt);
   }
 }
 
@@ -294,14 +266,9 @@ mesh_texture_kernel(const float* __restrict__ tex, int64_t tex_stride, const flo
   const int64_t g = (int64_t)blockIdx.x * MR_THREADS + threadIdx.x;
   if (g >= pixels) return;
   const float2 st = uv[g];
-  const MrBil q = mr_bilinear(st.x, st.y, Th, Tw);
-  const float* t = tex + (g / per_view) * tex_stride;
-  const float* t00 = t + ((int64_t)q.y0 * Tw + q.x0) * C;
-  const float* t01 = t + ((int64_t)q.y0 * Tw + q.x1) * C;
-  const float* t10 = t + ((int64_t)q.y1 * Tw + q.x0) * C;
-  const float* t11 = t + ((int64_t)q.y1 * Tw + q.x1) * C;
+  const MrTap q = mr_tap(st.x, st.y, Th, Tw, C, (g / per_view) * tex_stride);
   float* o = out + g * C;
-  for (int c = 0; c < C; c++) o[c] = mr_mix(q, t00[c], t01[c], t10[c], t11[c]);
+  for (int c = 0; c < C; c++) o[c] = mr_tap_mix(q, tex, c);
 }
 
 __global__ void __launch_bounds__(MR_THREADS)
@@ -310,26 +277,13 @@ mesh_texture_backward_kernel(const float* __restrict__ tex, int64_t tex_stride, 
   const int64_t g = (int64_t)blockIdx.x * MR_THREADS + threadIdx.x;
   if (g >= pixels) return;
   const float2 st = uv[g];
-  const MrBil q = mr_bilinear(st.x, st.y, Th, Tw);
-  const int64_t base = (g / per_view) * tex_stride;
-  const int64_t o00 = base + ((int64_t)q.y0 * Tw + q.x0) * C, o01 = base + ((int64_t)q.y0 * Tw + q.x1) * C,
-                o10 = base + ((int64_t)q.y1 * Tw + q.x0) * C, o11 = base + ((int64_t)q.y1 * Tw + q.x1) * C;
-  const float w00 = (1.f - q.fy) * (1.f - q.fx), w01 = (1.f - q.fy) * q.fx, w10 = q.fy * (1.f - q.fx), w11 = q.fy * q.fx;
+  const MrTap q = mr_tap(st.x, st.y, Th, Tw, C, (g / per_view) * tex_stride);
   const float* go = g_out + g * C;
   float gs = 0.f, gt = 0.f;
   for (int c = 0; c < C; c++) {
     const float v = go[c];
-    if (g_tex) {
-      atomicAdd(g_tex + o00 + c, w00 * v);
-      atomicAdd(g_tex + o01 + c, w01 * v);
-      atomicAdd(g_tex + o10 + c, w10 * v);
-      atomicAdd(g_tex + o11 + c, w11 * v);
-    }
-    if (g_uv) {
-      const float t00 = tex[o00 + c], t01 = tex[o01 + c], t10 = tex[o10 + c], t11 = tex[o11 + c];
-      gs += v * ((1.f - q.fy) * (t01 - t00) + q.fy * (t11 - t10));
-      gt += v * ((1.f - q.fx) * (t10 - t00) + q.fx * (t11 - t01));
-    }
+    if (g_tex) mr_tap_scatter(q, g_tex, c, v);
+    if (g_uv) mr_tap_slopes(q, tex, c, v, gs, gt);
   }
   if (g_uv) g_uv[g] = make_float2(gs * (float)Tw, gt * (float)Th);
 }
@@ -367,30 +321,25 @@ extern "C" int gip_mesh_rasterize(const float* pos, const int32_t* tri, int32_t 
   return mr_done();
 }
 
-// the shapes shared by the per-pixel entry points: pixels = B * H * W of rast / uv, a batch of 1 or B on the other operand
-static int mr_batch_ok(int32_t B, int32_t H, int32_t W, int32_t batch) { return mr_image_ok(B, H, W) && (batch == 1 || batch == B); }
-
 extern "C" int gip_mesh_interpolate(const float* attr, int32_t attr_batch, int64_t N, int32_t C, const int32_t* idx, int64_t F,
                                     const float* rast, int32_t B, int32_t H, int32_t W, float* out, void* stream) {
-  if (!mr_batch_ok(B, H, W, attr_batch) || N < 0 || N > INT32_MAX || C < 1 || F < 0 || F > MR_MAX_FACES || !rast || !out) return 1;
-  if ((!idx && N != 3 * F) || N * C > INT32_MAX || (F > 0 && N > 0 && !attr)) return 1;
+  if (!mr_attr_ok(attr, attr_batch, N, C, idx, F, B, H, W) || !rast || !out) return 1;
   const int64_t pixels = (int64_t)B * H * W;
   hipLaunchKernelGGL(mesh_interpolate_kernel, dim3(mr_blocks(pixels)), dim3(MR_THREADS), 0, (hipStream_t)stream, attr,
-                     attr_batch == 1 ? (int64_t)0 : N * C, idx, (const float4*)rast, pixels, (int64_t)H * W, (int)F, (int)N, (int)C, out);
+                     mr_stride(attr_batch, N * C), idx, (const float4*)rast, pixels, (int64_t)H * W, (int)F, (int)N, (int)C, out);
   return mr_done();
 }
 
 extern "C" int gip_mesh_interpolate_backward(const float* g_out, int32_t attr_batch, int64_t N, int32_t C, const int32_t* idx, int64_t F,
                                              const float* rast, int32_t B, int32_t H, int32_t W, float* g_attr, void* stream) {
-  if (!mr_batch_ok(B, H, W, attr_batch) || N < 0 || N > INT32_MAX || C < 1 || F < 0 || F > MR_MAX_FACES || !rast || !g_out) return 1;
-  if ((!idx && N != 3 * F) || N * C > INT32_MAX) return 1;
+  if (!mr_attr_ok(g_attr, attr_batch, N, C, idx, F, B, H, W) || !rast || !g_out) return 1;
   if (N == 0) return 0;
   if (!g_attr) return 1;
   hipStream_t st = (hipStream_t)stream;
   if (hipMemsetAsync(g_attr, 0, (size_t)attr_batch * N * C * sizeof(float), st) != hipSuccess) return 3;
   const int64_t pixels = (int64_t)B * H * W;
   hipLaunchKernelGGL(mesh_interpolate_backward_kernel, dim3(mr_blocks(pixels)), dim3(MR_THREADS), 0, st, g_out, idx, (const float4*)rast,
-                     pixels, (int64_t)H * W, (int)F, (int)N, (int)C, g_attr, attr_batch == 1 ? (int64_t)0 : N * C);
+                     pixels, (int64_t)H * W, (int)F, (int)N, (int)C, g_attr, mr_stride(attr_batch, N * C));
   return mr_done();
 }
 
@@ -399,7 +348,7 @@ extern "C" int gip_mesh_texture(const float* tex, int32_t tex_batch, int32_t Th,
   if (!mr_batch_ok(B, H, W, tex_batch) || !mr_tex_ok(Th, Tw, C) || !tex || !uv || !out) return 1;
   const int64_t pixels = (int64_t)B * H * W;
   hipLaunchKernelGGL(mesh_texture_kernel, dim3(mr_blocks(pixels)), dim3(MR_THREADS), 0, (hipStream_t)stream, tex,
-                     tex_batch == 1 ? (int64_t)0 : (int64_t)Th * Tw * C, (const float2*)uv, pixels, (int64_t)H * W, (int)Th, (int)Tw, (int)C,
+                     mr_stride(tex_batch, (int64_t)Th * Tw * C), (const float2*)uv, pixels, (int64_t)H * W, (int)Th, (int)Tw, (int)C,
                      out);
   return mr_done();
 }
@@ -412,7 +361,7 @@ extern "C" int gip_mesh_texture_backward(const float* tex, int32_t tex_batch, in
   if (g_tex && hipMemsetAsync(g_tex, 0, (size_t)tex_batch * Th * Tw * C * sizeof(float), st) != hipSuccess) return 3;
   const int64_t pixels = (int64_t)B * H * W;
   hipLaunchKernelGGL(mesh_texture_backward_kernel, dim3(mr_blocks(pixels)), dim3(MR_THREADS), 0, st, tex,
-                     tex_batch == 1 ? (int64_t)0 : (int64_t)Th * Tw * C, (const float2*)uv, g_out, pixels, (int64_t)H * W, (int)Th, (int)Tw,
+                     mr_stride(tex_batch, (int64_t)Th * Tw * C), (const float2*)uv, g_out, pixels, (int64_t)H * W, (int)Th, (int)Tw,
                      (int)C, g_tex, (float2*)g_uv);
   return mr_done();
 }

@@ -29,12 +29,12 @@ from .. import _lib
 __all__ = ["MeshRasterizerContext", "DiffMeshRasterizerContext", "MipMeshRasterizerContext", "MipStack", "edge_topology", "render_mesh"]
 
 
+_MAX_SIDE = 16384             # of an image or a texture: the library's MR_MAX_SIZE
+_INT32_MAX = 2 ** 31 - 1      # the most pixels, or values of one tensor, the library indexes
+
+
 def _p(t):
     return ctypes.c_void_p(t.data_ptr() if t is not None and t.numel() else None)
-
-
-def _stream(dev):
-    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
 def _check(rc, name):
@@ -42,9 +42,18 @@ def _check(rc, name):
         raise RuntimeError("%s failed with status %d" % (name, rc))
 
 
+def _call(dev, name, *args):
+    """The library's entry point `name` with args and, as its last argument, dev's current stream; RuntimeError unless it returns 0."""
+    with torch.cuda.device(dev):
+        _check(getattr(_lib.model_lib(), name)(*args, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), name)
+
+
+def _is_gpu_float(t):
+    return isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32
+
+
 def _gpu_float(t, what, dims, last=None):
-    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() in dims and
-            (last is None or t.shape[-1] == last)):
+    if not (_is_gpu_float(t) and t.dim() in dims and (last is None or t.shape[-1] == last)):
         raise ValueError("%s must be a float32 GPU tensor with %s dimensions%s" %
                          (what, " or ".join(str(d) for d in dims), "" if last is None else " and a last dimension of %d" % last))
     return t.detach().contiguous()
@@ -57,8 +66,8 @@ def _resolution(resolution):
         H, W = int(resolution[0]), int(resolution[1])
     else:
         H = W = int(resolution)
-    if H < 1 or W < 1 or H > 16384 or W > 16384:
-        raise ValueError("resolution must lie in 1 .. 16384")
+    if H < 1 or W < 1 or H > _MAX_SIDE or W > _MAX_SIDE:
+        raise ValueError("resolution must lie in 1 .. %d" % _MAX_SIDE)
     return H, W
 
 
@@ -102,7 +111,7 @@ def _rasterize(pos, tri, resolution, cull_backfaces=False, validate=True, differ
     F = int(tri.shape[0])
     if F == 0:      # nothing to draw: no launch
         return torch.zeros((B, H, W, 4), dtype=torch.float32, device=pos.device)
-    if B * H * W > 2 ** 31 - 1 or F > 2 ** 24 - 1 or B * F > 2 ** 31 - 1:
+    if B * H * W > _INT32_MAX or F > 2 ** 24 - 1 or B * F > _INT32_MAX:
         raise ValueError("rasterize: %d views of %d x %d with %d triangles are outside the limits of gip_mesh_rasterize" % (B, H, W, F))
     if differentiable and given.requires_grad and torch.is_grad_enabled():
         return _RasterizeGrad.apply(given, tri, H, W, bool(cull_backfaces))
@@ -114,9 +123,7 @@ def _rasterize_launch(pos, tri, H, W, cull_backfaces):
     need = _workspace_bytes(B, H, W, F)
     ws = torch.empty(need, dtype=torch.uint8, device=pos.device)
     rast = torch.empty((B, H, W, 4), dtype=torch.float32, device=pos.device)
-    with torch.cuda.device(pos.device):
-        _check(_lib.model_lib().gip_mesh_rasterize(_p(pos), _p(tri), B, V, F, H, W, int(bool(cull_backfaces)), _p(ws), need, _p(rast),
-                                                   _stream(pos.device)), "gip_mesh_rasterize")
+    _call(pos.device, "gip_mesh_rasterize", _p(pos), _p(tri), B, V, F, H, W, int(bool(cull_backfaces)), _p(ws), need, _p(rast))
     return rast
 
 
@@ -137,9 +144,7 @@ class _RasterizeGrad(torch.autograd.Function):
         V, F = int(pos.shape[1]), int(tri.shape[0])
         g = g.contiguous().float()
         g_pos = torch.zeros_like(pos)
-        with torch.cuda.device(pos.device):
-            _check(_lib.model_lib().gip_mesh_rasterize_backward(_p(pos), _p(tri), B, V, F, H, W, _p(rast), _p(g), _p(g_pos),
-                                                                _stream(pos.device)), "gip_mesh_rasterize_backward")
+        _call(pos.device, "gip_mesh_rasterize_backward", _p(pos), _p(tri), B, V, F, H, W, _p(rast), _p(g), _p(g_pos))
         return g_pos, None, None, None, None
 
 
@@ -153,9 +158,7 @@ class _Interpolate(torch.autograd.Function):
         B, H, W, _ = rast.shape
         nb, N, C = attr.shape
         out = torch.empty((B, H, W, C), dtype=torch.float32, device=rast.device)
-        with torch.cuda.device(rast.device):
-            _check(_lib.model_lib().gip_mesh_interpolate(_p(attr), nb, N, C, _p(idx), F, _p(rast), B, H, W, _p(out), _stream(rast.device)),
-                   "gip_mesh_interpolate")
+        _call(rast.device, "gip_mesh_interpolate", _p(attr), nb, N, C, _p(idx), F, _p(rast), B, H, W, _p(out))
         ctx.save_for_backward(rast, idx, attr)
         ctx.shape, ctx.F = (nb, N, C), F
         return out
@@ -167,16 +170,12 @@ class _Interpolate(torch.autograd.Function):
         B, H, W, _ = rast.shape
         g = g.contiguous().float()
         g_attr = g_rast = None
-        with torch.cuda.device(rast.device):
-            if ctx.needs_input_grad[0]:
-                g_attr = torch.empty((nb, N, C), dtype=torch.float32, device=rast.device)
-                _check(_lib.model_lib().gip_mesh_interpolate_backward(_p(g), nb, N, C, _p(idx), ctx.F, _p(rast), B, H, W, _p(g_attr),
-                                                                      _stream(rast.device)), "gip_mesh_interpolate_backward")
-            if ctx.needs_input_grad[1]:      # only a rast of DiffMeshRasterizerContext carries a gradient
-                g_rast = torch.empty_like(rast)
-                _check(_lib.model_lib().gip_mesh_interpolate_backward_rast(_p(g), _p(attr), nb, N, C, _p(idx), ctx.F, _p(rast), B, H, W,
-                                                                           _p(g_rast), _stream(rast.device)),
-                       "gip_mesh_interpolate_backward_rast")
+        if ctx.needs_input_grad[0]:
+            g_attr = torch.empty((nb, N, C), dtype=torch.float32, device=rast.device)
+            _call(rast.device, "gip_mesh_interpolate_backward", _p(g), nb, N, C, _p(idx), ctx.F, _p(rast), B, H, W, _p(g_attr))
+        if ctx.needs_input_grad[1]:      # only a rast of DiffMeshRasterizerContext carries a gradient
+            g_rast = torch.empty_like(rast)
+            _call(rast.device, "gip_mesh_interpolate_backward_rast", _p(g), _p(attr), nb, N, C, _p(idx), ctx.F, _p(rast), B, H, W, _p(g_rast))
         return g_attr, g_rast, None, None
 
 
@@ -186,8 +185,7 @@ class _Texture(torch.autograd.Function):
         nb, Th, Tw, C = tex.shape
         B, H, W, _ = uv.shape
         out = torch.empty((B, H, W, C), dtype=torch.float32, device=uv.device)
-        with torch.cuda.device(uv.device):
-            _check(_lib.model_lib().gip_mesh_texture(_p(tex), nb, Th, Tw, C, _p(uv), B, H, W, _p(out), _stream(uv.device)), "gip_mesh_texture")
+        _call(uv.device, "gip_mesh_texture", _p(tex), nb, Th, Tw, C, _p(uv), B, H, W, _p(out))
         ctx.save_for_backward(tex, uv)
         return out
 
@@ -199,9 +197,7 @@ class _Texture(torch.autograd.Function):
         g = g.contiguous().float()
         g_tex = torch.empty_like(tex) if ctx.needs_input_grad[0] else None
         g_uv = torch.empty_like(uv) if ctx.needs_input_grad[1] else None
-        with torch.cuda.device(uv.device):
-            _check(_lib.model_lib().gip_mesh_texture_backward(_p(tex), nb, Th, Tw, C, _p(uv), _p(g), B, H, W, _p(g_tex), _p(g_uv),
-                                                              _stream(uv.device)), "gip_mesh_texture_backward")
+        _call(uv.device, "gip_mesh_texture_backward", _p(tex), nb, Th, Tw, C, _p(uv), _p(g), B, H, W, _p(g_tex), _p(g_uv))
         return g_tex, g_uv
 
 
@@ -214,9 +210,7 @@ class _Shade(torch.autograd.Function):
         B, H, W, _ = rast.shape
         F = int(uv.shape[0])
         shaded = torch.empty((B, H, W, 4), dtype=torch.float32, device=rast.device)
-        with torch.cuda.device(rast.device):
-            _check(_lib.model_lib().gip_mesh_shade(_p(rast), _p(uv), F, int(flip_v), _p(tex), Th, Tw, _p(bg), B, H, W, _p(shaded),
-                                                   _stream(rast.device)), "gip_mesh_shade")
+        _call(rast.device, "gip_mesh_shade", _p(rast), _p(uv), F, int(flip_v), _p(tex), Th, Tw, _p(bg), B, H, W, _p(shaded))
         ctx.save_for_backward(tex, uv, rast)
         ctx.flip_v = int(flip_v)
         return shaded
@@ -234,13 +228,10 @@ class _Shade(torch.autograd.Function):
         if F == 0:      # nothing was drawn: no launch
             return ((None if g_tex is None else torch.zeros_like(tex)), (None if g_uv is None else torch.zeros_like(uv)),
                     (None if g_rast is None else torch.zeros_like(rast)), None, None)
-        with torch.cuda.device(rast.device):
-            if g_tex is not None or g_uv is not None:
-                _check(_lib.model_lib().gip_mesh_shade_backward(_p(rast), _p(uv), F, ctx.flip_v, _p(tex), Th, Tw, _p(g), B, H, W, _p(g_tex),
-                                                                _p(g_uv), _stream(rast.device)), "gip_mesh_shade_backward")
-            if g_rast is not None:
-                _check(_lib.model_lib().gip_mesh_shade_backward_rast(_p(rast), _p(uv), F, ctx.flip_v, _p(tex), Th, Tw, _p(g), B, H, W,
-                                                                     _p(g_rast), _stream(rast.device)), "gip_mesh_shade_backward_rast")
+        if g_tex is not None or g_uv is not None:
+            _call(rast.device, "gip_mesh_shade_backward", _p(rast), _p(uv), F, ctx.flip_v, _p(tex), Th, Tw, _p(g), B, H, W, _p(g_tex), _p(g_uv))
+        if g_rast is not None:
+            _call(rast.device, "gip_mesh_shade_backward_rast", _p(rast), _p(uv), F, ctx.flip_v, _p(tex), Th, Tw, _p(g), B, H, W, _p(g_rast))
         return g_tex, g_uv, g_rast, None, None
 
 
@@ -257,7 +248,7 @@ def edge_topology(tri, num_vertices):
     if not (isinstance(tri, torch.Tensor) and tri.dtype == torch.int32 and tri.dim() == 2 and tri.shape[1] == 3):
         raise ValueError("tri must be an [F, 3] int32 tensor")
     V = int(num_vertices)
-    if V < 1 or V > 2 ** 31 - 1:
+    if V < 1 or V > _INT32_MAX:
         raise ValueError("num_vertices must lie in 1 .. 2^31 - 1")
     F = int(tri.shape[0])
     if F == 0:
@@ -290,9 +281,7 @@ class _Antialias(torch.autograd.Function):
         V, F = int(pos.shape[1]), int(tri.shape[0])
         color, pos = color.detach().contiguous(), pos.detach().contiguous()
         out = torch.empty_like(color)
-        with torch.cuda.device(color.device):
-            _check(_lib.model_lib().gip_mesh_antialias(_p(color), C, _p(rast), _p(pos), _p(tri), _p(topo), B, V, F, H, W, _p(out),
-                                                       _stream(color.device)), "gip_mesh_antialias")
+        _call(color.device, "gip_mesh_antialias", _p(color), C, _p(rast), _p(pos), _p(tri), _p(topo), B, V, F, H, W, _p(out))
         ctx.save_for_backward(color, pos, rast, tri, topo)
         return out
 
@@ -304,10 +293,8 @@ class _Antialias(torch.autograd.Function):
         g = g.contiguous().float()
         g_color = torch.empty_like(color) if ctx.needs_input_grad[0] else None
         g_pos = torch.zeros_like(pos) if ctx.needs_input_grad[1] else None
-        with torch.cuda.device(color.device):
-            _check(_lib.model_lib().gip_mesh_antialias_backward(_p(color), C, _p(rast), _p(pos), _p(tri), _p(topo), B, V, F, H, W, _p(g),
-                                                                _p(g_color), _p(g_pos), _stream(color.device)),
-                   "gip_mesh_antialias_backward")
+        _call(color.device, "gip_mesh_antialias_backward", _p(color), C, _p(rast), _p(pos), _p(tri), _p(topo), B, V, F, H, W, _p(g), _p(g_color),
+              _p(g_pos))
         return g_color, g_pos, None, None, None
 
 
@@ -328,7 +315,7 @@ class _TopologyCache:
 
 def _antialias(color, rast, pos, tri, topology, cache):
     for t, what in ((color, "color"), (rast, "rast"), (pos, "pos")):
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32):
+        if not _is_gpu_float(t):
             raise ValueError("%s must be a float32 GPU tensor" % what)
     if pos.dim() == 2:
         pos = pos[None]
@@ -338,7 +325,7 @@ def _antialias(color, rast, pos, tri, topology, cache):
         raise ValueError("rast must be [B, H, W, 4] with pos's B")
     if color.dim() != 4 or tuple(color.shape[:3]) != tuple(rast.shape[:3]) or color.shape[3] < 1:
         raise ValueError("color must be [B, H, W, C] with rast's B, H, W and at least one channel")
-    if color.numel() > 2 ** 31 - 1:
+    if color.numel() > _INT32_MAX:
         raise ValueError("color: at most 2^31 - 1 values")
     V = int(pos.shape[1])
     if not (isinstance(tri, torch.Tensor) and tri.is_cuda and tri.dtype == torch.int32 and tri.dim() == 2 and tri.shape[1] == 3):
@@ -351,6 +338,23 @@ def _antialias(color, rast, pos, tri, topology, cache):
               tuple(topology.shape) == tuple(tri.shape)):
         raise ValueError("topology must be what edge_topology(tri, V) returned: an [F, 3] int32 GPU tensor")
     return _Antialias.apply(color, pos, rast.detach().contiguous(), tri.detach().contiguous(), topology.contiguous())
+
+
+def _texture_tensor(tex, uv=None, whole_stack=False):
+    """tex as [nb, Th, Tw, C], checked against uv [B, H, W, 2] where one is given.  whole_stack: the mip stack's limit, which counts the
+    values of all nb textures together."""
+    if not (_is_gpu_float(tex) and tex.dim() in (3, 4)):
+        raise ValueError("tex must be a float32 GPU tensor, [1 or B, Th, Tw, C] or [Th, Tw, C]")
+    t = tex[None] if tex.dim() == 3 else tex
+    if min(t.shape) < 1 or max(t.shape[1:3]) > _MAX_SIDE or (whole_stack and t.numel() > _INT32_MAX):
+        raise ValueError("tex must have at least one texel and channel, at most %d texels a side%s" %
+                         (_MAX_SIDE, " and at most 2^31 - 1 values" if whole_stack else ""))
+    if uv is not None:
+        if not (_is_gpu_float(uv) and uv.dim() == 4 and uv.shape[-1] == 2):
+            raise ValueError("uv must be a float32 GPU tensor [B, H, W, 2]")
+        if t.shape[0] not in (1, uv.shape[0]) or t.device != uv.device:
+            raise ValueError("tex must have a batch of 1 or B and live on uv's device")
+    return t
 
 
 class MeshRasterizerContext:
@@ -376,10 +380,11 @@ class MeshRasterizerContext:
         return _rasterize(pos, tri, resolution, cull_backfaces, validate), None
 
     def rasterize_one(self, pos, tri, resolution, cull_backfaces=False, validate=True):
-        """rasterize of one view: pos [V, 4] -> (rast [H, W, 4], None)."""
+        """rasterize of one view: pos [V, 4] -> (rast [H, W, 4], rast_db [H, W, 4] where rasterize returns one, else None)."""
         if not (isinstance(pos, torch.Tensor) and pos.dim() == 2):
             raise ValueError("rasterize_one needs pos as [V, 4]")
-        return _rasterize(pos[None, ...], tri, resolution, cull_backfaces, validate)[0], None
+        rast, rast_db = self.rasterize(pos[None, ...], tri, resolution, cull_backfaces, validate)
+        return rast[0], None if rast_db is None else rast_db[0]
 
     def antialias(self, color, rast, pos, tri):
         raise NotImplementedError("antialias: the mesh rasterizer has no antialiasing pass")
@@ -392,7 +397,7 @@ class MeshRasterizerContext:
             raise NotImplementedError("interpolate: rast_db (pixel differentials) is not supported")
         if diff_attrs is not None:
             raise NotImplementedError("interpolate: diff_attrs (attribute pixel differentials) is not supported")
-        if not (isinstance(attr, torch.Tensor) and attr.is_cuda and attr.dtype == torch.float32 and attr.dim() in (2, 3)):
+        if not (_is_gpu_float(attr) and attr.dim() in (2, 3)):
             raise ValueError("attr must be a float32 GPU tensor, [N, C] or [1 or B, N, C]")
         rast = self._rast_input(rast)
         a = attr[None] if attr.dim() == 2 else attr
@@ -411,15 +416,7 @@ class MeshRasterizerContext:
             raise NotImplementedError("texture: filter_mode %r is not supported, only 'linear' (no mipmaps)" % (filter_mode,))
         if uv_da is not None or mip is not None:
             raise NotImplementedError("texture: %s (mipmaps) is not supported" % ("uv_da" if uv_da is not None else "mip"))
-        for t, what in ((tex, "tex"), (uv, "uv")):
-            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32):
-                raise ValueError("%s must be a float32 GPU tensor" % what)
-        if uv.dim() != 4 or uv.shape[-1] != 2 or tex.dim() not in (3, 4):
-            raise ValueError("texture needs tex [1 or B, Th, Tw, C] or [Th, Tw, C] and uv [B, H, W, 2]")
-        t = tex[None] if tex.dim() == 3 else tex
-        if t.shape[0] not in (1, uv.shape[0]) or min(t.shape[1:]) < 1 or max(t.shape[1:3]) > 16384:
-            raise ValueError("tex must have a batch of 1 or B, at least one texel and channel, and at most 16384 texels a side")
-        return _Texture.apply(t.contiguous(), uv.contiguous())
+        return _Texture.apply(_texture_tensor(tex, uv).contiguous(), uv.contiguous())
 
 
 def _rast_with_gradient(rast):
@@ -443,11 +440,6 @@ class DiffMeshRasterizerContext(MeshRasterizerContext):
         (gip_mesh_rasterize_backward; the snapping to the sub-pixel grid is straight-through).  rast_db stays None."""
         return _rasterize(pos, tri, resolution, cull_backfaces, validate, differentiable=True), None
 
-    def rasterize_one(self, pos, tri, resolution, cull_backfaces=False, validate=True):
-        if not (isinstance(pos, torch.Tensor) and pos.dim() == 2):
-            raise ValueError("rasterize_one needs pos as [V, 4]")
-        return _rasterize(pos[None, ...], tri, resolution, cull_backfaces, validate, differentiable=True)[0], None
-
     def antialias(self, color, rast, pos, tri, topology=None):
         """[B, H, W, C]: color with every pixel pair that a silhouette edge of the nearer pixel's triangle crosses blended by where
         the edge crosses (nvdiffrast's rule; csrc/mesh_grad.hip states it).  Differentiable in color and in pos [B, V, 4]; rast and tri
@@ -461,9 +453,7 @@ def _rast_db_launch(pos, tri, rast):
     B, H, W, _ = rast.shape
     V, F = int(pos.shape[1]), int(tri.shape[0])
     rast_db = torch.empty_like(rast)
-    with torch.cuda.device(rast.device):
-        _check(_lib.model_lib().gip_mesh_rast_db(_p(pos), _p(tri), B, V, F, H, W, _p(rast), _p(rast_db), _stream(rast.device)),
-               "gip_mesh_rast_db")
+    _call(rast.device, "gip_mesh_rast_db", _p(pos), _p(tri), B, V, F, H, W, _p(rast), _p(rast_db))
     return rast_db
 
 
@@ -475,9 +465,7 @@ class _InterpolateDa(torch.autograd.Function):
         B, H, W, _ = rast.shape
         nb, N, C = attr.shape
         out = torch.empty((B, H, W, 2 * K), dtype=torch.float32, device=rast.device)
-        with torch.cuda.device(rast.device):
-            _check(_lib.model_lib().gip_mesh_interpolate_da(_p(attr), nb, N, C, _p(idx), F, _p(rast), _p(rast_db), _p(channels), K, B, H, W,
-                                                            _p(out), _stream(rast.device)), "gip_mesh_interpolate_da")
+        _call(rast.device, "gip_mesh_interpolate_da", _p(attr), nb, N, C, _p(idx), F, _p(rast), _p(rast_db), _p(channels), K, B, H, W, _p(out))
         ctx.save_for_backward(rast, rast_db, idx, channels)
         ctx.shape, ctx.K, ctx.F = (nb, N, C), K, F
         return out
@@ -489,10 +477,8 @@ class _InterpolateDa(torch.autograd.Function):
         B, H, W, _ = rast.shape
         g = g.contiguous().float()
         g_attr = torch.empty((nb, N, C), dtype=torch.float32, device=rast.device)
-        with torch.cuda.device(rast.device):
-            _check(_lib.model_lib().gip_mesh_interpolate_da_backward(_p(g), nb, N, C, _p(idx), ctx.F, _p(rast), _p(rast_db), _p(channels),
-                                                                     ctx.K, B, H, W, _p(g_attr), _stream(rast.device)),
-                   "gip_mesh_interpolate_da_backward")
+        _call(rast.device, "gip_mesh_interpolate_da_backward", _p(g), nb, N, C, _p(idx), ctx.F, _p(rast), _p(rast_db), _p(channels), ctx.K, B, H,
+              W, _p(g_attr))
         return g_attr, None, None, None, None, None, None
 
 
@@ -507,15 +493,6 @@ def _mip_levels(Th, Tw, max_mip_level):
     L, texels = ctypes.c_int32(0), ctypes.c_int64(0)
     _check(_lib.model_lib().gip_mesh_mip_levels(Th, Tw, cap, ctypes.byref(L), ctypes.byref(texels)), "gip_mesh_mip_levels")
     return cap, int(L.value), int(texels.value)
-
-
-def _texture_tensor(tex):
-    if not (isinstance(tex, torch.Tensor) and tex.is_cuda and tex.dtype == torch.float32 and tex.dim() in (3, 4)):
-        raise ValueError("tex must be a float32 GPU tensor, [1 or B, Th, Tw, C] or [Th, Tw, C]")
-    t = tex[None] if tex.dim() == 3 else tex
-    if min(t.shape) < 1 or max(t.shape[1:3]) > 16384 or t.numel() > 2 ** 31 - 1:
-        raise ValueError("tex must have at least one texel and channel, at most 16384 texels a side and at most 2^31 - 1 values")
-    return t
 
 
 class MipStack:
@@ -541,8 +518,7 @@ def _construct_mip(t, max_mip_level):
     cap, L, texels = _mip_levels(Th, Tw, max_mip_level)
     buffer = torch.empty((nb, texels, C), dtype=torch.float32, device=t.device)
     if L:
-        with torch.cuda.device(t.device):
-            _check(_lib.model_lib().gip_mesh_mip_build(_p(t), nb, Th, Tw, C, cap, _p(buffer), texels, _stream(t.device)), "gip_mesh_mip_build")
+        _call(t.device, "gip_mesh_mip_build", _p(t), nb, Th, Tw, C, cap, _p(buffer), texels)
     return MipStack((nb, Th, Tw, C), cap, L, texels, buffer)
 
 
@@ -554,9 +530,8 @@ class _TextureMip(torch.autograd.Function):
         nb, Th, Tw, C = tex.shape
         B, H, W, _ = uv.shape
         out = torch.empty((B, H, W, C), dtype=torch.float32, device=uv.device)
-        with torch.cuda.device(uv.device):
-            _check(_lib.model_lib().gip_mesh_texture_mip(_p(tex), nb, Th, Tw, C, _p(stack.buffer), stack.texels, stack.max_level, _p(uv), _p(uv_da),
-                                                         _p(bias), int(nearest), B, H, W, _p(out), _stream(uv.device)), "gip_mesh_texture_mip")
+        _call(uv.device, "gip_mesh_texture_mip", _p(tex), nb, Th, Tw, C, _p(stack.buffer), stack.texels, stack.max_level, _p(uv), _p(uv_da),
+              _p(bias), int(nearest), B, H, W, _p(out))
         ctx.save_for_backward(tex, uv, uv_da, bias)
         ctx.stack, ctx.nearest = stack, int(nearest)
         return out
@@ -573,14 +548,10 @@ class _TextureMip(torch.autograd.Function):
         g_uv = torch.empty_like(uv) if ctx.needs_input_grad[1] else None
         g_da = torch.empty_like(uv_da) if uv_da is not None and ctx.needs_input_grad[2] else None
         g_bias = torch.empty_like(bias) if bias is not None and ctx.needs_input_grad[3] else None
-        lib = _lib.model_lib()
-        with torch.cuda.device(uv.device):
-            _check(lib.gip_mesh_texture_mip_backward(_p(tex), nb, Th, Tw, C, _p(stack.buffer), stack.texels, stack.max_level, _p(uv), _p(uv_da),
-                                                     _p(bias), ctx.nearest, _p(g), B, H, W, _p(g_tex), _p(g_mip), _p(g_uv), _p(g_da), _p(g_bias),
-                                                     _stream(uv.device)), "gip_mesh_texture_mip_backward")
-            if g_mip is not None:
-                _check(lib.gip_mesh_mip_fold(_p(g_tex), nb, Th, Tw, C, stack.max_level, _p(g_mip), stack.texels, _stream(uv.device)),
-                       "gip_mesh_mip_fold")
+        _call(uv.device, "gip_mesh_texture_mip_backward", _p(tex), nb, Th, Tw, C, _p(stack.buffer), stack.texels, stack.max_level, _p(uv),
+              _p(uv_da), _p(bias), ctx.nearest, _p(g), B, H, W, _p(g_tex), _p(g_mip), _p(g_uv), _p(g_da), _p(g_bias))
+        if g_mip is not None:
+            _call(uv.device, "gip_mesh_mip_fold", _p(g_tex), nb, Th, Tw, C, stack.max_level, _p(g_mip), stack.texels)
         return g_tex, g_uv, g_da, g_bias, None, None
 
 
@@ -599,13 +570,6 @@ class MipMeshRasterizerContext(DiffMeshRasterizerContext):
         if int(tri.shape[0]) == 0:      # nothing is drawn: no launch
             return rast, torch.zeros_like(rast)
         return rast, _rast_db_launch(pos.detach().contiguous(), tri.detach().contiguous(), rast.detach())
-
-    def rasterize_one(self, pos, tri, resolution, cull_backfaces=False, validate=True):
-        """rasterize of one view: pos [V, 4] -> (rast [H, W, 4], rast_db [H, W, 4])."""
-        if not (isinstance(pos, torch.Tensor) and pos.dim() == 2):
-            raise ValueError("rasterize_one needs pos as [V, 4]")
-        rast, rast_db = self.rasterize(pos[None, ...], tri, resolution, cull_backfaces, validate)
-        return rast[0], rast_db[0]
 
     def interpolate(self, attr, rast, tri, rast_db=None, diff_attrs=None):
         """(out, out_da).  Without rast_db and diff_attrs: the parent's (out, None).  With both: out is the parent's, bit for bit, and
@@ -632,7 +596,7 @@ class MipMeshRasterizerContext(DiffMeshRasterizerContext):
             if not chosen or min(chosen) < 0 or max(chosen) >= C:
                 raise ValueError("diff_attrs: channel indices must lie in [0, %d) and there must be at least one" % C)
             channels, K = torch.tensor(chosen, dtype=torch.int32, device=r.device), len(chosen)
-        if r.numel() // 4 * 2 * K > 2 ** 31 - 1:
+        if r.numel() // 4 * 2 * K > _INT32_MAX:
             raise ValueError("interpolate: out_da would hold more than 2^31 - 1 values")
         idx = _index_tensor(tri, "tri", int(a.shape[1]), validate=False)      # the parent's call has checked it
         return out, _InterpolateDa.apply(a, r, db, idx, channels, K, int(idx.shape[0]))
@@ -640,7 +604,7 @@ class MipMeshRasterizerContext(DiffMeshRasterizerContext):
     def texture_construct_mip(self, tex, max_mip_level=None):
         """The MipStack of tex [1 or B, Th, Tw, C] (or [Th, Tw, C]) to pass as texture(..., mip=): level l + 1 averages the 2 x 2
         blocks of level l, while every side above 1 is even, down to 1 x 1 or max_mip_level.  One call into the library."""
-        return _construct_mip(_texture_tensor(tex).detach().contiguous(), max_mip_level)
+        return _construct_mip(_texture_tensor(tex, whole_stack=True).detach().contiguous(), max_mip_level)
 
     def texture(self, tex, uv, filter_mode="auto", uv_da=None, mip_level_bias=None, mip=None, max_mip_level=None, boundary_mode="clamp"):
         """[B, H, W, C]: the lookup of tex [1 or B, Th, Tw, C] (or [Th, Tw, C]) at uv [B, H, W, 2].  filter_mode "auto" is
@@ -661,14 +625,9 @@ class MipMeshRasterizerContext(DiffMeshRasterizerContext):
             raise NotImplementedError("texture: filter_mode %r is not supported" % (filter_mode,))
         if isinstance(mip, (list, tuple)):
             raise NotImplementedError("texture: mip as a list of tensors is not supported, pass what texture_construct_mip returned")
-        t = _texture_tensor(tex)
-        if not (isinstance(uv, torch.Tensor) and uv.is_cuda and uv.dtype == torch.float32 and uv.dim() == 4 and uv.shape[-1] == 2):
-            raise ValueError("uv must be a float32 GPU tensor [B, H, W, 2]")
-        if t.shape[0] not in (1, uv.shape[0]) or t.device != uv.device:
-            raise ValueError("tex must have a batch of 1 or B and live on uv's device")
+        t = _texture_tensor(tex, uv, whole_stack=True)
         for extra, what, shape in ((uv_da, "uv_da", tuple(uv.shape[:3]) + (4,)), (mip_level_bias, "mip_level_bias", tuple(uv.shape[:3]))):
-            if extra is not None and not (isinstance(extra, torch.Tensor) and extra.is_cuda and extra.dtype == torch.float32 and
-                                          tuple(extra.shape) == shape and extra.device == uv.device):
+            if extra is not None and not (_is_gpu_float(extra) and tuple(extra.shape) == shape and extra.device == uv.device):
                 raise ValueError("%s must be a float32 GPU tensor of shape %s" % (what, list(shape)))
         t = t.contiguous()
         if mip is None:
@@ -720,11 +679,11 @@ def render_mesh(camera, vertices, faces, uv, texture, bg_color=None, cull_backfa
         _no_position_gradient(vertices, "vertices")
         vertices = _gpu_float(vertices, "vertices", (2,), 3)
     dev = vertices.device
-    if not (isinstance(uv, torch.Tensor) and uv.is_cuda and uv.dtype == torch.float32 and uv.dim() == 3 and tuple(uv.shape[1:]) == (3, 2)):
+    if not (_is_gpu_float(uv) and uv.dim() == 3 and tuple(uv.shape[1:]) == (3, 2)):
         raise ValueError("uv must be an [F, 3, 2] float32 GPU tensor")
-    if not (isinstance(texture, torch.Tensor) and texture.is_cuda and texture.dtype == torch.float32 and texture.dim() == 3 and
-            texture.shape[2] == 3 and min(texture.shape[:2]) >= 1 and max(texture.shape[:2]) <= 16384):
-        raise ValueError("texture must be a [Th, Tw, 3] float32 GPU tensor of at most 16384 texels a side")
+    if not (_is_gpu_float(texture) and texture.dim() == 3 and texture.shape[2] == 3 and min(texture.shape[:2]) >= 1 and
+            max(texture.shape[:2]) <= _MAX_SIDE):
+        raise ValueError("texture must be a [Th, Tw, 3] float32 GPU tensor of at most %d texels a side" % _MAX_SIDE)
     H, W = int(cams[0].image_height), int(cams[0].image_width)
     if any((int(c.image_height), int(c.image_width)) != (H, W) for c in cams):
         raise ValueError("render_mesh: the cameras of one batch must share an image size")
