@@ -14,15 +14,12 @@
 //   field_prepare_kernel   one thread per Gaussian: xyz', the adjugate inverse of Sigma with 1 / (det + 1e-24), opacity -> a 10-float
 //                          record; the per-axis interval of blocks the centre belongs to (lo[b] < x' and x' < hi[b] are monotone in
 //                          b, so the members form one interval) -> one 64-bit word of six 10-bit fields, "empty" = first > last.
-//   field_eval_kernel      one workgroup per block, voxels on lanes (VPT voxels per lane).  Binning: NO duplicate list and NO sort —
-//                          every workgroup walks the P range words (8 bytes per Gaussian, the same L2-resident table for all
-//                          workgroups), 1024 per trip, and compacts the members IN INDEX ORDER (ballot + popcount, per-wave counts
-//                          through LDS) into an LDS index list; when the list may overflow, and at the end, the listed records are
-//                          staged in LDS 256 at a time and every lane adds them to its voxels.  The per-voxel order is therefore
-//                          the Gaussians' order in memory, two runs are bitwise equal, and there is no float atomic.  Each batch of
-//                          256 is summed on its own and then added to the voxel's total (a two-level sum: the rounding error grows
-//                          with sqrt(256) + sqrt(batches) instead of sqrt(members)).
-// The fused multiply-adds of the evaluation are explicit fmaf(), the exponential is __expf (v_exp_f32) unless FIELD_PRECISE_EXP.
+//                          The ONE prepare kernel of the field family: field_sample.hip and texture.hip launch it through
+//                          field_prepare_launch, so membership and records are the same by construction.
+//   field_eval_kernel      one workgroup per block, voxels on lanes (VPT voxels per lane, a further pass when a block has more than
+//                          256 * 16).  Binning: NO duplicate list and NO sort — the walk of field_common.h (field_walk) over the P
+//                          range words, which also evaluates the pairs; this kernel's own part is voxel -> point and address, and
+//                          one sum per pair.
 //
 // ---- surface -------------------------------------------------------------------------------------------------------------------
 // Marching tetrahedra on the Kuhn decomposition: every grid cube is cut into the six tetrahedra 0 -> e_a -> e_a + e_b -> (1,1,1), one
@@ -33,19 +30,8 @@
 // vertex at t = (thr - f0) / (f1 - f0) from p.  Passes: flag crossing edges + count triangles per cube (gip_surface_count), two
 // exclusive scans by the caller, vertices and faces (gip_surface_emit).  Vertex order = edge id, face order = cube id, tetrahedron,
 // triangle of the case: deterministic.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "field_common.h"
 
-#include "../../include/gip_model.h"
-
-#define FIELD_THREADS 256
-#define FIELD_WAVES (FIELD_THREADS / 64)
-#define FIELD_SUB 4                                 // range words tested per thread per trip
-#define FIELD_CHUNK (FIELD_THREADS * FIELD_SUB)     // 1024
-#define FIELD_CAP 2048                              // capacity of the LDS member list; flushed when a trip might overflow it
-#define FIELD_BATCH 256                             // records staged in LDS at a time
-#define FIELD_REC 10                                // floats of a record: xyz' (3), inverse covariance (6), opacity
-#define FIELD_MAX_BLOCKS 1024                       // per axis: the range word has 10 bits per field
 #define FIELD_MAX_VPT 16
 
 // ------------------------------------------------------------------------------------------------------------------ prepare
@@ -118,21 +104,25 @@ field_prepare_kernel(const float* __restrict__ xyz, const float* __restrict__ op
   range[g] = word;
 }
 
+void field_prepare_launch(const float* xyz, const float* opacity, const float* scaling, const float* rotation, int64_t P,
+                          const float* center, float scale, const float* grid, int R, int nb, float margin, FieldPrepared out,
+                          hipStream_t stream) {
+  hipLaunchKernelGGL(field_prepare_kernel, dim3((unsigned)((P + FIELD_THREADS - 1) / FIELD_THREADS)), dim3(FIELD_THREADS), 0, stream, xyz,
+                     opacity, scaling, rotation, P, center, scale, grid, R, nb, margin, out.rec, out.range);
+}
+
 // ------------------------------------------------------------------------------------------------------------------ evaluate
 template <int VPT>
 __global__ void __launch_bounds__(FIELD_THREADS)
 field_eval_kernel(const float* __restrict__ rec, const uint64_t* __restrict__ range, int64_t P, const float* __restrict__ grid, int R,
                   int nb, float* __restrict__ field) {
-  __shared__ int s_idx[FIELD_CAP];
-  __shared__ float4 s_rec[FIELD_BATCH][3];
-  __shared__ int s_cnt[2][FIELD_SUB][FIELD_WAVES];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  __shared__ FieldLds<false> lds;
+  const int tid = threadIdx.x;
   const int s = R / nb, s3 = s * s * s;
   const int bz = blockIdx.x % nb, by = (blockIdx.x / nb) % nb, bx = blockIdx.x / (nb * nb);
-  const uint64_t lt = lane ? (~0ull >> (64 - lane)) : 0ull;   // lanes below this one
 
   for (int v0 = 0; v0 < s3; v0 += FIELD_THREADS * VPT) {      // one pass unless a block has more than 256 * 16 voxels
-    float px[VPT], py[VPT], pz[VPT], acc[VPT];
+    float px[VPT], py[VPT], pz[VPT], acc[VPT][1];
     int64_t at[VPT];
 #pragma unroll
     for (int k = 0; k < VPT; k++) {
@@ -143,116 +133,35 @@ field_eval_kernel(const float* __restrict__ rec, const uint64_t* __restrict__ ra
       py[k] = grid[iy];
       pz[k] = grid[iz];
       at[k] = v < s3 ? ((int64_t)ix * R + iy) * R + iz : -1;
-      acc[k] = 0.f;
+      acc[k][0] = 0.f;
     }
-    int staged = 0, par = 0;
-    for (int64_t base = 0; base < P; base += FIELD_CHUNK) {
-      // ---- which of the next 1024 Gaussians belong to this block; their indices appended to s_idx in index order
-      uint64_t bal[FIELD_SUB];
-      bool mine[FIELD_SUB];
-#pragma unroll
-      for (int i = 0; i < FIELD_SUB; i++) {
-        const int64_t g = base + i * FIELD_THREADS + tid;
-        bool m = false;
-        if (g < P) {
-          const uint64_t w = range[g];
-          const int x0 = (int)(w & 1023), x1 = (int)((w >> 10) & 1023), y0 = (int)((w >> 20) & 1023), y1 = (int)((w >> 30) & 1023),
-                    z0 = (int)((w >> 40) & 1023), z1 = (int)((w >> 50) & 1023);
-          m = bx >= x0 && bx <= x1 && by >= y0 && by <= y1 && bz >= z0 && bz <= z1;
-        }
-        mine[i] = m;
-        bal[i] = __ballot(m);
-        if (lane == 0) s_cnt[par][i][wave] = __popcll(bal[i]);
-      }
-      __syncthreads();
-      int run = staged;
-#pragma unroll
-      for (int i = 0; i < FIELD_SUB; i++) {
-        int off = 0;
-#pragma unroll
-        for (int w = 0; w < FIELD_WAVES; w++) {
-          if (w == wave) off = run;
-          run += s_cnt[par][i][w];
-        }
-        if (mine[i]) s_idx[off + __popcll(bal[i] & lt)] = (int)(base + i * FIELD_THREADS + tid);
-      }
-      staged = run;   // the same value in every thread; <= FIELD_CAP because a flush leaves at most FIELD_CAP - FIELD_CHUNK behind
-      par ^= 1;
-      if (staged <= FIELD_CAP - FIELD_CHUNK && base + FIELD_CHUNK < P) continue;
-      // ---- flush: add the listed Gaussians to this lane's voxels, 256 records at a time
-      for (int sb = 0; sb < staged; sb += FIELD_BATCH) {
-        __syncthreads();   // s_idx is complete; the previous batch's records are no longer read
-        const int n = min(FIELD_BATCH, staged - sb);
-        if (tid < n) {
-          const float* r = rec + (int64_t)s_idx[sb + tid] * FIELD_REC;
-          // power = dx (A dx + B dy + C dz) + dy (D dy + E dz) + dz (F dz): the scalings by -0.5 and -1 are exact
-          s_rec[tid][0] = make_float4(r[0], r[1], r[2], r[9]);
-          s_rec[tid][1] = make_float4(-0.5f * r[3], -r[4], -r[5], -0.5f * r[6]);
-          s_rec[tid][2] = make_float4(-r[7], -0.5f * r[8], 0.f, 0.f);
-        }
-        __syncthreads();
-        float part[VPT];
-#pragma unroll
-        for (int k = 0; k < VPT; k++) part[k] = 0.f;
-        for (int j = 0; j < n; j++) {
-          const float4 c0 = s_rec[j][0], c1 = s_rec[j][1], c2 = s_rec[j][2];
-#pragma unroll
-          for (int k = 0; k < VPT; k++) {
-            const float dx = px[k] - c0.x, dy = py[k] - c0.y, dz = pz[k] - c0.z;
-            const float t0 = fmaf(c1.z, dz, fmaf(c1.y, dy, c1.x * dx));
-            const float t1 = fmaf(c2.x, dz, c1.w * dy);
-            const float power = fmaf(dx, t0, fmaf(dy, t1, dz * (c2.y * dz)));
-#ifdef FIELD_PRECISE_EXP
-            const float w = power > 0.f ? 0.f : expf(power);
-#else
-            const float w = power > 0.f ? 0.f : __expf(power);
-#endif
-            part[k] = fmaf(c0.w, w, part[k]);
-          }
-        }
-#pragma unroll
-        for (int k = 0; k < VPT; k++) acc[k] += part[k];
-      }
-      staged = 0;
-    }
+    field_walk<VPT, 1, false>(lds, rec, range, nullptr, P, bx, by, bz, px, py, pz, VPT, acc,
+                              [](const FieldPair& q, float (&part)[1]) { part[0] = fmaf(q.c0.w, q.e, part[0]); });
 #pragma unroll
     for (int k = 0; k < VPT; k++)
-      if (at[k] >= 0) field[at[k]] = acc[k];
-    __syncthreads();   // a further pass reuses s_idx and s_cnt
+      if (at[k] >= 0) field[at[k]] = acc[k][0];
   }
 }
 
-static int field_shape_ok(int64_t P, int32_t R, int32_t nb) {
-  if (P < 0 || P > INT32_MAX || R < 1 || nb < 1 || nb > FIELD_MAX_BLOCKS || R % nb != 0) return 0;
-  if ((int64_t)nb * nb * nb > INT32_MAX) return 0;
-  return 1;
-}
-
 extern "C" int gip_field_workspace_size(int64_t P, int32_t R, int32_t num_blocks, size_t* bytes) {
-  if (!bytes || !field_shape_ok(P, R, num_blocks)) return 1;
-  // records [P, 10] float, then range words [P] (8-byte aligned: 40 P is a multiple of 8)
-  *bytes = (size_t)P * (FIELD_REC * sizeof(float) + sizeof(uint64_t));
-  return 0;
+  return field_workspace_size(P, R, num_blocks, bytes);
 }
 
 extern "C" int gip_density_field(const float* xyz, const float* opacity, const float* scaling, const float* rotation, int64_t P,
                                  const float* center, float scale, const float* grid, int32_t R, int32_t num_blocks, float margin,
                                  void* workspace, size_t workspace_bytes, float* field, void* stream) {
   size_t need = 0;
-  if (gip_field_workspace_size(P, R, num_blocks, &need) != 0 || !grid || !field) return 1;
+  if (field_workspace_size(P, R, num_blocks, &need) != 0 || !grid || !field) return 1;
   if (P > 0 && (!xyz || !opacity || !scaling || !rotation || !center || !workspace || workspace_bytes < need)) return 1;
   const int s = R / num_blocks;
   const int64_t s3 = (int64_t)s * s * s;
   if (s3 > INT32_MAX) return 1;
-  float* rec = (float*)workspace;
-  uint64_t* range = (uint64_t*)(rec + (size_t)P * FIELD_REC);
+  const FieldPrepared prep = field_workspace_split(workspace, P);
   hipStream_t st = (hipStream_t)stream;
-  if (P > 0)
-    hipLaunchKernelGGL(field_prepare_kernel, dim3((unsigned)((P + FIELD_THREADS - 1) / FIELD_THREADS)), dim3(FIELD_THREADS), 0, st, xyz,
-                       opacity, scaling, rotation, P, center, scale, grid, (int)R, (int)num_blocks, margin, rec, range);
+  if (P > 0) field_prepare_launch(xyz, opacity, scaling, rotation, P, center, scale, grid, (int)R, (int)num_blocks, margin, prep, st);
   const dim3 blocks((unsigned)(num_blocks * num_blocks * num_blocks));
 #define FIELD_LAUNCH(V) \
-  hipLaunchKernelGGL(field_eval_kernel<V>, blocks, dim3(FIELD_THREADS), 0, st, rec, range, P, grid, (int)R, (int)num_blocks, field)
+  hipLaunchKernelGGL(field_eval_kernel<V>, blocks, dim3(FIELD_THREADS), 0, st, prep.rec, prep.range, P, grid, (int)R, (int)num_blocks, field)
   if (s3 <= FIELD_THREADS) FIELD_LAUNCH(1);
   else if (s3 <= 2 * FIELD_THREADS) FIELD_LAUNCH(2);
   else if (s3 <= 4 * FIELD_THREADS) FIELD_LAUNCH(4);

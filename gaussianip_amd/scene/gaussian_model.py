@@ -175,23 +175,16 @@ class GaussianModel:
         self.scale = 1.8 / extent if extent > 0 else 1.0      # a single centre has no extent (the reference divides by zero there)
         return mask, xyzs, opacities, stds, rots
 
-    @torch.no_grad()
-    def extract_fields(self, resolution=128, num_blocks=16, relax_ratio=1.5):
-        """The density of the Gaussians on a resolution^3 grid over the normalised cloud ([R, R, R] float32, `ij` order), the
-        reference's GaussianModel.extract_fields (gs_renderer.py:240-331) in two launches (csrc/field.hip) instead of a Python loop
-        over num_blocks^3 blocks: Gaussians with opacity > 0.005, normalised by self.center / self.scale (set here, as there), each
-        contributing to the blocks whose box, relaxed by relax_ratio block sizes, strictly contains its centre.
-        ValueError when num_blocks does not divide resolution (the reference's behaviour there is an accident of Tensor.split)."""
+    def _field_call(self, entry, src, colors, resolution, num_blocks, relax_ratio, before, after):
+        """One call of the C entry `entry` of the field family (gip_density_field, gip_field_sample, gip_texture_bake) on the sources
+        `src` of _field_sources(): the sources (with `colors` [N, 3] of the whole model cut to them, unless None) and the geometry,
+        then the entry's own arguments `before` and `after` the workspace, then the stream; tensors go by address.  RuntimeError
+        naming the entry on a non-zero status."""
         import ctypes
 
         from .. import _lib
-        resolution, num_blocks = self._field_geometry("extract_fields", resolution, num_blocks)
-        dev = self._xyz.device
-        occ = torch.zeros((resolution,) * 3, dtype=torch.float32, device=dev)
-        src = self._field_sources()
-        if src is None:
-            return occ
-        _, xyzs, opacities, stds, rots = src
+        mask, xyzs, opacities, stds, rots = src
+        dev = xyzs.device
         P = int(opacities.shape[0])
         grid = torch.linspace(-1, 1, resolution, dtype=torch.float32).to(dev)      # the host's values: the cut below depends on their bits
         margin = (2 / num_blocks) * relax_ratio       # rounded to float32 on the way in, like `vmin -= block_size * relax_ratio`
@@ -201,13 +194,45 @@ class GaussianModel:
         if rc != 0:
             raise RuntimeError("gip_field_workspace_size failed with status %d" % rc)
         ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
-        p = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+        rgb = () if colors is None else (colors.float()[mask].contiguous(),)
+        args = ((xyzs, opacities, stds, rots) + rgb + (P, self.center.contiguous(), self.scale, grid, resolution, num_blocks, margin) +
+                tuple(before) + (ws, need.value) + tuple(after))
         with torch.cuda.device(dev):
-            rc = lib.gip_density_field(p(xyzs), p(opacities), p(stds), p(rots), P, p(self.center.contiguous()), self.scale, p(grid),
-                                       resolution, num_blocks, margin, p(ws), need.value, p(occ),
-                                       ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+            rc = getattr(lib, entry)(*(ctypes.c_void_p(a.data_ptr()) if isinstance(a, torch.Tensor) else a for a in args),
+                                     ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
         if rc != 0:
-            raise RuntimeError("gip_density_field failed with status %d" % rc)
+            raise RuntimeError("%s failed with status %d" % (entry, rc))
+
+    @staticmethod
+    def _point_blocks(u, resolution, num_blocks):
+        """The block [V] (int64, (bx * nb + by) * nb + bz) each normalised point of u [V, 3] is evaluated in: per axis the block of the
+        last grid value <= the coordinate (points outside the grid: the edge blocks)."""
+        grid = torch.linspace(-1, 1, resolution, dtype=torch.float32).to(u.device)      # as in _field_call: exact for grid values
+        cell = (torch.bucketize(u.contiguous(), grid, right=True) - 1).clamp(0, resolution - 1) // (resolution // num_blocks)
+        return (cell[:, 0] * num_blocks + cell[:, 1]) * num_blocks + cell[:, 2]
+
+    def _colors(self, what, colors):
+        """`colors` checked: [N, 3] per Gaussian of the model (before the opacity prefilter); None = the base colour."""
+        from ..utils.sh import C0
+        if colors is None:
+            colors = (0.5 + C0 * self._features_dc.float().reshape(-1, 3)).clamp(0, 1)
+        if not (isinstance(colors, torch.Tensor) and colors.device == self._xyz.device and colors.dim() == 2 and
+                tuple(colors.shape) == (self._xyz.shape[0], 3)):
+            raise ValueError("%s: colors must be an [N, 3] tensor on the model's device, one row per Gaussian" % what)
+        return colors
+
+    @torch.no_grad()
+    def extract_fields(self, resolution=128, num_blocks=16, relax_ratio=1.5):
+        """The density of the Gaussians on a resolution^3 grid over the normalised cloud ([R, R, R] float32, `ij` order), the
+        reference's GaussianModel.extract_fields (gs_renderer.py:240-331) in two launches (csrc/field.hip) instead of a Python loop
+        over num_blocks^3 blocks: Gaussians with opacity > 0.005, normalised by self.center / self.scale (set here, as there), each
+        contributing to the blocks whose box, relaxed by relax_ratio block sizes, strictly contains its centre.
+        ValueError when num_blocks does not divide resolution (the reference's behaviour there is an accident of Tensor.split)."""
+        resolution, num_blocks = self._field_geometry("extract_fields", resolution, num_blocks)
+        occ = torch.zeros((resolution,) * 3, dtype=torch.float32, device=self._xyz.device)
+        src = self._field_sources()
+        if src is not None:
+            self._field_call("gip_density_field", src, None, resolution, num_blocks, relax_ratio, (), (occ,))
         return occ
 
     @torch.no_grad()
@@ -252,45 +277,20 @@ class GaussianModel:
         """density [V], gradient [V, 3] (normalised space) and colour sum [V, 3] at the normalised points u [V, 3], each evaluated in
         the block `block` [V] (int64, (bx * nb + by) * nb + bz) — one call of gip_field_sample (csrc/field_sample.hip).  Outputs in
         the caller's order.  `colors`: [N, 3] per Gaussian of the model (before the opacity prefilter), None = the base colour."""
-        import ctypes
-
-        from .. import _lib
-        from ..utils.sh import C0
         dev = self._xyz.device
         V = int(u.shape[0])
         out = {"density": torch.zeros(V, dtype=torch.float32, device=dev), "gradient": torch.zeros((V, 3), dtype=torch.float32, device=dev),
                "color_sum": torch.zeros((V, 3), dtype=torch.float32, device=dev)}
-        if colors is None:
-            colors = (0.5 + C0 * self._features_dc.float().reshape(-1, 3)).clamp(0, 1)
-        if not (isinstance(colors, torch.Tensor) and colors.device == dev and colors.dim() == 2 and
-                tuple(colors.shape) == (self._xyz.shape[0], 3)):
-            raise ValueError("%s: colors must be an [N, 3] tensor on the model's device, one row per Gaussian" % what)
+        colors = self._colors(what, colors)
         src = self._field_sources()
         if src is None or V == 0:
             return out
-        mask, xyzs, opacities, stds, rots = src
-        rgb = colors.float()[mask].contiguous()
-        P = int(opacities.shape[0])
         order = torch.sort(block, stable=True).indices            # grouped by block, the caller's order kept inside a block
         counts = torch.bincount(block, minlength=num_blocks ** 3)
         block_start = torch.cat((counts.new_zeros(1), counts.cumsum(0))).to(torch.int32)
         pts = u[order].contiguous()
-        grid = torch.linspace(-1, 1, resolution, dtype=torch.float32).to(dev)      # as in extract_fields: membership depends on their bits
-        margin = (2 / num_blocks) * relax_ratio
-        lib = _lib.model_lib()
-        need = ctypes.c_size_t(0)
-        rc = lib.gip_field_sample_workspace_size(P, resolution, num_blocks, ctypes.byref(need))
-        if rc != 0:
-            raise RuntimeError("gip_field_sample_workspace_size failed with status %d" % rc)
-        ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
         dens, grad, csum = (torch.empty_like(out[k]) for k in ("density", "gradient", "color_sum"))
-        p = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
-        with torch.cuda.device(dev):
-            rc = lib.gip_field_sample(p(xyzs), p(opacities), p(stds), p(rots), p(rgb), P, p(self.center.contiguous()), self.scale, p(grid),
-                                      resolution, num_blocks, margin, p(pts), p(block_start), V, p(ws), need.value, p(dens), p(grad),
-                                      p(csum), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        if rc != 0:
-            raise RuntimeError("gip_field_sample failed with status %d" % rc)
+        self._field_call("gip_field_sample", src, colors, resolution, num_blocks, relax_ratio, (pts, block_start, V), (dens, grad, csum))
         out["density"][order], out["gradient"][order], out["color_sum"][order] = dens, grad, csum
         return out
 
@@ -320,9 +320,7 @@ class GaussianModel:
             u = points
         else:
             u = (points - self.center) * self.scale
-        grid = torch.linspace(-1, 1, resolution, dtype=torch.float32).to(dev)
-        cell = (torch.bucketize(u.contiguous(), grid, right=True) - 1).clamp(0, resolution - 1) // (resolution // num_blocks)
-        block = (cell[:, 0] * num_blocks + cell[:, 1]) * num_blocks + cell[:, 2]
+        block = self._point_blocks(u, resolution, num_blocks)
         out = self._sample("sample_fields", u, block, colors, resolution, num_blocks, relax_ratio)
         scale = self.scale if src is not None else 1.0
         return {"density": out["density"], "gradient": out["gradient"] * scale, "color": self._blend(out["color_sum"], out["density"])}
@@ -415,19 +413,11 @@ class GaussianModel:
                    normalized=False):
         """bake_texture's checks and its one call of gip_texture_bake: {"density": [T, T], "color_sum": [T, T, 3], "uv", "cell"}, the
         raw sums (0 at unowned texels)."""
-        import ctypes
-
-        from .. import _lib
         from ..utils import texture as tex
-        from ..utils.sh import C0
+        from ..utils.mesh import _mesh_args
         resolution, num_blocks = self._field_geometry("bake_texture", resolution, num_blocks)
         dev = self._xyz.device
-        if not (isinstance(vertices, torch.Tensor) and vertices.is_cuda and vertices.dtype == torch.float32 and vertices.dim() == 2 and
-                vertices.shape[1] == 3):
-            raise ValueError("bake_texture needs a [V, 3] float32 GPU tensor of vertices")
-        if not (isinstance(faces, torch.Tensor) and faces.is_cuda and faces.dtype == torch.int32 and faces.dim() == 2 and
-                faces.shape[1] == 3):
-            raise ValueError("bake_texture needs an [F, 3] int32 GPU tensor of faces")
+        vertices, faces = _mesh_args("bake_texture", vertices, faces)
         if slices is not None and not 1 <= int(slices) <= 65535:
             raise ValueError("bake_texture: slices must lie in 1 .. 65535")
         V, F = int(vertices.shape[0]), int(faces.shape[0])
@@ -435,27 +425,19 @@ class GaussianModel:
         if T < 4 or T > 16384:
             raise ValueError("bake_texture: texture_size must lie in 4 .. 16384")
         c, _, _ = tex.atlas_layout(F, T)
-        if colors is None:
-            colors = (0.5 + C0 * self._features_dc.float().reshape(-1, 3)).clamp(0, 1)
-        if not (isinstance(colors, torch.Tensor) and colors.device == dev and colors.dim() == 2 and
-                tuple(colors.shape) == (self._xyz.shape[0], 3)):
-            raise ValueError("bake_texture: colors must be an [N, 3] tensor on the model's device, one row per Gaussian")
+        colors = self._colors("bake_texture", colors)
         density = torch.zeros((T, T), dtype=torch.float32, device=dev)
         color_sum = torch.zeros((T, T, 3), dtype=torch.float32, device=dev)
         out = {"density": density, "color_sum": color_sum, "uv": torch.from_numpy(tex.atlas_uv(F, T)).to(dev), "cell": c}
         if F == 0:
             return out
-        vertices, faces = vertices.detach().to(dev).contiguous(), faces.detach().to(dev).contiguous()
+        vertices, faces = vertices.to(dev), faces.to(dev)
         src = self._field_sources()
         fl = faces.long()
         if src is not None and V > 0:
-            mask, xyzs, opacities, stds, rots = src
             u = vertices if normalized else ((vertices - self.center) * self.scale).contiguous()
             tri = u[fl.clamp(0, V - 1)]
-            centroid = ((tri[:, 0] + tri[:, 1] + tri[:, 2]) / 3).contiguous()
-            grid = torch.linspace(-1, 1, resolution, dtype=torch.float32).to(dev)      # as in extract_fields: membership depends on their bits
-            cell = (torch.bucketize(centroid, grid, right=True) - 1).clamp(0, resolution - 1) // (resolution // num_blocks)
-            block = (cell[:, 0] * num_blocks + cell[:, 1]) * num_blocks + cell[:, 2]
+            block = self._point_blocks((tri[:, 0] + tri[:, 1] + tri[:, 2]) / 3, resolution, num_blocks)
             counts = torch.bincount(block, minlength=num_blocks ** 3)
             lo, hi, fullest = (int(x) for x in torch.stack((fl.min(), fl.max(), counts.max())).cpu())      # the one host read
         else:
@@ -468,23 +450,8 @@ class GaussianModel:
             slices = min(max((fullest * (c * (c + 1) // 2) + 1023) // 1024, 1), 1024)
         face_order = torch.sort(block, stable=True).indices.to(torch.int32)
         block_start = torch.cat((counts.new_zeros(1), counts.cumsum(0))).to(torch.int32)
-        rgb = colors.float()[mask].contiguous()
-        P = int(opacities.shape[0])
-        margin = (2 / num_blocks) * relax_ratio
-        lib = _lib.model_lib()
-        need = ctypes.c_size_t(0)
-        rc = lib.gip_texture_bake_workspace_size(P, resolution, num_blocks, ctypes.byref(need))
-        if rc != 0:
-            raise RuntimeError("gip_texture_bake_workspace_size failed with status %d" % rc)
-        ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
-        p = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
-        with torch.cuda.device(dev):
-            rc = lib.gip_texture_bake(p(xyzs), p(opacities), p(stds), p(rots), p(rgb), P, p(self.center.contiguous()), self.scale, p(grid),
-                                      resolution, num_blocks, margin, p(u), V, p(faces), F, p(face_order), p(block_start), T, c,
-                                      int(slices), p(ws), need.value, p(density), p(color_sum),
-                                      ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        if rc != 0:
-            raise RuntimeError("gip_texture_bake failed with status %d" % rc)
+        self._field_call("gip_texture_bake", src, colors, resolution, num_blocks, relax_ratio,
+                         (u, V, faces, F, face_order, block_start, T, c, int(slices)), (density, color_sum))
         return out
 
     @torch.no_grad()

@@ -21,6 +21,8 @@ import zlib
 import numpy as np
 import torch
 
+from .mesh import _mesh_args
+
 
 def atlas_layout(F, size):
     """(c, n, b): cell side, cells per row and leg of the atlas of F faces in a size x size texture.  ValueError when even cells of
@@ -118,16 +120,6 @@ def _view_size(what, cameras):
     return cams, K, H, W
 
 
-def _mesh_tensors(what, vertices, faces):
-    if not (isinstance(vertices, torch.Tensor) and vertices.is_cuda and vertices.dtype == torch.float32 and vertices.dim() == 2 and
-            vertices.shape[1] == 3):
-        raise ValueError("%s needs a [V, 3] float32 GPU tensor of vertices" % what)
-    if not (isinstance(faces, torch.Tensor) and faces.is_cuda and faces.dtype == torch.int32 and faces.dim() == 2 and
-            faces.shape[1] == 3 and faces.device == vertices.device):
-        raise ValueError("%s needs an [F, 3] int32 GPU tensor of faces on the vertices' device" % what)
-    return vertices.detach().contiguous(), faces.detach().contiguous()
-
-
 @torch.no_grad()
 def visible_depth(cameras, vertices, faces, validate=True):
     """[K, H, W] float32: the clip-space w of the mesh surface (vertices [V, 3] float32 world coordinates, faces [F, 3] int32, on the
@@ -136,7 +128,7 @@ def visible_depth(cameras, vertices, faces, validate=True):
     project_views tests a texel's own w against.  Two calls into the library."""
     from .rasterize import MeshRasterizerContext
     cams, K, H, W = _view_size("visible_depth", cameras)
-    vertices, faces = _mesh_tensors("visible_depth", vertices, faces)
+    vertices, faces = _mesh_args("visible_depth", vertices, faces)
     dev = vertices.device
     if faces.shape[0] == 0 or vertices.shape[0] == 0:
         return torch.zeros((K, H, W), dtype=torch.float32, device=dev)
@@ -170,7 +162,7 @@ def project_views(vertices, faces, texture_size, cameras, images, vis_depth, *, 
         raise ValueError("project_views: unpremultiply needs min_alpha > 0 (the colour is divided by the alpha)")
     if not depth_tolerance >= 0:
         raise ValueError("project_views: depth_tolerance must be >= 0")
-    vertices, faces = _mesh_tensors("project_views", vertices, faces)
+    vertices, faces = _mesh_args("project_views", vertices, faces)
     dev = vertices.device
 
     def on_device(t, shape, what):

@@ -81,3 +81,18 @@ def edge_case(name):
 
 
 EDGE_CASES = ("single", "transparent", "octant", "packed", "voxel_blocks")
+
+# ---- blocks of more than 512 voxels: (resolution, num_blocks) -> the seed of cloud(300, seed).  field_eval_kernel holds 1 / 2 / 4 / 8 / 16
+# voxels per lane by the block's size and makes a further pass beyond 256 * 16; the cases above stop at 512 voxels per block.  Normalised
+# centres lie in [-0.9, 0.9] and the box faces at +-4 (one block) or +-1.47 / +-2.5 (two), so every kept Gaussian is a member of every
+# block and no centre is near a face.
+LARGE_BLOCK_P = 300
+LARGE_BLOCKS = {(10, 1): 51,       # 1000 voxels per block: 4 per lane
+                (12, 1): 52,       # 1728: 8 per lane
+                (16, 1): 53,       # 4096: 16 per lane, exactly one pass
+                (17, 1): 54,       # 4913: 16 per lane, two passes, a ragged tail of 817
+                (34, 2): 55}       # 4913 in each of 8 blocks: the same with non-zero block coordinates
+
+
+def large_block_case(R, nb):
+    return cloud(LARGE_BLOCK_P, LARGE_BLOCKS[(R, nb)]), R, nb

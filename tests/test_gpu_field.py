@@ -105,6 +105,19 @@ def test_edge_cases_against_float64(golden, name):
     assert (occ[empty] == 0).all()              # blocks without a member are exactly zero
 
 
+@pytest.mark.parametrize("R,nb", sorted(field_inputs.LARGE_BLOCKS))
+def test_large_blocks_against_float64(golden, R, nb):
+    """4, 8 and 16 voxels per lane and the kernel's second pass (tests/field_inputs.py: LARGE_BLOCKS), under the edge cases' bar.  Every
+    kept Gaussian is a member of every block here, so there is no empty block to assert on."""
+    cl, R, nb = field_inputs.large_block_case(R, nb)
+    f64, info = field_reference.density_field(cl["xyz"], cl["opacity"], cl["scaling"], cl["rotation"], R, nb)
+    assert info["face_distance"] > 1e-5
+    assert (R // nb) ** 3 > 512 and info["kept"] > 0 and (info["members"] == info["kept"]).all()
+    occ, _ = _kernel(cl, R, nb)
+    ref_err = min(float(golden[n + "_err"]) for n in field_inputs.CASES)
+    _check("large_%d_%d" % (R, nb), occ.cpu().numpy(), f64, np.abs(f64).max(), ref_err)
+
+
 def test_nothing_passes_the_prefilter():
     cl, R, nb = field_inputs.edge_case("transparent")
     occ, _ = _kernel(cl, R, nb)

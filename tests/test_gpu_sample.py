@@ -62,6 +62,16 @@ def test_grid_points_match_the_reference_field(name):
     assert torch.equal(got, occ.reshape(-1))
 
 
+@pytest.mark.parametrize("R,nb", [(17, 1), (34, 2)])
+def test_grid_points_equal_the_field_on_its_second_pass(R, nb):
+    """Blocks of 4913 voxels: the field kernel holds 16 voxels per lane and makes two passes, the sampler five of four points."""
+    cl, R, nb = field_inputs.large_block_case(R, nb)
+    gm = _model(cl)
+    out = _sample(gm, sample_inputs.grid_points(R).cuda(), resolution=R, num_blocks=nb, normalized=True)
+    occ = gm.extract_fields(resolution=R, num_blocks=nb)
+    assert float(occ.max()) > 0 and torch.equal(out["density"], occ.reshape(-1))
+
+
 # ---------------------------------------------------------------------------------------------------------------- 2. off-grid points
 @functools.lru_cache(maxsize=None)
 def _offgrid():

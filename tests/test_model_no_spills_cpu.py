@@ -2,8 +2,11 @@
 Makefile's flags of that library (-ffp-contract=off) and the compiler's kernel-resource-usage remarks are read.  Every named kernel
 must be found, the file must hold no other kernel, and nothing is allowed to spill.  What each file keeps per lane, which is what
 would spill first:
+  field.hip            the evaluate kernel keeps up to 16 voxels with three coordinates, an address, a sum and a batch sum each; it also
+                       holds the one prepare kernel of the field family, which the next two files launch through a host function.
   field_sample.hip     the evaluate kernel keeps SAMPLE_PPT points with seven sums and seven batch sums each.
   texture.hip          the evaluate kernel keeps TEX_PPT texels with three coordinates, four sums and four batch sums each.
+                       (The per-lane arrays of these three are handed to the shared walk of field_common.h by reference.)
   texture_project.hip  the kernel keeps a texel's point, normal and four sums and loops over the views without a local array.
   mesh_raster.hip      the set-up kernel keeps a triangle's snapped corners, three 64-bit edge functions and their six 64-bit steps.
   mesh_grad.hip        the antialias kernels keep what four pixel pairs found (weight, edge, slope), in arrays that must stay in registers.
@@ -21,9 +24,9 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 SOURCES = [
     ("field.hip", ("field_prepare_kernel", "field_eval_kernelILi1E", "field_eval_kernelILi2E", "field_eval_kernelILi4E", "field_eval_kernelILi8E",
                    "field_eval_kernelILi16E", "surface_count_kernel", "surface_emit_kernel")),
-    ("field_sample.hip", ("sample_prepare_kernel", "sample_eval_kernelILi4ELb0E", "sample_eval_kernelILi4ELb1E")),
+    ("field_sample.hip", ("sample_eval_kernelILi4ELb0E", "sample_eval_kernelILi4ELb1E")),
     ("ssim.hip", ("ssim_forward_kernel", "ssim_backward_kernel", "ssim_finish_kernel")),
-    ("texture.hip", ("texture_prepare_kernel", "texture_eval_kernelILi4EE")),
+    ("texture.hip", ("texture_eval_kernelILi4EE",)),
     ("texture_project.hip", ("texture_project_kernel",)),
     ("mesh_raster.hip", ("mesh_setup_kernel", "mesh_large_kernel", "mesh_resolve_kernel", "mesh_shade_kernel", "mesh_shade_backward_kernel",
                          "mesh_interpolate_kernel", "mesh_interpolate_backward_kernel", "mesh_texture_kernel", "mesh_texture_backward_kernel")),
