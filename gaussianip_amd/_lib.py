@@ -66,7 +66,8 @@ call_counts = {}       # C-ABI entry point -> number of calls through this modul
 
 
 class _Counted:
-    """The loaded library with a per-symbol call counter in front of every entry point."""
+    """The loaded library with a per-symbol call counter in front of every entry point.  A `*_buckets` entry point of the
+    rasterizer is the launch set of the entry point it extends with another key layout: it counts under that name as well."""
 
     def __init__(self, lib):
         self._lib = lib
@@ -77,8 +78,11 @@ class _Counted:
         if w is None:
             fn = getattr(self._lib, name)
 
-            def w(*args, _fn=fn, _name=name):
-                call_counts[_name] = call_counts.get(_name, 0) + 1
+            names = (name, name.replace("_buckets", "")) if name.startswith("gip_raster_") and "_buckets" in name else (name,)
+
+            def w(*args, _fn=fn, _names=names):
+                for n in _names:
+                    call_counts[n] = call_counts.get(n, 0) + 1
                 return _fn(*args)
             self._wrapped[name] = w
         return w
@@ -111,6 +115,21 @@ def raster_lib():
         lib.gip_raster_forward_profiled.argtypes = lib.gip_raster_forward.argtypes + [ctypes.POINTER(ctypes.c_float)]
         lib.gip_raster_backward_profiled.restype = ctypes.c_int
         lib.gip_raster_backward_profiled.argtypes = lib.gip_raster_backward.argtypes + [ctypes.POINTER(ctypes.c_float)]
+        # bucket mode (a per-tile key bucket of `bucket_stride` entries behind the dense layout; 0 = dense): additive entry points
+        _u32 = ctypes.c_uint32
+        lib.gip_raster_state_bytes_buckets.restype = ctypes.c_size_t
+        lib.gip_raster_state_bytes_buckets.argtypes = [ctypes.POINTER(GipRasterConfig), _u32]
+        lib.gip_raster_state_layout_buckets.restype = ctypes.c_int
+        lib.gip_raster_state_layout_buckets.argtypes = [ctypes.POINTER(GipRasterConfig), _u32, ctypes.POINTER(GipRasterStateLayout),
+                                                        ctypes.POINTER(ctypes.c_size_t)]
+        lib.gip_raster_forward_buckets.restype = ctypes.c_int
+        lib.gip_raster_forward_buckets.argtypes = lib.gip_raster_forward.argtypes + [_u32]
+        lib.gip_raster_backward_buckets.restype = ctypes.c_int
+        lib.gip_raster_backward_buckets.argtypes = lib.gip_raster_backward.argtypes + [_u32]
+        lib.gip_raster_forward_buckets_profiled.restype = ctypes.c_int
+        lib.gip_raster_forward_buckets_profiled.argtypes = lib.gip_raster_forward.argtypes + [_u32, ctypes.POINTER(ctypes.c_float)]
+        lib.gip_raster_backward_buckets_profiled.restype = ctypes.c_int
+        lib.gip_raster_backward_buckets_profiled.argtypes = lib.gip_raster_backward.argtypes + [_u32, ctypes.POINTER(ctypes.c_float)]
         lib.gip_raster_read_header.restype = ctypes.c_int
         lib.gip_raster_read_header.argtypes = [_vp, _vp, _vp]
         lib.gip_raster_mark_visible.restype = ctypes.c_int
@@ -412,7 +431,9 @@ def status_string(rc):
 
 RASTER_SYMBOLS = ["gip_abi_version", "gip_status_string", "gip_raster_state_bytes", "gip_raster_scratch_bytes",
                   "gip_raster_state_layout", "gip_raster_forward", "gip_raster_backward", "gip_raster_read_header",
-                  "gip_raster_mark_visible", "gip_raster_forward_profiled", "gip_raster_backward_profiled"]
+                  "gip_raster_mark_visible", "gip_raster_forward_profiled", "gip_raster_backward_profiled",
+                  "gip_raster_state_bytes_buckets", "gip_raster_state_layout_buckets", "gip_raster_forward_buckets",
+                  "gip_raster_backward_buckets", "gip_raster_forward_buckets_profiled", "gip_raster_backward_buckets_profiled"]
 FIELD_SYMBOLS = ["gip_field_workspace_size", "gip_density_field", "gip_surface_count", "gip_surface_emit"]
 SAMPLE_SYMBOLS = ["gip_field_sample_workspace_size", "gip_field_sample"]
 TEXTURE_SYMBOLS = ["gip_texture_bake_workspace_size", "gip_texture_bake"]

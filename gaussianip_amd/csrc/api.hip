@@ -68,6 +68,31 @@ extern "C" int gip_raster_state_layout(const GipRasterConfig* c, GipRasterStateL
   return GIP_OK;
 }
 
+// Bucket mode: the per-tile buckets lie BEHIND the dense layout's end, so every offset above holds in both modes.
+// A stride is a whole number of 256-byte lines (32 keys); 0 = dense.
+static bool valid_stride(const GipRasterConfig* c, uint32_t S) {
+  if (S == 0) return true;
+  if (S % 32u) return false;
+  const size_t T = (size_t)((c->W + GIP_TILE - 1) / GIP_TILE) * ((c->H + GIP_TILE - 1) / GIP_TILE);
+  return (size_t)c->V * T <= ((size_t)1 << 40) / 8 / S;
+}
+
+extern "C" int gip_raster_state_layout_buckets(const GipRasterConfig* c, uint32_t bucket_stride, GipRasterStateLayout* L,
+                                               size_t* bucket_keys) {
+  int rc = gip_raster_state_layout(c, L);
+  if (rc != GIP_OK) return rc;
+  if (!valid_stride(c, bucket_stride)) return GIP_ERR_BAD_ARGUMENT;
+  if (bucket_keys) *bucket_keys = L->total;
+  L->total += align256((size_t)c->V * L->tiles_x * L->tiles_y * bucket_stride * 8);
+  return GIP_OK;
+}
+
+extern "C" size_t gip_raster_state_bytes_buckets(const GipRasterConfig* c, uint32_t bucket_stride) {
+  GipRasterStateLayout L;
+  if (gip_raster_state_layout_buckets(c, bucket_stride, &L, nullptr) != GIP_OK) return 0;
+  return L.total;
+}
+
 extern "C" size_t gip_raster_state_bytes(const GipRasterConfig* c) {
   GipRasterStateLayout L;
   if (gip_raster_state_layout(c, &L) != GIP_OK) return 0;
@@ -101,7 +126,7 @@ static void fill_params(const GipRasterConfig* c, const GipRasterStateLayout& L,
   }
 }
 
-static GipStatePtrs state_ptrs(void* state, const GipRasterStateLayout& L) {
+static GipStatePtrs state_ptrs(void* state, const GipRasterStateLayout& L, size_t bucket_keys) {
   char* b = (char*)state;
   GipStatePtrs p;
   p.header = (GipRasterHeader*)(b + L.header);
@@ -114,7 +139,7 @@ static GipStatePtrs state_ptrs(void* state, const GipRasterStateLayout& L) {
   p.inst_slot = (uint32_t*)(b + L.inst_slot);
   p.block_sums = (uint32_t*)(b + L.block_sums);
   p.block_offset = (uint32_t*)(b + L.block_offset);
-  p.keys = (unsigned long long*)(b + L.keys);
+  p.keys = (unsigned long long*)(b + (bucket_keys ? bucket_keys : L.keys));
   p.n_contrib = (uint32_t*)(b + L.n_contrib);
   p.final_T = (float*)(b + L.final_T);
   p.tile_order = (uint32_t*)(b + L.tile_order);
@@ -181,18 +206,20 @@ struct StageTimer {
 }  // namespace
 
 static int forward_impl(const GipRasterConfig* cfg, const GipRasterInputs* in, const GipRasterOutputs* out,
-                        void* state, size_t state_bytes, void* stream, float* times) {
+                        void* state, size_t state_bytes, void* stream, float* times, uint32_t bucket_stride) {
   if (!valid_config(cfg)) return cfg && (cfg->V > GIP_MAX_VIEWS || cfg->sh_degree > 3) ? GIP_ERR_UNSUPPORTED : GIP_ERR_BAD_ARGUMENT;
   int rc = check_inputs(cfg, in);
   if (rc != GIP_OK) return rc;
   if (!out || !out->color || !out->radii || !out->depth || !out->alpha || !state) return GIP_ERR_BAD_ARGUMENT;
   GipRasterStateLayout L;
-  gip_raster_state_layout(cfg, &L);
+  size_t bucket_keys = 0;
+  if (gip_raster_state_layout_buckets(cfg, bucket_stride, &L, &bucket_keys) != GIP_OK) return GIP_ERR_BAD_ARGUMENT;
   if (state_bytes < L.total) return GIP_ERR_BUFFER_TOO_SMALL;
   GipKernelParams kp;
   fill_params(cfg, L, &kp);
+  kp.bucket_stride = bucket_stride;
   if (!in->shs) kp.sh_mfma = 0;                      // colors_precomp with a stale sh_coeffs: nothing to contract
-  GipStatePtrs st = state_ptrs(state, L);
+  GipStatePtrs st = state_ptrs(state, L, bucket_stride ? bucket_keys : 0);
   st.host_header = out->host_header;
   hipStream_t s = (hipStream_t)stream;
   StageTimer tm(s, times);
@@ -213,10 +240,12 @@ static int forward_impl(const GipRasterConfig* cfg, const GipRasterInputs* in, c
   tm.end(GIP_STAGE_SCAN);
   LAUNCH_CHECK();
   if (cfg->P > 0) {
-    tm.begin(GIP_STAGE_SCATTER);
-    gip_launch_scatter(kp, st, s);
-    tm.end(GIP_STAGE_SCATTER);
-    LAUNCH_CHECK();
+    if (!bucket_stride) {                              // bucket mode: preprocess stored the keys, the scan finished inst_offset
+      tm.begin(GIP_STAGE_SCATTER);
+      gip_launch_scatter(kp, st, s);
+      tm.end(GIP_STAGE_SCATTER);
+      LAUNCH_CHECK();
+    }
     tm.begin(GIP_STAGE_TILE_SORT);
     gip_launch_tile_sort(kp, st, s);
     tm.end(GIP_STAGE_TILE_SORT);
@@ -231,30 +260,42 @@ static int forward_impl(const GipRasterConfig* cfg, const GipRasterInputs* in, c
 
 extern "C" int gip_raster_forward(const GipRasterConfig* cfg, const GipRasterInputs* in, const GipRasterOutputs* out,
                                   void* state, size_t state_bytes, void* stream) {
-  return forward_impl(cfg, in, out, state, state_bytes, stream, nullptr);
+  return forward_impl(cfg, in, out, state, state_bytes, stream, nullptr, 0);
+}
+extern "C" int gip_raster_forward_buckets(const GipRasterConfig* cfg, const GipRasterInputs* in, const GipRasterOutputs* out,
+                                          void* state, size_t state_bytes, void* stream, uint32_t bucket_stride) {
+  return forward_impl(cfg, in, out, state, state_bytes, stream, nullptr, bucket_stride);
+}
+extern "C" int gip_raster_forward_buckets_profiled(const GipRasterConfig* cfg, const GipRasterInputs* in, const GipRasterOutputs* out,
+                                                   void* state, size_t state_bytes, void* stream, uint32_t bucket_stride,
+                                                   float* times_ms) {
+  if (!times_ms) return GIP_ERR_BAD_ARGUMENT;
+  return forward_impl(cfg, in, out, state, state_bytes, stream, times_ms, bucket_stride);
 }
 extern "C" int gip_raster_forward_profiled(const GipRasterConfig* cfg, const GipRasterInputs* in, const GipRasterOutputs* out,
                                            void* state, size_t state_bytes, void* stream, float* times_ms) {
   if (!times_ms) return GIP_ERR_BAD_ARGUMENT;
-  return forward_impl(cfg, in, out, state, state_bytes, stream, times_ms);
+  return forward_impl(cfg, in, out, state, state_bytes, stream, times_ms, 0);
 }
 
 static int backward_impl(const GipRasterConfig* cfg, const GipRasterInputs* in, const GipRasterGradsIn* gin,
                          const void* state, size_t state_bytes, void* scratch, size_t scratch_bytes,
-                         const GipRasterGradsOut* gout, void* stream, float* times) {
+                         const GipRasterGradsOut* gout, void* stream, float* times, uint32_t bucket_stride) {
   if (!valid_config(cfg)) return GIP_ERR_BAD_ARGUMENT;
   int rc = check_inputs(cfg, in);
   if (rc != GIP_OK) return rc;
   if (!gin || !gin->alpha || !gin->color || !gin->depth || !gout || !state || !scratch) return GIP_ERR_BAD_ARGUMENT;
   if (cfg->forward_only) return GIP_ERR_BAD_ARGUMENT;      // that forward kept nothing for a backward
   GipRasterStateLayout L;
-  gip_raster_state_layout(cfg, &L);
+  size_t bucket_keys = 0;
+  if (gip_raster_state_layout_buckets(cfg, bucket_stride, &L, &bucket_keys) != GIP_OK) return GIP_ERR_BAD_ARGUMENT;
   if (state_bytes < L.total || scratch_bytes < gip_raster_scratch_bytes(cfg)) return GIP_ERR_BUFFER_TOO_SMALL;
   if (cfg->P == 0) return GIP_OK;
   GipKernelParams kp;
   fill_params(cfg, L, &kp);
+  kp.bucket_stride = bucket_stride;
   if (!in->shs) kp.sh_mfma = 0;
-  GipStatePtrs st = state_ptrs(const_cast<void*>(state), L);
+  GipStatePtrs st = state_ptrs(const_cast<void*>(state), L, bucket_stride ? bucket_keys : 0);
   hipStream_t s = (hipStream_t)stream;
   StageTimer tm(s, times);
   tm.begin(GIP_STAGE_RENDER_BWD);
@@ -274,13 +315,25 @@ static int backward_impl(const GipRasterConfig* cfg, const GipRasterInputs* in, 
 extern "C" int gip_raster_backward(const GipRasterConfig* cfg, const GipRasterInputs* in, const GipRasterGradsIn* gin,
                                    const void* state, size_t state_bytes, void* scratch, size_t scratch_bytes,
                                    const GipRasterGradsOut* gout, void* stream) {
-  return backward_impl(cfg, in, gin, state, state_bytes, scratch, scratch_bytes, gout, stream, nullptr);
+  return backward_impl(cfg, in, gin, state, state_bytes, scratch, scratch_bytes, gout, stream, nullptr, 0);
+}
+extern "C" int gip_raster_backward_buckets(const GipRasterConfig* cfg, const GipRasterInputs* in, const GipRasterGradsIn* gin,
+                                           const void* state, size_t state_bytes, void* scratch, size_t scratch_bytes,
+                                           const GipRasterGradsOut* gout, void* stream, uint32_t bucket_stride) {
+  return backward_impl(cfg, in, gin, state, state_bytes, scratch, scratch_bytes, gout, stream, nullptr, bucket_stride);
+}
+extern "C" int gip_raster_backward_buckets_profiled(const GipRasterConfig* cfg, const GipRasterInputs* in, const GipRasterGradsIn* gin,
+                                                    const void* state, size_t state_bytes, void* scratch, size_t scratch_bytes,
+                                                    const GipRasterGradsOut* gout, void* stream, uint32_t bucket_stride,
+                                                    float* times_ms) {
+  if (!times_ms) return GIP_ERR_BAD_ARGUMENT;
+  return backward_impl(cfg, in, gin, state, state_bytes, scratch, scratch_bytes, gout, stream, times_ms, bucket_stride);
 }
 extern "C" int gip_raster_backward_profiled(const GipRasterConfig* cfg, const GipRasterInputs* in, const GipRasterGradsIn* gin,
                                             const void* state, size_t state_bytes, void* scratch, size_t scratch_bytes,
                                             const GipRasterGradsOut* gout, void* stream, float* times_ms) {
   if (!times_ms) return GIP_ERR_BAD_ARGUMENT;
-  return backward_impl(cfg, in, gin, state, state_bytes, scratch, scratch_bytes, gout, stream, times_ms);
+  return backward_impl(cfg, in, gin, state, state_bytes, scratch, scratch_bytes, gout, stream, times_ms, 0);
 }
 
 extern "C" int gip_raster_read_header(const void* state, GipRasterHeader* host_header, void* stream) {

@@ -9,7 +9,9 @@
 //   2. gip_scan_kernel              exclusive scan of the V*T tile counts -> ranges; longest-first launch order; scan of
 //                                   the per-workgroup tiles_touched sums -> instance offsets; header
 //   3. gip_scatter_kernel           every (Gaussian, tile) instance takes a slot in its tile's bucket
-//                                   (one returning integer atomic) and stores key = depth_bits<<32 | index
+//                                   (one returning integer atomic) and stores key = depth_bits<<32 | index.  Dense layout only:
+//                                   in bucket mode (GipKernelParams::bucket_stride) a tile's list has a fixed address, preprocess
+//                                   stores the keys itself, the scan launch finishes inst_offset, and this launch does not run
 //   4. gip_tile_sort_kernel /       per-tile sort of the bucket (bitonic network on u64, all-ascending "flip" form so any
 //      gip_tile_sort_long_kernel    length works without padding): a wave sorts lists < 512 entirely in registers with
 //                                   DPP / ds_bpermute lane exchanges; longer lists combine those wave blocks through LDS
@@ -36,6 +38,7 @@
 #define SCAN_THREADS 1024
 #define SCAN_WAVES (SCAN_THREADS / 64)
 #define SCAN_CHUNK SCAN_THREADS        // tiles per workgroup
+#define SCAN_FIN 32                    // 256-Gaussian blocks per inst_offset workgroup (bucket mode), <= 64
 
 __device__ __forceinline__ uint32_t nseg_of(uint32_t count) { return (count + GIP_SEGMENT - 1) / GIP_SEGMENT; }
 
@@ -72,7 +75,8 @@ gip_scan_kernel(GipKernelParams kp, const uint32_t* __restrict__ tile_count, con
                 uint32_t* __restrict__ tile_start,
                 uint32_t* __restrict__ seg_start, uint32_t* __restrict__ ckpt_start,
                 const uint32_t* __restrict__ block_sums, uint32_t* __restrict__ block_offset,
-                uint32_t* __restrict__ tile_order, GipRasterHeader* __restrict__ header, uint32_t* __restrict__ host_header) {
+                uint32_t* __restrict__ tile_order, GipRasterHeader* __restrict__ header, uint32_t* __restrict__ host_header,
+                uint32_t* __restrict__ inst_offset) {
   __shared__ uint32_t s_w[SCAN_WAVES];
   __shared__ uint32_t s_acc[2][3 + ORDER_CLASSES];       // [before | total][count, segments, checkpoints, classes 0..5]
   __shared__ uint32_t s_max;
@@ -80,6 +84,36 @@ gip_scan_kernel(GipKernelParams kp, const uint32_t* __restrict__ tile_count, con
   const int n = kp.V * kp.T;
   const int n_chunks = (n + SCAN_CHUNK - 1) / SCAN_CHUNK;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int nb_chunks = kp.V * kp.nblk > 0 ? (kp.V * kp.nblk + SCAN_CHUNK - 1) / SCAN_CHUNK : 1;
+  if ((int)blockIdx.x >= n_chunks + nb_chunks) {
+    // ---- bucket mode only: inst_offset without a scatter pass.  Preprocess left every Gaussian's exclusive prefix of
+    //      tiles_touched inside its 256-Gaussian block; a workgroup per SCAN_FIN blocks adds the blocks' offsets in place.
+    //      Like the workgroups below it sums everything before its blocks itself (no dependency on another workgroup).
+    __shared__ uint32_t s_fin[SCAN_FIN];
+    const int nb = kp.V * kp.nblk;
+    const int j0 = ((int)blockIdx.x - n_chunks - nb_chunks) * SCAN_FIN;
+    uint32_t before = 0;
+    for (int i = tid; i < j0; i += SCAN_THREADS) before += block_sums[i];
+    before = wave_sum_u32(before);
+    if (tid == 0) s_max = 0u;
+    __syncthreads();
+    if (lane == 0) atomicAdd(&s_max, before);
+    __syncthreads();
+    if (wave == 0) {
+      const int i = j0 + lane;
+      const uint32_t x = (lane < SCAN_FIN && i < nb) ? block_sums[i] : 0u;
+      const uint32_t incl = gip_wave_incl_scan_u32(x);
+      if (lane < SCAN_FIN) s_fin[lane] = s_max + incl - x;
+    }
+    __syncthreads();
+    for (int b = tid / GIP_BLOCK; b < SCAN_FIN; b += SCAN_THREADS / GIP_BLOCK) {
+      const int i = j0 + b;
+      if (i >= nb) break;
+      const int v = i / kp.nblk, idx = (i - v * kp.nblk) * GIP_BLOCK + (tid & (GIP_BLOCK - 1));
+      if (idx < kp.P) inst_offset[(size_t)v * kp.P + idx] += s_fin[b];
+    }
+    return;
+  }
   if ((int)blockIdx.x >= n_chunks) {
     // ---- instance offsets: exclusive scan of the per-256-Gaussian sums of tiles_touched (V * nblk entries), the same way: a
     //      workgroup per 1024-entry chunk sums everything BEFORE its chunk itself (coalesced, 8 loads in flight), then scans its
@@ -197,15 +231,18 @@ gip_scan_kernel(GipKernelParams kp, const uint32_t* __restrict__ tile_count, con
     header->class_end[3] = n0 + n1 + n2 + n3 + n4;      // sort phase B: 1..511 = [class_end[0], class_end[3]); beyond: empty tiles
     header->abi_version = GIP_ABI_VERSION;
     header->num_rendered = total;
-    header->overflow = (total > kp.capacity) ? 1u : 0u;
+    // bucket mode: a list longer than its bucket was cut short by preprocess — the same verdict as too many rows
+    const uint32_t over = (total > kp.capacity || (kp.bucket_stride && s_max > kp.bucket_stride)) ? 1u : 0u;
+    header->overflow = over;
     header->max_tile_count = s_max;
+    header->reserved[0] = kp.bucket_stride;
     header->num_segments = s_acc[1][1];
     header->num_checkpoints = s_acc[1][2];
     if (host_header) {      // pinned host mirror: the caller's capacity check needs no device-to-host copy
       // (no system-scope fence here: the host reads the mirror only after an event recorded behind this kernel, and the
       // kernel's completion releases its stores; the fence held the last workgroup for a PCIe round trip)
       host_header[0] = GIP_ABI_VERSION; host_header[1] = total;
-      host_header[2] = (total > kp.capacity) ? 1u : 0u; host_header[3] = s_max;
+      host_header[2] = over; host_header[3] = s_max; host_header[4] = kp.bucket_stride;
     }
   }
 }
@@ -213,8 +250,10 @@ gip_scan_kernel(GipKernelParams kp, const uint32_t* __restrict__ tile_count, con
 void gip_launch_scan(const GipKernelParams& kp, GipStatePtrs st, hipStream_t s) {
   const int n = kp.V * kp.T, nb = kp.V * kp.nblk;
   const int n_chunks = (n + SCAN_CHUNK - 1) / SCAN_CHUNK, b_chunks = nb > 0 ? (nb + SCAN_CHUNK - 1) / SCAN_CHUNK : 1;
-  hipLaunchKernelGGL(gip_scan_kernel, dim3(n_chunks + b_chunks), dim3(SCAN_THREADS), 0, s, kp, st.tile_count, st.tile_count_b, st.tile_start,
-                     st.seg_start, st.ckpt_start, st.block_sums, st.block_offset, st.tile_order, st.header, st.host_header);
+  const int f_chunks = kp.bucket_stride ? (nb + SCAN_FIN - 1) / SCAN_FIN : 0;      // bucket mode: inst_offset is finished here
+  hipLaunchKernelGGL(gip_scan_kernel, dim3(n_chunks + b_chunks + f_chunks), dim3(SCAN_THREADS), 0, s, kp, st.tile_count, st.tile_count_b, st.tile_start,
+                     st.seg_start, st.ckpt_start, st.block_sums, st.block_offset, st.tile_order, st.header, st.host_header,
+                     st.inst_offset);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -617,14 +656,13 @@ gip_tile_sort_kernel(GipKernelParams kp, GipRasterHeader* __restrict__ header, c
       if (pos >= end_a) break;
       const uint32_t t = tile_order[pos];
       const uint32_t start = tile_start[t];
-      uint32_t end = tile_start[t + 1];
-      if (end > kp.capacity) end = kp.capacity;
-      if (end <= start) continue;
-      const uint32_t n = end - start;
+      const uint32_t n = gip_list_len(kp, start, tile_start[t + 1]);
+      if (n == 0) continue;
+      unsigned long long* a = keys + gip_list_base(kp, t, start);
       write_seg_tiles<LONG_THREADS>(kp, seg_start, seg_tile, t, n);
       if (n <= 1) continue;
-      if (n <= LONG_CHUNK) lds_sort<LONG_THREADS>(s_long, n, keys + start, keys + start);
-      else sort_beyond_lds(keys + start, n, s_long);
+      if (n <= LONG_CHUNK) lds_sort<LONG_THREADS>(s_long, n, a, a);
+      else sort_beyond_lds(a, n, s_long);
     }
   }
   // ---- phase M: quarter (256 threads) per tile, four tiles per draw ----
@@ -641,11 +679,9 @@ gip_tile_sort_kernel(GipKernelParams kp, GipRasterHeader* __restrict__ header, c
       if (pos < end_m) {
         const uint32_t t = tile_order[pos];
         const uint32_t start = tile_start[t];
-        uint32_t end = tile_start[t + 1];
-        if (end > kp.capacity) end = kp.capacity;
-        if (end > start) {
-          n = end - start;
-          a = keys + start;
+        n = gip_list_len(kp, start, tile_start[t + 1]);
+        if (n > 0) {
+          a = keys + gip_list_base(kp, t, start);
           const uint32_t s0 = seg_start[t], ns = (n + GIP_SEGMENT - 1) / GIP_SEGMENT;
           for (uint32_t b = threadIdx.x & 255; b < ns; b += 256)
             if (s0 + b < kp.seg_capacity) seg_tile[s0 + b] = t;
@@ -661,16 +697,14 @@ gip_tile_sort_kernel(GipKernelParams kp, GipRasterHeader* __restrict__ header, c
   for (uint32_t pos = end_m + (threadIdx.x >> 6) * gridDim.x + blockIdx.x; pos < end_b; pos += gridDim.x * waves_per_wg) {
     const uint32_t t = tile_order[pos];
     const uint32_t start = tile_start[t];
-    uint32_t end = tile_start[t + 1];
-    if (end > kp.capacity) end = kp.capacity;
-    if (end <= start) continue;
-    const uint32_t n = end - start;
+    const uint32_t n = gip_list_len(kp, start, tile_start[t + 1]);
+    if (n == 0) continue;
     {
       const uint32_t s0 = seg_start[t], ns = (n + GIP_SEGMENT - 1) / GIP_SEGMENT;
       for (uint32_t b = lane; b < ns; b += 64)
         if (s0 + b < kp.seg_capacity) seg_tile[s0 + b] = t;
     }
-    unsigned long long* a = keys + start;
+    unsigned long long* a = keys + gip_list_base(kp, t, start);
     if (n <= 1) continue;
     if (n <= 64) wave_sort_tile<1>(a, n, lane);
     else if (n <= 128) wave_sort_tile<2>(a, n, lane);

@@ -49,6 +49,8 @@ struct GipKernelParams {
   int forward_only;         // GipRasterConfig::forward_only: nothing is kept for a backward
   int sh_mfma;              // SH colours / their backward on the matrix cores (sh_mfma.hip): shs given, degree >= 1, V >= 2, !sh_scalar
   int antialiasing;         // GipRasterConfig::antialiasing: opacity-compensated 2-D filter (preprocess.hip, gather_backward.hip)
+  uint32_t bucket_stride;   // 0: dense key layout (a tile's list at its scanned prefix).  S > 0: bucket mode, tile vt's list at
+                            // keys[vt * S ..): preprocess stores the keys itself and no scatter pass runs (gip_list_base below)
   GipViewConst view[GIP_MAX_VIEWS];
 };
 
@@ -63,7 +65,7 @@ struct GipStatePtrs {
   uint32_t* inst_slot;      // [V,P,GIP_SLOTS]
   uint32_t* block_sums;     // [V*nblk]
   uint32_t* block_offset;   // [V*nblk+1]
-  unsigned long long* keys; // [capacity]
+  unsigned long long* keys; // [capacity]; bucket mode: [V*T*bucket_stride], behind the dense layout's end
   uint32_t* n_contrib;      // [V,H,W]
   float* final_T;           // [V,H,W]
   uint32_t* tile_order;     // [V*T] heavy-first launch order
@@ -89,6 +91,18 @@ void gip_launch_mark_visible(int P, const float* means3D, const float* view, uin
 
 // --- device helpers ---------------------------------------------------------------------------
 #ifdef __HIPCC__
+// Tile vt's list of keys.  Its length is the scanned count tile_start[vt + 1] - tile_start[vt] in both layouts, cut where the
+// rows / checkpoints end (capacity) and, in bucket mode, at the bucket's end; only its first key's address differs.
+__device__ __forceinline__ uint32_t gip_list_len(const GipKernelParams& kp, uint32_t start, uint32_t end) {
+  if (end > kp.capacity) end = kp.capacity;
+  uint32_t n = end > start ? end - start : 0u;
+  if (kp.bucket_stride && n > kp.bucket_stride) n = kp.bucket_stride;
+  return n;
+}
+__device__ __forceinline__ size_t gip_list_base(const GipKernelParams& kp, uint32_t vt, uint32_t start) {
+  return kp.bucket_stride ? (size_t)vt * kp.bucket_stride : (size_t)start;
+}
+
 // Wave64 inclusive sum via DPP row shifts + row broadcasts (no LDS traffic).
 __device__ __forceinline__ uint32_t gip_wave_incl_scan_u32(uint32_t v) {
   // log-step scan with shuffles; hipcc lowers constant-offset __shfl_up to DPP / ds_bpermute

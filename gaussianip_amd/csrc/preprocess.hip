@@ -58,7 +58,8 @@ gip_preprocess_kernel(GipKernelParams kp, const float* __restrict__ means3D, con
                       int32_t* __restrict__ radii, GipRecord* __restrict__ records,
                       uint32_t* __restrict__ tile_count, uint32_t* __restrict__ tile_count_b,
                       uint32_t* __restrict__ inst_slot, uint32_t* __restrict__ block_sums,
-                      GipRasterHeader* __restrict__ header, const float* __restrict__ sh_colors) {
+                      GipRasterHeader* __restrict__ header, const float* __restrict__ sh_colors,
+                      unsigned long long* __restrict__ bucket_keys, uint32_t* __restrict__ inst_offset) {
   const int v = blockIdx.y;
   const int idx = blockIdx.x * PRE_THREADS + threadIdx.x;
   const float* view = viewmatrix + 16 * v;   // wave-uniform -> scalar loads
@@ -254,6 +255,10 @@ gip_preprocess_kernel(GipKernelParams kp, const float* __restrict__ means3D, con
   // tile's range for the whole workgroup, and slot = range base + rank inside the workgroup.  Neighbouring Gaussians
   // share tiles: 256 per table cut the atomics 3x on the limb-ordered bench scene, 1024 per table 8x (5-15x more when the
   // model is Morton-ordered); it costs a few LDS operations per instance otherwise.
+  // Bucket mode (kp.bucket_stride = S): tile t's list lives at bucket_keys[(v T + t) S ..), so the slot IS the key's final
+  // place before the sort and the key is stored here, where the dense layout needs the scanned prefix and a scatter launch.
+  // One counter per tile: the instances beyond the remembered slots draw theirs with a returning atomic of their own on the
+  // same word, after the flush (no table entry, no tile_count_b); a slot >= S is dropped and the scan flags the overflow.
   {
     constexpr int HT = 8192;
     __shared__ uint32_t s_key[HT], s_cnt[HT];
@@ -286,7 +291,7 @@ gip_preprocess_kernel(GipKernelParams kp, const float* __restrict__ means3D, con
             const uint32_t packed = (h << 16) | (atomicAdd(&s_cnt[h], 1u) & 0xffffu);   // rank < 8192
 #pragma unroll
             for (int kk = 0; kk < GIP_SLOTS; kk++) if (kk == k_cur) slots[kk] = packed;
-          } else {
+          } else if (!kp.bucket_stride) {
             // instances beyond the remembered slots only count.  When their tile is already in the table (a neighbour's
             // — or this Gaussian's own — remembered instance put it there) they count in the HIGH half of its word (a
             // workgroup adds at most 1024 to a tile) and ride in that tile's flush; else one global atomic.  They never
@@ -329,21 +334,51 @@ gip_preprocess_kernel(GipKernelParams kp, const float* __restrict__ means3D, con
 #pragma unroll
       for (int k = 0; k < GIP_SLOTS; k++)
         if (k < ntiles) slots[k] = s_cnt[slots[k] >> 16] + (slots[k] & 0xffffu);
-      uint4* sp = reinterpret_cast<uint4*>(inst_slot + ((size_t)v * kp.P + idx) * GIP_SLOTS);
-      sp[0] = make_uint4(slots[0], slots[1], slots[2], slots[3]);
-      if (ntiles > 4) sp[1] = make_uint4(slots[4], slots[5], slots[6], slots[7]);
+      if (kp.bucket_stride) {
+        // second walk of the rectangle (as the scatter pass does: cheaper in registers than eight remembered tile indices)
+        const uint32_t S = kp.bucket_stride;
+        const unsigned long long key = ((unsigned long long)__float_as_uint(rec.depth) << 32) | (uint32_t)idx;
+        unsigned long long* bk = bucket_keys + (size_t)v * kp.T * S;
+        const int area = (rmaxx - rminx) * (rmaxy - rminy);
+        int k = 0, kt = 0;
+        for (int ty = rminy; ty < rmaxy; ty++)
+          for (int tx = rminx; tx < rmaxx; tx++, kt++) {
+            if (!gip_rect_has(rec.tmask, area, kt)) continue;
+            const int k_cur = k++;
+            const uint32_t tile = (uint32_t)(ty * gx + tx);
+            uint32_t slot = 0;
+            if (k_cur < GIP_SLOTS) {
+#pragma unroll
+              for (int kk = 0; kk < GIP_SLOTS; kk++) if (kk == k_cur) slot = slots[kk];
+            } else {
+              slot = atomicAdd(&tc[tile], 1u);
+            }
+            if (slot < S) bk[(size_t)tile * S + slot] = key;
+          }
+      } else {
+        uint4* sp = reinterpret_cast<uint4*>(inst_slot + ((size_t)v * kp.P + idx) * GIP_SLOTS);
+        sp[0] = make_uint4(slots[0], slots[1], slots[2], slots[3]);
+        if (ntiles > 4) sp[1] = make_uint4(slots[4], slots[5], slots[6], slots[7]);
+      }
     }
   }
 
   // per-256-Gaussian-block sums of tiles_touched (feed the instance-offset scan) + visible count
   constexpr int PRE_WAVES = PRE_THREADS / 64, PRE_SUB = PRE_THREADS / GIP_BLOCK;
   __shared__ uint32_t s_sum[PRE_WAVES], s_vis[PRE_WAVES];
-  uint32_t t = rec.tiles, vis = rec.radius > 0 ? 1u : 0u;
+  uint32_t vis = rec.radius > 0 ? 1u : 0u;
+  const uint32_t incl = gip_wave_incl_scan_u32(rec.tiles);           // lane 63: the wave's sum
 #pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) { t += __shfl_xor(t, d, 64); vis += __shfl_xor(vis, d, 64); }
+  for (int d = 32; d >= 1; d >>= 1) vis += __shfl_xor(vis, d, 64);
   const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) { s_sum[wave] = t; s_vis[wave] = vis; }
+  if ((threadIdx.x & 63) == 63) { s_sum[wave] = incl; s_vis[wave] = vis; }
   __syncthreads();
+  if (kp.bucket_stride && idx < kp.P) {
+    // no scatter pass: the exclusive prefix inside the 256-Gaussian block goes out here, the scan adds the block's offset
+    uint32_t pre = incl - rec.tiles;
+    for (int w = wave & ~(GIP_BLOCK / 64 - 1); w < wave; w++) pre += s_sum[w];
+    inst_offset[(size_t)v * kp.P + idx] = pre;
+  }
   if (threadIdx.x < PRE_SUB) {
     const int blk = blockIdx.x * PRE_SUB + threadIdx.x;              // the 256-Gaussian block the scan / scatter kernels index by
     const int w0 = threadIdx.x * (GIP_BLOCK / 64);
@@ -362,7 +397,7 @@ void gip_launch_preprocess(const GipKernelParams& kp, const GipRasterInputs& in,
   hipLaunchKernelGGL(gip_preprocess_kernel, grid, block, 0, s, kp, in.means3D, in.shs, in.colors_precomp, in.opacities,
                      in.scales, in.rotations, in.cov3D_precomp, in.viewmatrix, in.projmatrix, in.campos, radii,
                      st.records, st.tile_count, st.tile_count_b, st.inst_slot, st.block_sums, st.header,
-                     kp.sh_mfma ? st.sh_colors : nullptr);
+                     kp.sh_mfma ? st.sh_colors : nullptr, st.keys, st.inst_offset);
 }
 
 // mark_visible: the fork's checkFrustum (view-space z > 0.2).

@@ -184,9 +184,8 @@ gip_render_backward_kernel(GipKernelParams kp, const GipRasterHeader* __restrict
     const uint32_t vt = seg_tile[seg];
     const uint32_t b = seg - seg_start[vt];              // segment index inside the tile
     const uint32_t start = tile_start[vt];
-    uint32_t end = tile_start[vt + 1];
-    if (end > kp.capacity) end = kp.capacity;
-    if (end < start) end = start;
+    const uint32_t end = start + gip_list_len(kp, start, tile_start[vt + 1]);
+    const unsigned long long* lkeys = keys + gip_list_base(kp, vt, start);
     const int first = (int)(b * GIP_SEGMENT);            // list positions [first, last) of this segment
     const int last = min((int)(end - start), first + GIP_SEGMENT);
     const uint32_t v = vt / kp.T, tile = vt - v * kp.T;
@@ -246,7 +245,7 @@ gip_render_backward_kernel(GipKernelParams kp, const GipRasterHeader* __restrict
 #pragma unroll
     for (int c = 0; c < GIP_SEGMENT / 64; c++) {
       const int i = first + c * 64 + lane;
-      gk[c] = i < last ? (uint32_t)keys[start + i] : 0xffffffffu;
+      gk[c] = i < last ? (uint32_t)lkeys[i] : 0xffffffffu;
     }
     float4 r0 = make_float4(0.f, 0.f, 0.f, 0.f), r1 = r0, r2 = r0;
     uint4 r3 = make_uint4(0, 0, 0, 0);

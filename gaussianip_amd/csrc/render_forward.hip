@@ -85,9 +85,8 @@ gip_render_forward_kernel(GipKernelParams kp, const uint32_t* __restrict__ tile_
   const int cpix = ((((ly >> 3) << 1) | (lx >> 3)) << 6) | ((ly & 7) << 3) | (lx & 7);
 
   const uint32_t start = tile_start[vt];
-  uint32_t end = tile_start[vt + 1];
-  if (end > kp.capacity) end = kp.capacity;
-  if (end < start) end = start;
+  const uint32_t end = start + gip_list_len(kp, start, tile_start[vt + 1]);
+  const unsigned long long* lkeys = keys + gip_list_base(kp, vt, start);      // the list's first key
   const GipRecord* recs = records + (size_t)v * kp.P;
 
   // Every 64-entry chunk of the staged arrays is preceded by a NULL entry (opacity 0 => alpha 0 => skipped by the
@@ -119,8 +118,8 @@ gip_render_forward_kernel(GipKernelParams kp, const uint32_t* __restrict__ tile_
   // while batch b is blended, so the dependent key -> record gather never stalls the blend loop
   uint32_t g_next = 0xffffffffu, g_next2 = 0xffffffffu;
   float4 r0 = make_float4(0.f, 0.f, 0.f, 0.f), r1 = r0, r2 = r0;
-  if (start + threadIdx.x < end) g_next = (uint32_t)keys[start + threadIdx.x];
-  if (start + FWD_THREADS + threadIdx.x < end) g_next2 = (uint32_t)keys[start + FWD_THREADS + threadIdx.x];
+  if (start + threadIdx.x < end) g_next = (uint32_t)lkeys[threadIdx.x];
+  if (start + FWD_THREADS + threadIdx.x < end) g_next2 = (uint32_t)lkeys[FWD_THREADS + threadIdx.x];
   if (g_next != 0xffffffffu) {
     const float4* rp = reinterpret_cast<const float4*>(recs + g_next);
     r0 = rp[0]; r1 = rp[1]; r2 = rp[2];
@@ -169,7 +168,7 @@ gip_render_forward_kernel(GipKernelParams kp, const uint32_t* __restrict__ tile_
     }
     // issue the loads of the following batches (consumed one / two iterations from now)
     g_next = g_next2;
-    g_next2 = (k + 2 * FWD_THREADS < end) ? (uint32_t)keys[k + 2 * FWD_THREADS] : 0xffffffffu;
+    g_next2 = (k + 2 * FWD_THREADS < end) ? (uint32_t)lkeys[k - start + 2 * FWD_THREADS] : 0xffffffffu;
     if (g_next != 0xffffffffu) {
       const float4* rp = reinterpret_cast<const float4*>(recs + g_next);
       r0 = rp[0]; r1 = rp[1]; r2 = rp[2];

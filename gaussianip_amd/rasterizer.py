@@ -19,6 +19,11 @@ An overflowed training forward never aborts the run and never desynchronises a m
 write ZERO gradients (the step degenerates to a zero-gradient step on every rank alike), the host reads the header one
 step late, raises the hint, counts the event in `overflow_events` and warns.  `GIP_RASTER_ON_OVERFLOW=raise` restores
 the exception.  No-grad calls (output renders) are checked immediately and re-run at the exact requirement.
+
+Key layout: the first call of a shape bins through the dense layout (scan -> scatter launch); from then on every tile's keys
+live in a fixed bucket sized from the longest list the shape has had (`bucket_stride`), the preprocess kernel stores them
+itself and the scatter launch does not run (`GIP_RASTER_BUCKETS=0`: always dense).  Results are bit-identical; a list that
+outgrows its bucket is an overflow like the capacity's, with its own warning.
 """
 import ctypes
 import os
@@ -53,7 +58,8 @@ class GaussianRasterizationSettings(NamedTuple):
 _MIN_CAPACITY = 1 << 20
 _CAPACITY_MARGIN = 65536
 _capacity_hint = {}     # (device index, P, V, H, W) -> last observed num_rendered
-_pending_checks = []    # [event, pinned header, key, capacity] of deferred-check forwards whose header is not read yet
+_bucket_hint = {}       # _bucket_key(that key) -> longest tile list observed so far (GipRasterHeader::max_tile_count): only ever raised
+_pending_checks = []    # [event, pinned header, key, capacity, bucket stride, bucket key] of deferred-check forwards whose header is not read yet
 overflow_events = 0     # forwards that overflowed their capacity hint (their steps ran with zero gradients)
 
 
@@ -87,6 +93,55 @@ def _pick_capacity(key, P, V):
     if last is None:
         return None  # unknown: first call learns it synchronously
     return int(max(_MIN_CAPACITY, 3 * last + _CAPACITY_MARGIN))
+
+
+# ---------------------------------------------------------------------------------------------
+# bucket mode: every tile's keys at a fixed address (tile * stride), written by preprocess itself — no scatter launch.
+# Needs the longest list in advance, so it follows the capacity protocol: a hint from the previous call of the shape, an
+# overflow flag when a list outgrew its bucket (zero-gradient step, warning, hint raised), dense when there is no hint.
+# ---------------------------------------------------------------------------------------------
+_BUCKET_BYTES = 2 << 30
+
+
+def _buckets_enabled():
+    """GIP_RASTER_BUCKETS=0: always the dense key layout (scan -> scatter), the layout of a shape's first call."""
+    return os.environ.get("GIP_RASTER_BUCKETS", "1") != "0"
+
+
+def _bucket_budget():
+    """GIP_RASTER_BUCKET_BYTES: most bytes the buckets of one launch set may take (default 2 GiB); beyond it the call is dense."""
+    return int(os.environ.get("GIP_RASTER_BUCKET_BYTES", str(_BUCKET_BYTES)))
+
+
+def bucket_stride(last_max):
+    """Entries per bucket for a shape whose longest list so far was `last_max`: the smallest ODD multiple of 32 entries (256 bytes)
+    that is >= 2 * last_max + 64.  Odd, so that the buckets' first lines do not all fall on the same memory channels."""
+    m = (2 * int(last_max) + 64 + 31) // 32
+    return 32 * (m | 1)
+
+
+def _bucket_key(key):
+    """The capacity key plus the list mode: exact lists are several times longer than the default ones (the capacity hint's
+    3x margin covers that switch, the bucket stride's 2x does not), so each mode learns its own longest list."""
+    return key + (_exact_lists(),)
+
+
+def _learn_longest_list(bkey, max_tile):
+    """The hint is the longest list seen for the key and is never lowered: the cameras of a training run change from step to
+    step (distance 1.3-1.7, field of view 40-70 degrees), and with them the longest list by more than the stride's factor of
+    two, while a bucket's unused tail costs address space only.  (The capacity hint follows the last call instead: its rows are
+    written.)"""
+    _bucket_hint[bkey] = max(_bucket_hint.get(bkey, 0), int(max_tile))
+
+
+def _pick_stride(bkey, V, H, W):
+    """The policy: 0 = dense."""
+    last = _bucket_hint.get(bkey)
+    if last is None or not _buckets_enabled():
+        return 0
+    S = bucket_stride(last)
+    T = ((H + 15) // 16) * ((W + 15) // 16)
+    return S if V * T * S * 8 <= _bucket_budget() else 0
 
 
 _dummy = {}
@@ -146,11 +201,13 @@ def _check(rc, what):
 
 
 def _run_forward(plan, capacity, forward_only=False):
+    """`plan.bucket_stride` (set by the policy; absent or 0 = dense) chooses the key layout."""
     lib = _lib.raster_lib()
+    stride = int(getattr(plan, "bucket_stride", 0))
     dev = plan.means3D.device
     cfg = _make_config(plan.P, plan.V, plan.H, plan.W, plan.sh_degree, plan.M, plan.scale_modifier, plan.tanfovx,
                        plan.tanfovy, capacity, plan.prefiltered, plan.debug, forward_only, plan.antialiasing)
-    nbytes = lib.gip_raster_state_bytes(ctypes.byref(cfg))
+    nbytes = lib.gip_raster_state_bytes_buckets(ctypes.byref(cfg), stride) if stride else lib.gip_raster_state_bytes(ctypes.byref(cfg))
     if nbytes == 0:
         raise ValueError("invalid rasterizer configuration (P=%d V=%d H=%d W=%d sh_degree=%d)" %
                          (plan.P, plan.V, plan.H, plan.W, plan.sh_degree))
@@ -167,9 +224,12 @@ def _run_forward(plan, capacity, forward_only=False):
     outs = _lib.GipRasterOutputs(_ptr(color), _ptr(radii), _ptr(depth), _ptr(alpha),
                                  ctypes.c_void_p(plan.host_header.data_ptr()))
     stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    rc = lib.gip_raster_forward(ctypes.byref(cfg), ctypes.byref(ins), ctypes.byref(outs), _ptr(state), nbytes, stream)
+    if stride:
+        rc = lib.gip_raster_forward_buckets(ctypes.byref(cfg), ctypes.byref(ins), ctypes.byref(outs), _ptr(state), nbytes, stream, stride)
+    else:
+        rc = lib.gip_raster_forward(ctypes.byref(cfg), ctypes.byref(ins), ctypes.byref(outs), _ptr(state), nbytes, stream)
     _check(rc, "gip_raster_forward")
-    plan.cfg, plan.state, plan.capacity = cfg, state, capacity
+    plan.cfg, plan.state, plan.capacity, plan.bucket_stride = cfg, state, capacity, stride
     return color, radii, depth, alpha
 
 
@@ -208,14 +268,20 @@ def _settle(entry):
     """Reads a completed header copy: teaches the capacity policy the real size; reports an overflow.  Returns the
     overflow flag."""
     global overflow_events
-    ev, host, key, cap = entry
-    num_rendered, overflow = int(host[1]), int(host[2])
+    ev, host, key, cap, stride, bkey = entry
+    num_rendered, overflow, max_tile = int(host[1]), int(host[2]), int(host[3])
     _capacity_hint[key] = max(num_rendered, 1)
+    _learn_longest_list(bkey, max_tile)
     if overflow:
         overflow_events += 1
-        msg = ("gaussianip_amd rasterizer: %d tile instances exceeded the capacity hint %d; that forward's images are "
-               "truncated and its backward produced zero gradients (zero-gradient step). The hint has been raised." %
-               (num_rendered, cap))
+        if num_rendered > cap or not stride:
+            msg = ("gaussianip_amd rasterizer: %d tile instances exceeded the capacity hint %d; that forward's images are "
+                   "truncated and its backward produced zero gradients (zero-gradient step). The hint has been raised." %
+                   (num_rendered, cap))
+        else:
+            msg = ("gaussianip_amd rasterizer: a tile list of %d entries outgrew its bucket of %d; that forward's images are "
+                   "truncated and its backward produced zero gradients (zero-gradient step). The bucket hint has been raised." %
+                   (max_tile, stride))
         if _on_overflow() == "raise":
             raise RuntimeError(msg + " (GIP_RASTER_ON_OVERFLOW=raise)")
         warnings.warn(msg, RuntimeWarning, stacklevel=3)
@@ -257,21 +323,25 @@ def _forward_with_policy(plan, need_backward, forward_only=False):
     if cap is None:
         cap = max(_MIN_CAPACITY, 8 * plan.P * plan.V)
     while True:
+        bkey = _bucket_key(key)
+        stride = plan.bucket_stride = _pick_stride(bkey, plan.V, plan.H, plan.W)
         outs = _run_forward(plan, cap, forward_only and os.environ.get("GIP_RASTER_FORWARD_ONLY", "1") != "0")
         ev, host = _read_header_async(plan)
         if not sync_now:
-            plan.pending = [ev, host, key, cap]
+            plan.pending = [ev, host, key, cap, stride, bkey]
             _pending_checks.append(plan.pending)
             _header_owner[plan.header_slot] = plan.pending
             return outs
         ev.synchronize()
         num_rendered, overflow = int(host[1]), int(host[2])
         _capacity_hint[key] = max(num_rendered, 1)
+        _learn_longest_list(bkey, int(host[3]))
         if not overflow:
             plan.pending = None
             plan.num_rendered = num_rendered
             return outs
-        cap = int(num_rendered * 1.25) + 65536  # exact requirement is known: re-run once
+        if num_rendered > cap:
+            cap = int(num_rendered * 1.25) + 65536  # exact requirement is known: re-run once (the bucket stride follows its hint)
 
 
 def _verify_pending(plan):
@@ -315,8 +385,12 @@ def _run_backward(plan, outs, g_color, g_depth, g_alpha):
                                   _ptr(g["opacities"]), _ptr(g["scales"]), _ptr(g["rotations"]),
                                   _ptr(g["cov3D_precomp"]))
     stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    rc = lib.gip_raster_backward(ctypes.byref(cfg), ctypes.byref(ins), ctypes.byref(gin), _ptr(plan.state),
-                                 plan.state.numel(), _ptr(scratch), sbytes, ctypes.byref(gout), stream)
+    if plan.bucket_stride:
+        rc = lib.gip_raster_backward_buckets(ctypes.byref(cfg), ctypes.byref(ins), ctypes.byref(gin), _ptr(plan.state),
+                                             plan.state.numel(), _ptr(scratch), sbytes, ctypes.byref(gout), stream, plan.bucket_stride)
+    else:
+        rc = lib.gip_raster_backward(ctypes.byref(cfg), ctypes.byref(ins), ctypes.byref(gin), _ptr(plan.state),
+                                     plan.state.numel(), _ptr(scratch), sbytes, ctypes.byref(gout), stream)
     _check(rc, "gip_raster_backward")
     return g
 
@@ -485,10 +559,14 @@ class GaussianRasterizer(torch.nn.Module):
 # state inspection (tests / parity of the tile & index buffers)
 # ---------------------------------------------------------------------------------------------
 def state_views(plan):
-    """Decode a forward's state buffer into named torch views (no copies)."""
+    """Decode a forward's state buffer into named torch views (no copies) — the dense view of either key layout: in bucket
+    mode `keys` is a copy compacted from the buckets to the positions `tile_start` gives."""
     lib = _lib.raster_lib()
     L = _lib.GipRasterStateLayout()
-    _check(lib.gip_raster_state_layout(ctypes.byref(plan.cfg), ctypes.byref(L)), "gip_raster_state_layout")
+    S = int(getattr(plan, "bucket_stride", 0))
+    bucket_off = ctypes.c_size_t(0)
+    _check(lib.gip_raster_state_layout_buckets(ctypes.byref(plan.cfg), S, ctypes.byref(L), ctypes.byref(bucket_off)),
+           "gip_raster_state_layout_buckets")
     st = plan.state
     V, P, H, W = plan.V, plan.P, plan.H, plan.W
     T = L.tiles_x * L.tiles_y
@@ -497,14 +575,27 @@ def state_views(plan):
         nbytes = count * torch.empty((), dtype=dtype).element_size()
         return st[off:off + nbytes].view(dtype).reshape(shape)
 
+    tile_start = view(L.tile_start, V * T + 1, torch.int32, (V * T + 1,))
+    if S:
+        buckets = view(bucket_off.value, V * T * S, torch.int64, (V * T * S,))
+        ts = tile_start.long()
+        n = min(int(ts[-1]), int(plan.capacity))
+        pos = torch.arange(n, device=st.device)
+        vt = torch.searchsorted(ts[1:].contiguous(), pos, right=True)
+        off = pos - ts[vt]
+        keys = torch.zeros(int(plan.capacity), dtype=torch.int64, device=st.device)
+        ok = off < S
+        keys[:n][ok] = buckets[(vt * S + off)[ok]]
+    else:
+        keys = view(L.keys, int(plan.capacity), torch.int64, (int(plan.capacity),))
     return dict(
         header=view(L.header, 16, torch.int32, (16,)),
         records=view(L.records, V * P * 16, torch.float32, (V, P, 16)),
         records_u32=view(L.records, V * P * 16, torch.int32, (V, P, 16)),
         inst_offset=view(L.inst_offset, V * P, torch.int32, (V, P)),
         tile_count=view(L.tile_count, V * T, torch.int32, (V, T)),
-        tile_start=view(L.tile_start, V * T + 1, torch.int32, (V * T + 1,)),
-        keys=view(L.keys, int(plan.capacity), torch.int64, (int(plan.capacity),)),
+        tile_start=tile_start,
+        keys=keys,
         n_contrib=view(L.n_contrib, V * H * W, torch.int32, (V, H, W)),
         tiles_x=L.tiles_x, tiles_y=L.tiles_y)
 
@@ -532,6 +623,9 @@ def profile_stages(means3D, opacities, settings_list, g_color, g_depth=None, g_a
     _validate(shs, colors_precomp, scales, rotations, cov3D_precomp)
     plan = _build_plan(means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, list(settings_list))
     (color, radii, depth, alpha) = _forward_with_policy(plan, False)   # sizes the capacity synchronously
+    if not plan.bucket_stride and _pick_stride(_bucket_key(_hint_key(plan.means3D.device, plan.P, plan.V, plan.H, plan.W)), plan.V, plan.H, plan.W):
+        (color, radii, depth, alpha) = _forward_with_policy(plan, False)   # the first call of a shape is dense: profile what follows it
+    S = plan.bucket_stride
     dev = plan.means3D.device
     cfg = plan.cfg
     V, P, M = plan.V, plan.P, plan.M
@@ -555,11 +649,18 @@ def profile_stages(means3D, opacities, settings_list, g_color, g_depth=None, g_a
     for it in range(iters + 1):
         for i in range(len(STAGE_NAMES)):
             times[i] = 0.0
-        _check(lib.gip_raster_forward_profiled(ctypes.byref(cfg), ctypes.byref(ins), ctypes.byref(outs),
-                                               _ptr(plan.state), plan.state.numel(), stream, times), "forward_profiled")
-        _check(lib.gip_raster_backward_profiled(ctypes.byref(cfg), ctypes.byref(ins), ctypes.byref(gin),
-                                                _ptr(plan.state), plan.state.numel(), _ptr(scratch), sbytes,
-                                                ctypes.byref(gout), stream, times), "backward_profiled")
+        if S:           # the stage that did not run (scatter) keeps its 0
+            _check(lib.gip_raster_forward_buckets_profiled(ctypes.byref(cfg), ctypes.byref(ins), ctypes.byref(outs),
+                                                           _ptr(plan.state), plan.state.numel(), stream, S, times), "forward_profiled")
+            _check(lib.gip_raster_backward_buckets_profiled(ctypes.byref(cfg), ctypes.byref(ins), ctypes.byref(gin),
+                                                            _ptr(plan.state), plan.state.numel(), _ptr(scratch), sbytes,
+                                                            ctypes.byref(gout), stream, S, times), "backward_profiled")
+        else:
+            _check(lib.gip_raster_forward_profiled(ctypes.byref(cfg), ctypes.byref(ins), ctypes.byref(outs),
+                                                   _ptr(plan.state), plan.state.numel(), stream, times), "forward_profiled")
+            _check(lib.gip_raster_backward_profiled(ctypes.byref(cfg), ctypes.byref(ins), ctypes.byref(gin),
+                                                    _ptr(plan.state), plan.state.numel(), _ptr(scratch), sbytes,
+                                                    ctypes.byref(gout), stream, times), "backward_profiled")
         if it > 0:  # first iteration is warm-up
             for i in range(len(STAGE_NAMES)):
                 acc[i] += float(times[i])

@@ -47,7 +47,8 @@ extern "C" {
 #define GIP_SEGMENT 64
 #endif
 //#define GIP_SEGMENT_DOC        /* list entries per backward work item; forward checkpoints every GIP_SEGMENT entries */
-#define GIP_SLOTS 8            /* bucket slots remembered per (view, Gaussian): scatter needs no second atomic for these */
+#define GIP_SLOTS 8            /* bucket slots remembered per (view, Gaussian): no second atomic for these (dense layout: the scatter
+                                  pass reads them from inst_slot; bucket mode: preprocess stores the keys at them itself) */
 #define GIP_CKPT_FLOATS 5      /* per pixel per checkpoint: T, C.r, C.g, C.b, D */
 
 /* status codes */
@@ -119,7 +120,7 @@ typedef struct GipRasterOutputs {
   float*   depth;  /* [V,1,H,W] */
   float*   alpha;  /* [V,1,H,W] */
   uint32_t* host_header; /* optional (null = unused): 16 x u32 of PINNED, device-mapped HOST memory.  The binning stage
-                            stores {abi_version, num_rendered, overflow, max_tile_count} there as soon as the totals
+                            stores {abi_version, num_rendered, overflow, max_tile_count, bucket stride} there as soon as the totals
                             are known, so the caller learns the capacity verdict from an event on `stream` without
                             enqueueing a device-to-host copy (the reference instead blocks on a D2H read of
                             num_rendered inside every forward). */
@@ -154,7 +155,8 @@ typedef struct GipRasterHeader {
   uint32_t abi_version;
   uint32_t num_rendered;   /* total (tile, Gaussian) instances required, over all views (of the rectangles described
                               at the record layout below: <= the fork's num_rendered) */
-  uint32_t overflow;       /* 1 if num_rendered > capacity: outputs are invalid, re-run with more */
+  uint32_t overflow;       /* 1 if num_rendered > capacity — or, in bucket mode, max_tile_count > the bucket stride: outputs are
+                              invalid, re-run with more */
   uint32_t max_tile_count; /* longest per-tile list */
   uint32_t num_visible;    /* Gaussians with radii > 0, over all views */
   uint32_t num_segments;   /* sum over tiles of ceil(count / GIP_SEGMENT): work items of the backward replay */
@@ -162,7 +164,7 @@ typedef struct GipRasterHeader {
   uint32_t class_end[4];   /* positions in tile_order where the per-tile-sort size classes end: [1] lists >= 2048, [2] >= 1024, [0] >= 512, [3] >= 1 */
   uint32_t sort_cursor;    /* scratch: work counters of the per-tile sort kernel (lists >= 2048 entries, ... */
   uint32_t sort_cursor_m;  /* ... lists of 512..2047 entries) */
-  uint32_t reserved[3];
+  uint32_t reserved[3];    /* [0]: the bucket stride this forward ran with (0 = dense key layout), see gip_raster_forward_buckets */
 } GipRasterHeader;
 
 /* Byte offsets of the sub-buffers inside `state` (for tests, debugging and parity checks of the
@@ -170,15 +172,19 @@ typedef struct GipRasterHeader {
 typedef struct GipRasterStateLayout {
   size_t header;       /* GipRasterHeader */
   size_t records;      /* [V,P] x GIP_RECORD_BYTES */
-  size_t inst_offset;  /* [V,P] u32: exclusive prefix sum of tiles_touched (view-major, global) */
-  size_t tile_count;   /* [V,T] u32: entries per tile drawn through the remembered slots (total = this + tile_count_b) */
+  size_t inst_offset;  /* [V,P] u32: exclusive prefix sum of tiles_touched (view-major, global).  Dense: written by the scatter pass;
+                          bucket mode: preprocess writes the prefix inside each 256-Gaussian block, the scan launch adds block_offset */
+  size_t tile_count;   /* [V,T] u32: entries per tile drawn through the remembered slots (total = this + tile_count_b); bucket mode:
+                          the one counter per tile, every entry */
   size_t tile_start;   /* [V*T+1] u32: exclusive scan of tile_count == ranges[tile].x, ranges[tile].y = next */
-  size_t tile_cursor;  /* [V,T] u32 scratch for bucket fill (instances beyond GIP_SLOTS per Gaussian) */
-  size_t tile_count_b; /* [V,T] u32: part of the per-tile count contributed by instances beyond GIP_SLOTS */
-  size_t inst_slot;    /* [V,P,GIP_SLOTS] u32: bucket slot each of a Gaussian's first GIP_SLOTS instances drew */
+  size_t tile_cursor;  /* [V,T] u32 scratch for bucket fill (instances beyond GIP_SLOTS per Gaussian); bucket mode: stays zero */
+  size_t tile_count_b; /* [V,T] u32: part of the per-tile count contributed by instances beyond GIP_SLOTS; bucket mode: stays zero */
+  size_t inst_slot;    /* [V,P,GIP_SLOTS] u32: bucket slot each of a Gaussian's first GIP_SLOTS instances drew; bucket mode: not written */
   size_t block_sums;   /* [V,ceil(P/256)] u32 */
   size_t block_offset; /* [V*ceil(P/256)+1] u32 */
-  size_t keys;         /* [capacity] u64 sorted per tile: (depth_bits << 32) | gaussian_index */
+  size_t keys;         /* [capacity] u64 sorted per tile: (depth_bits << 32) | gaussian_index, tile t's list at tile_start[t].  Bucket
+                          mode: unused — tile t's list is at bucket_keys[t * stride ..) behind `total` of the dense layout
+                          (gip_raster_state_layout_buckets), the same keys in the same order */
   size_t n_contrib;    /* [V,H,W] u32 */
   size_t final_T;      /* [V,H,W] f32: transmittance after the last blended entry (the fork's final_T) */
   size_t tile_order;   /* [V*T] u32: tile ids, longest lists first (launch order of the render kernels) */
@@ -244,6 +250,35 @@ int gip_raster_forward_profiled(const GipRasterConfig* cfg, const GipRasterInput
 int gip_raster_backward_profiled(const GipRasterConfig* cfg, const GipRasterInputs* in, const GipRasterGradsIn* gin,
                                  const void* state, size_t state_bytes, void* scratch, size_t scratch_bytes,
                                  const GipRasterGradsOut* gout, void* stream, float* times_ms /* [GIP_NUM_STAGES] */);
+
+/* Bucket mode: the same rasterizer with another place for the per-tile key lists.  Tile t (view-major, 0 <= t < V * T) of the
+ * launch set keeps its keys at bucket_keys[t * bucket_stride .. + min(count, bucket_stride)), a fixed address, so the preprocess
+ * kernel stores every key the moment it has drawn the slot and the scatter launch (and inst_slot, tile_cursor, tile_count_b)
+ * drops out of the forward.  Counts, tile_start, seg_start, ckpt_start, tile_order, block_offset, the header and every output are
+ * those of the dense layout bit for bit (keys are unique, so the sorted lists are equal); `capacity` keeps its meaning for the
+ * rows and checkpoints.  A list longer than bucket_stride is cut and sets the header's overflow flag exactly like num_rendered >
+ * capacity does (zero gradients from the backward).  The caller chooses the stride from what it knows of the longest list
+ * (GipRasterHeader::max_tile_count of an earlier call): a multiple of 32 entries; an odd multiple spreads the buckets' first
+ * lines over the memory channels.  bucket_stride = 0 is the dense layout, i.e. the plain entry point.  The state is larger:
+ * gip_raster_state_bytes_buckets; every offset of the dense layout stays valid, the buckets start at *bucket_keys (= the dense
+ * total).  A backward must be given the stride of its forward.  The stride is not a GipRasterConfig field because that struct's
+ * size and GIP_ABI_VERSION are fixed: these entry points are additive. */
+size_t gip_raster_state_bytes_buckets(const GipRasterConfig* cfg, uint32_t bucket_stride);
+int    gip_raster_state_layout_buckets(const GipRasterConfig* cfg, uint32_t bucket_stride, GipRasterStateLayout* out,
+                                       size_t* bucket_keys /* may be null */);
+int gip_raster_forward_buckets(const GipRasterConfig* cfg, const GipRasterInputs* in, const GipRasterOutputs* out,
+                               void* state, size_t state_bytes, void* stream, uint32_t bucket_stride);
+int gip_raster_backward_buckets(const GipRasterConfig* cfg, const GipRasterInputs* in, const GipRasterGradsIn* gin,
+                                const void* state, size_t state_bytes, void* scratch, size_t scratch_bytes,
+                                const GipRasterGradsOut* gout, void* stream, uint32_t bucket_stride);
+/* ... and their measurement variants (GIP_STAGE_SCATTER keeps its slot and is not written when the stage did not run) */
+int gip_raster_forward_buckets_profiled(const GipRasterConfig* cfg, const GipRasterInputs* in, const GipRasterOutputs* out,
+                                        void* state, size_t state_bytes, void* stream, uint32_t bucket_stride,
+                                        float* times_ms /* [GIP_NUM_STAGES] */);
+int gip_raster_backward_buckets_profiled(const GipRasterConfig* cfg, const GipRasterInputs* in, const GipRasterGradsIn* gin,
+                                         const void* state, size_t state_bytes, void* scratch, size_t scratch_bytes,
+                                         const GipRasterGradsOut* gout, void* stream, uint32_t bucket_stride,
+                                         float* times_ms /* [GIP_NUM_STAGES] */);
 
 /* Asynchronously copies the header to `host_header` ([host], ideally pinned) on `stream`. */
 int gip_raster_read_header(const void* state, GipRasterHeader* host_header, void* stream);
