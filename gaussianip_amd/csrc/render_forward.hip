@@ -15,17 +15,23 @@
 //   * workgroups are launched longest-list-first (tile_order from the scan kernel);
 //   * the tile's depth-sorted list is consumed in batches of 512: each lane fetches one key, gathers that
 //     Gaussian's 64-byte record with dwordx4 loads, stages the 40 bytes the blend needs into LDS (conic pre-scaled
-//     into the exp2 domain), and computes an 8-bit BLOCK MASK from the tight screen-space extent of the
+//     into the exp2 domain; three arrays of one 16-byte slot stride, back to back, so that one byte offset formed on
+//     the scalar side plus the reads' immediate offsets address an entry), and computes an 8-bit BLOCK MASK from the
+//     tight screen-space extent of the
 //     alpha >= 1/255 ellipse (|dx| <= sqrt(2 ln(255 o) cov_xx), same for y; and distance <= sqrt(t / lambda_min)).  A pair outside that ellipse fails the
 //     reference's alpha < 1/255 test, so skipping it cannot change any output;
 //   * each wave ballots the mask bits of its block and walks only the set bits with scalar find-first-one, two per
-//     step, FWD_PAIRS steps per trip (independent exp / alpha chains), and leaves as soon as all its pixels terminated;
+//     step, FWD_PAIRS steps per trip (independent exp / alpha chains) while more than FWD_PAIRS bits of the 64-entry
+//     chunk remain, then one last trip of 2 steps or 1 (no NULL-padded steps), and leaves as soon as all its pixels
+//     terminated;
 //   * at every GIP_SEGMENT-entry boundary the per-pixel blend state (T, C, D) is checkpointed (20 B / pixel) so
 //     that the backward pass needs no sequential walk over the tile.
 // (A two-pass segment-parallel forward — local blend of every segment + per-tile combine with exact replay of the
 //  segment a pixel terminates in — was built and measured in round 1: 0.44 ms vs 0.40 ms for the then-current kernel
 //  at 100k Gaussians, because the replays of terminating pixels cost what the flat pass saves)
 #include <stdlib.h>
+
+#include <type_traits>
 
 #include "gip_internal.h"
 
@@ -55,6 +61,13 @@ __device__ __forceinline__ int ffs_clear(unsigned long long& m) {
   int j;
   asm volatile("s_ff1_i32_b64 %0, %1\n\ts_bitset0_b64 %1, %0" : "=&s"(j), "+s"(m));
   return j;
+}
+
+// number of set bits of the wave-uniform mask m, on the scalar side (the builtin's 64-bit result is compared on the vector side)
+__device__ __forceinline__ int popcount64(unsigned long long m) {
+  int n;
+  asm("s_bcnt1_i32_b64 %0, %1" : "=s"(n) : "s"(m) : "scc");
+  return n;
 }
 
 __global__ void __launch_bounds__(FWD_THREADS)
@@ -97,22 +110,30 @@ gip_render_forward_kernel(GipKernelParams kp, const uint32_t* __restrict__ tile_
   // v_pk_add / v_pk_fma (two fp32 per lane) at the rate of one scalar fp32 instruction: (x, y) - (px, py) is one
   // v_pk_add, (a dx, c dy) one v_pk_mul on the adjacent (a, c) pair, the colour / depth sums two v_pk_fma on (r, g), (b, d)
   constexpr int FWD_SLOTS = (FWD_THREADS / 64) * 65;
-  __shared__ v2f s_xy[FWD_SLOTS];
-  __shared__ v4f s_con[FWD_SLOTS];   // conic a, c, b (exp2 domain) + opacity
-  __shared__ v4f s_col[FWD_SLOTS];   // r, g, b + depth
+  // the three staged arrays share the 16-byte slot stride and lie back to back: one byte offset per entry, the arrays at
+  // immediate offsets of the LDS reads (centre: the low 8 bytes of its slot; the high 8 are never read)
+  constexpr int FWD_ARRAY_BYTES = FWD_SLOTS * 16;
+  __shared__ v4f s_stage[3 * FWD_SLOTS];
+  v4f* const s_xy = s_stage;                   // x, y
+  v4f* const s_con = s_stage + FWD_SLOTS;      // conic a, c, b (exp2 domain) + opacity
+  v4f* const s_col = s_stage + 2 * FWD_SLOTS;  // r, g, b + depth
   __shared__ uint32_t s_mask[FWD_THREADS];
   if (threadIdx.x < FWD_THREADS / 64) {
-    s_xy[threadIdx.x * 65] = (v2f){0.f, 0.f};
+    *(v2f*)&s_xy[threadIdx.x * 65] = (v2f){0.f, 0.f};
     s_con[threadIdx.x * 65] = (v4f){0.f, 0.f, 0.f, 0.f};
     s_col[threadIdx.x * 65] = (v4f){0.f, 0.f, 0.f, 0.f};
   }
   const int sidx = threadIdx.x + (threadIdx.x >> 6) + 1;      // staging slot of this thread's entry
+  // all-ones in the lane half that takes a pair's second entry: offset = first + (hsel & (second - first)), the difference
+  // formed on the scalar side.  Opaque to the compiler, which would otherwise turn the AND back into a two-operand select
+  int hsel = -hh;
+  asm volatile("" : "+v"(hsel));
 
   bool done = !inside;
   float T = 1.0f, Wt = 0.f;
   v2f CG = {0.f, 0.f}, BD = {0.f, 0.f};   // (red, green), (blue, depth): this lane half's share of the sums
   uint32_t last_contributor = 0;
-  int last_off = -1;      // byte offset (x16) of the last contributing entry inside the current batch, -1 = none yet
+  int last_off = -1;      // byte offset (x16, from the slot in front) of the last contributing entry inside the current batch, -1 = none yet
 
   // software pipeline over the batches: the key of batch b+2 and the record of batch b+1 are in flight
   // while batch b is blended, so the dependent key -> record gather never stalls the blend loop
@@ -125,12 +146,62 @@ gip_render_forward_kernel(GipKernelParams kp, const uint32_t* __restrict__ tile_
     r0 = rp[0]; r1 = rp[1]; r2 = rp[2];
   }
 
+  // One trip of a wave through its instruction stream: PAIRS pairs of list entries taken from the set bits of m, lanes 0-31
+  // the first entry of a pair, lanes 32-63 the second.  Returns true once every pixel of the wave has terminated.
+  auto trip = [&](auto pairs, unsigned long long& m, const int cbase16) __attribute__((always_inline)) -> bool {
+    constexpr int PAIRS = decltype(pairs)::value;
+    int ja[PAIRS];                                      // byte offset (x16) of the slot in front of this lane half's entry
+    float al[PAIRS];
+    v4f cc[PAIRS];
+#pragma unroll
+    for (int u = 0; u < PAIRS; u++) {
+      // scalar side: byte offsets of the pair's two entries; find-first-one of an empty mask is -1 = the NULL slot
+      const int j1 = ffs_clear(m), j2 = ffs_clear(m);
+      // offsets count from the chunk's NULL slot (j = -1); the entry's own slot is the reads' immediate + 16
+      ja[u] = (cbase16 + j1 * 16) + (hsel & ((j2 - j1) * 16));
+      const char* sp = (const char*)s_stage + ja[u] + 16;
+      const v2f d = *(const v2f*)sp - pxy;                                 // (dx, dy)
+      const v4f co = *(const v4f*)(sp + FWD_ARRAY_BYTES);
+      cc[u] = *(const v4f*)(sp + 2 * FWD_ARRAY_BYTES);
+      const v2f t = co.xy * d;                                       // (a dx, c dy)
+      // log2 domain; same operation sequence as the backward's re-evaluation (render_backward.hip: bwd_pair)
+      const float power = __builtin_fmaf(d.x, __builtin_fmaf(co.z, d.y, t.x), t.y * d.y);
+      const float a = fminf(GIP_ALPHA_MAX, co.w * __builtin_amdgcn_exp2f(power));
+      al[u] = (power <= 0.0f && a >= GIP_ALPHA_MIN) ? a : 0.f;              // 0 = the reference skips this pair
+    }
+    const unsigned long long done_before = __ballot(done);
+#pragma unroll
+    for (int u = 0; u < PAIRS; u++) {
+      float a_e, a_o;                                                      // first / second entry of the pair
+      both32(al[u], a_e, a_o);
+      // the reference's per-entry rule, applied to both entries in order by both lane halves; a terminated pixel
+      // sees alpha 0, which leaves T and the sums unchanged.  T (1 - a) is evaluated as fma(-a, T, T).
+      a_e = done ? 0.f : a_e;
+      const float t1 = __builtin_fmaf(-a_e, T, T);
+      const bool stop1 = t1 < GIP_T_MIN;                                   // only reachable with a_e > 0
+      const float T1 = stop1 ? T : t1;
+      a_o = (done || stop1) ? 0.f : a_o;
+      const float t2 = __builtin_fmaf(-a_o, T1, T1);
+      const bool stop2 = t2 < GIP_T_MIN;
+      const float w_e = stop1 ? 0.f : a_e * T, w_o = stop2 ? 0.f : a_o * T1;
+      const float w = hh ? w_o : w_e;
+      CG = __builtin_elementwise_fma(cc[u].xy, (v2f){w, w}, CG);
+      BD = __builtin_elementwise_fma(cc[u].zw, (v2f){w, w}, BD);
+      Wt += w;
+      last_off = w > 0.f ? ja[u] : last_off;                               // resolved to a list index once per batch
+      T = stop2 ? T1 : t2;
+      done = done || stop1 || stop2;
+    }
+    // wave-uniform; re-test termination only when something changed
+    return __ballot(done) != done_before && __all(done);
+  };
+
   for (uint32_t base = start; base < end; base += FWD_THREADS) {
     if (__syncthreads_count(done) == FWD_THREADS) break;
     const uint32_t k = base + threadIdx.x;
     if (k < end) {
       const float4 q0 = r0, q1 = r1, q2 = r2;
-      s_xy[sidx] = (v2f){q0.x, q0.y};
+      *(v2f*)&s_xy[sidx] = (v2f){q0.x, q0.y};
       // conic pre-scaled into the exp2 domain: power * log2(e) = A dx^2 + B dx dy + C dy^2 (sign tests are unchanged)
       s_con[sidx] = (v4f){q1.x * -0.72134752044448170f, q1.z * -0.72134752044448170f, q1.y * -1.4426950408889634f, q0.w};
       s_col[sidx] = (v4f){q2.x, q2.y, q2.z, q0.z};
@@ -181,7 +252,9 @@ gip_render_forward_kernel(GipKernelParams kp, const uint32_t* __restrict__ tile_
         if (rel != 0 && (rel % GIP_SEGMENT) == 0) {
           // blend state at the start of segment rel / GIP_SEGMENT (>= 1): lets the backward treat every segment of
           // this tile as an independent work item (render_backward.hip).  The two lane halves hold partial sums.
-          const float s0 = CG.x + xchg32(CG.x, hh), s1 = CG.y + xchg32(CG.y, hh), s2 = BD.x + xchg32(BD.x, hh), sd = BD.y + xchg32(BD.y, hh);
+          float lo0, hi0, lo1, hi1, lo2, hi2, lod, hid;
+          both32(CG.x, lo0, hi0); both32(CG.y, lo1, hi1); both32(BD.x, lo2, hi2); both32(BD.y, lod, hid);
+          const float s0 = lo0 + hi0, s1 = lo1 + hi1, s2 = lo2 + hi2, sd = lod + hid;
           const uint32_t slot = ckpt_start[vt] + rel / GIP_SEGMENT - 1;
           // a pixel that has already terminated never reads this row back: the backward only loads the checkpoint of a segment
           // that starts before the pixel's last contributor (render_backward.hip: n_contrib > first), and a terminated pixel's
@@ -194,60 +267,20 @@ gip_render_forward_kernel(GipKernelParams kp, const uint32_t* __restrict__ tile_
         const int e = c0 + lane;
         const uint32_t mk = e < cnt ? s_mask[e] : 0u;
         unsigned long long m = __ballot((mk >> wave) & 1u);
-        const int cbase16 = ((c0 >> 6) * 65 + 1) << 4;
+        const int cbase16 = ((c0 >> 6) * 65) << 4;            // the chunk's NULL slot
         bool wave_done = false;
-        while (m) {
-          // FWD_PAIRS pairs of list entries per trip: lanes 0-31 take the first entry of a pair, lanes 32-63 the second
-          int ja[FWD_PAIRS];                                  // byte offset (x16) of this lane half's entry in the staged arrays
-          float al[FWD_PAIRS];
-          v4f cc[FWD_PAIRS];
-#pragma unroll
-          for (int u = 0; u < FWD_PAIRS; u++) {
-            // scalar side: byte offsets of the pair's two entries; find-first-one of an empty mask is -1 = the NULL slot
-            const int j1 = ffs_clear(m), j2 = ffs_clear(m);
-            const int a1 = cbase16 + (j1 << 4), a2 = cbase16 + (j2 << 4);
-            ja[u] = hh ? a2 : a1;
-            const v2f d = *(const v2f*)((const char*)s_xy + (ja[u] >> 1)) - pxy;        // (dx, dy)
-            const v4f co = *(const v4f*)((const char*)s_con + ja[u]);
-            cc[u] = *(const v4f*)((const char*)s_col + ja[u]);
-            const v2f t = co.xy * d;                                       // (a dx, c dy)
-            // log2 domain; same operation sequence as the backward's re-evaluation (render_backward.hip: bwd_pair)
-            const float power = __builtin_fmaf(d.x, __builtin_fmaf(co.z, d.y, t.x), t.y * d.y);
-            const float a = fminf(GIP_ALPHA_MAX, co.w * __builtin_amdgcn_exp2f(power));
-            al[u] = (power <= 0.0f && a >= GIP_ALPHA_MIN) ? a : 0.f;              // 0 = the reference skips this pair
-          }
-          const unsigned long long done_before = __ballot(done);
-#pragma unroll
-          for (int u = 0; u < FWD_PAIRS; u++) {
-            float a_e, a_o;                                                      // first / second entry of the pair
-            both32(al[u], a_e, a_o);
-            // the reference's per-entry rule, applied to both entries in order by both lane halves; a terminated pixel
-            // sees alpha 0, which leaves T and the sums unchanged.  T (1 - a) is evaluated as fma(-a, T, T).
-            a_e = done ? 0.f : a_e;
-            const float t1 = __builtin_fmaf(-a_e, T, T);
-            const bool stop1 = t1 < GIP_T_MIN;                                   // only reachable with a_e > 0
-            const float T1 = stop1 ? T : t1;
-            a_o = (done || stop1) ? 0.f : a_o;
-            const float t2 = __builtin_fmaf(-a_o, T1, T1);
-            const bool stop2 = t2 < GIP_T_MIN;
-            const float w_e = stop1 ? 0.f : a_e * T, w_o = stop2 ? 0.f : a_o * T1;
-            const float w = hh ? w_o : w_e;
-            CG = __builtin_elementwise_fma(cc[u].xy, (v2f){w, w}, CG);
-            BD = __builtin_elementwise_fma(cc[u].zw, (v2f){w, w}, BD);
-            Wt += w;
-            last_off = w > 0.f ? ja[u] : last_off;                               // resolved to a list index once per batch
-            T = stop2 ? T1 : t2;
-            done = done || stop1 || stop2;
-          }
-          if (__ballot(done) != done_before) {     // wave-uniform; re-test termination only when something changed
-            if (__all(done)) { wave_done = true; break; }
-          }
+        // full trips while more than FWD_PAIRS bits remain, then one last trip sized to what is left (2 pairs for 3-4 bits,
+        // 1 pair for 1-2): a NULL slot only ever fills the second entry of the chunk's last pair
+        while (!wave_done && popcount64(m) > FWD_PAIRS) wave_done = trip(std::integral_constant<int, FWD_PAIRS>(), m, cbase16);
+        if (!wave_done && m) {
+          if (popcount64(m) > 2) wave_done = trip(std::integral_constant<int, 2>(), m, cbase16);
+          else wave_done = trip(std::integral_constant<int, 1>(), m, cbase16);
         }
         if (wave_done) break;
       }
     }
     if (last_off >= 0) {                                // n_contrib = 1-based list position of the last contributor
-      const uint32_t slot = (uint32_t)last_off >> 4;    // slot = chunk * 65 + 1 + position: list index = slot - chunk - 1
+      const uint32_t slot = ((uint32_t)last_off >> 4) + 1;   // slot = chunk * 65 + 1 + position: list index = slot - chunk - 1
       last_contributor = (base - start) + slot - slot / 65u;
       last_off = -1;
     }
