@@ -34,8 +34,18 @@ extern "C" const char* gip_status_string(int status) {
   }
 }
 
-extern "C" int gip_raster_state_layout(const GipRasterConfig* c, GipRasterStateLayout* L) {
-  if (!valid_config(c) || !L) return GIP_ERR_BAD_ARGUMENT;
+// Bucket mode: the per-tile buckets lie BEHIND the dense layout's end, so every offset holds in both modes.
+// A stride is a whole number of 256-byte lines (32 keys); 0 = dense.
+static bool valid_stride(const GipRasterConfig* c, uint32_t S) {
+  if (S == 0) return true;
+  if (S % 32u) return false;
+  const size_t T = (size_t)((c->W + GIP_TILE - 1) / GIP_TILE) * ((c->H + GIP_TILE - 1) / GIP_TILE);
+  return (size_t)c->V * T <= ((size_t)1 << 40) / 8 / S;
+}
+
+extern "C" int gip_raster_state_layout_buckets(const GipRasterConfig* c, uint32_t bucket_stride, GipRasterStateLayout* L,
+                                               size_t* bucket_keys) {
+  if (!valid_config(c) || !L || !valid_stride(c, bucket_stride)) return GIP_ERR_BAD_ARGUMENT;
   memset(L, 0, sizeof(*L));
   const size_t P = (size_t)c->P, V = (size_t)c->V;
   L->tiles_x = (uint32_t)((c->W + GIP_TILE - 1) / GIP_TILE);
@@ -64,26 +74,8 @@ extern "C" int gip_raster_state_layout(const GipRasterConfig* c, GipRasterStateL
   L->checkpoints = off;  off = align256(off + ckpt_cap * GIP_CKPT_FLOATS * 256 * sizeof(float));
   L->keys = off;         off = align256(off + (size_t)c->capacity * 8);
   L->sh_colors = off;    off = align256(off + (sh_mfma_path(c) ? V * P * 4 * sizeof(float) : 0));
-  L->total = off;
-  return GIP_OK;
-}
-
-// Bucket mode: the per-tile buckets lie BEHIND the dense layout's end, so every offset above holds in both modes.
-// A stride is a whole number of 256-byte lines (32 keys); 0 = dense.
-static bool valid_stride(const GipRasterConfig* c, uint32_t S) {
-  if (S == 0) return true;
-  if (S % 32u) return false;
-  const size_t T = (size_t)((c->W + GIP_TILE - 1) / GIP_TILE) * ((c->H + GIP_TILE - 1) / GIP_TILE);
-  return (size_t)c->V * T <= ((size_t)1 << 40) / 8 / S;
-}
-
-extern "C" int gip_raster_state_layout_buckets(const GipRasterConfig* c, uint32_t bucket_stride, GipRasterStateLayout* L,
-                                               size_t* bucket_keys) {
-  int rc = gip_raster_state_layout(c, L);
-  if (rc != GIP_OK) return rc;
-  if (!valid_stride(c, bucket_stride)) return GIP_ERR_BAD_ARGUMENT;
-  if (bucket_keys) *bucket_keys = L->total;
-  L->total += align256((size_t)c->V * L->tiles_x * L->tiles_y * bucket_stride * 8);
+  if (bucket_keys) *bucket_keys = off;
+  L->total = off + align256(V * T * bucket_stride * 8);
   return GIP_OK;
 }
 
@@ -93,11 +85,12 @@ extern "C" size_t gip_raster_state_bytes_buckets(const GipRasterConfig* c, uint3
   return L.total;
 }
 
-extern "C" size_t gip_raster_state_bytes(const GipRasterConfig* c) {
-  GipRasterStateLayout L;
-  if (gip_raster_state_layout(c, &L) != GIP_OK) return 0;
-  return L.total;
+// the plain entry points are the dense layout: stride 0
+extern "C" int gip_raster_state_layout(const GipRasterConfig* c, GipRasterStateLayout* L) {
+  return gip_raster_state_layout_buckets(c, 0, L, nullptr);
 }
+
+extern "C" size_t gip_raster_state_bytes(const GipRasterConfig* c) { return gip_raster_state_bytes_buckets(c, 0); }
 
 extern "C" size_t gip_raster_scratch_bytes(const GipRasterConfig* c) {
   if (!valid_config(c)) return 0;
@@ -150,6 +143,20 @@ static GipStatePtrs state_ptrs(void* state, const GipRasterStateLayout& L, size_
   p.sh_colors = (float*)(b + L.sh_colors);
   p.host_header = nullptr;
   return p;
+}
+
+// What forward and backward do before their first launch: the layout for the stride, the size check, the kernels' parameters
+// and the state's pointers (`keys` = the buckets when there are any).
+static int prepare(const GipRasterConfig* cfg, const GipRasterInputs* in, void* state, size_t state_bytes, uint32_t bucket_stride,
+                   GipRasterStateLayout* L, GipKernelParams* kp, GipStatePtrs* st) {
+  size_t bucket_keys = 0;
+  if (gip_raster_state_layout_buckets(cfg, bucket_stride, L, &bucket_keys) != GIP_OK) return GIP_ERR_BAD_ARGUMENT;
+  if (state_bytes < L->total) return GIP_ERR_BUFFER_TOO_SMALL;
+  fill_params(cfg, *L, kp);
+  kp->bucket_stride = bucket_stride;
+  if (!in->shs) kp->sh_mfma = 0;                     // colors_precomp with a stale sh_coeffs: nothing to contract
+  *st = state_ptrs(state, *L, bucket_stride ? bucket_keys : 0);
+  return GIP_OK;
 }
 
 static int check_inputs(const GipRasterConfig* c, const GipRasterInputs* in) {
@@ -212,14 +219,10 @@ static int forward_impl(const GipRasterConfig* cfg, const GipRasterInputs* in, c
   if (rc != GIP_OK) return rc;
   if (!out || !out->color || !out->radii || !out->depth || !out->alpha || !state) return GIP_ERR_BAD_ARGUMENT;
   GipRasterStateLayout L;
-  size_t bucket_keys = 0;
-  if (gip_raster_state_layout_buckets(cfg, bucket_stride, &L, &bucket_keys) != GIP_OK) return GIP_ERR_BAD_ARGUMENT;
-  if (state_bytes < L.total) return GIP_ERR_BUFFER_TOO_SMALL;
   GipKernelParams kp;
-  fill_params(cfg, L, &kp);
-  kp.bucket_stride = bucket_stride;
-  if (!in->shs) kp.sh_mfma = 0;                      // colors_precomp with a stale sh_coeffs: nothing to contract
-  GipStatePtrs st = state_ptrs(state, L, bucket_stride ? bucket_keys : 0);
+  GipStatePtrs st;
+  rc = prepare(cfg, in, state, state_bytes, bucket_stride, &L, &kp, &st);
+  if (rc != GIP_OK) return rc;
   st.host_header = out->host_header;
   hipStream_t s = (hipStream_t)stream;
   StageTimer tm(s, times);
@@ -287,15 +290,12 @@ static int backward_impl(const GipRasterConfig* cfg, const GipRasterInputs* in, 
   if (!gin || !gin->alpha || !gin->color || !gin->depth || !gout || !state || !scratch) return GIP_ERR_BAD_ARGUMENT;
   if (cfg->forward_only) return GIP_ERR_BAD_ARGUMENT;      // that forward kept nothing for a backward
   GipRasterStateLayout L;
-  size_t bucket_keys = 0;
-  if (gip_raster_state_layout_buckets(cfg, bucket_stride, &L, &bucket_keys) != GIP_OK) return GIP_ERR_BAD_ARGUMENT;
-  if (state_bytes < L.total || scratch_bytes < gip_raster_scratch_bytes(cfg)) return GIP_ERR_BUFFER_TOO_SMALL;
-  if (cfg->P == 0) return GIP_OK;
   GipKernelParams kp;
-  fill_params(cfg, L, &kp);
-  kp.bucket_stride = bucket_stride;
-  if (!in->shs) kp.sh_mfma = 0;
-  GipStatePtrs st = state_ptrs(const_cast<void*>(state), L, bucket_stride ? bucket_keys : 0);
+  GipStatePtrs st;
+  rc = prepare(cfg, in, const_cast<void*>(state), state_bytes, bucket_stride, &L, &kp, &st);
+  if (rc != GIP_OK) return rc;
+  if (scratch_bytes < gip_raster_scratch_bytes(cfg)) return GIP_ERR_BUFFER_TOO_SMALL;
+  if (cfg->P == 0) return GIP_OK;
   hipStream_t s = (hipStream_t)stream;
   StageTimer tm(s, times);
   tm.begin(GIP_STAGE_RENDER_BWD);

@@ -24,6 +24,10 @@ Key layout: the first call of a shape bins through the dense layout (scan -> sca
 live in a fixed bucket sized from the longest list the shape has had (`bucket_stride`), the preprocess kernel stores them
 itself and the scatter launch does not run (`GIP_RASTER_BUCKETS=0`: always dense).  Results are bit-identical; a list that
 outgrows its bucket is an overflow like the capacity's, with its own warning.
+
+Host path: one marshalling of a `_Plan` (`_marshal`, `_backward_buffers`), one launch per direction (`_launch_forward`,
+`_launch_backward`: the stride-taking entry points, stride 0 = dense), one reader of a landed header (`_read_header`, which teaches
+both hints), and one way out of `_pending_checks` for a deferred check (`_settle`).
 """
 import ctypes
 import os
@@ -59,7 +63,7 @@ _MIN_CAPACITY = 1 << 20
 _CAPACITY_MARGIN = 65536
 _capacity_hint = {}     # (device index, P, V, H, W) -> last observed num_rendered
 _bucket_hint = {}       # _bucket_key(that key) -> longest tile list observed so far (GipRasterHeader::max_tile_count): only ever raised
-_pending_checks = []    # [event, pinned header, key, capacity, bucket stride, bucket key] of deferred-check forwards whose header is not read yet
+_pending_checks = []    # the _Pending of every deferred-check forward whose header is not read yet, oldest first
 overflow_events = 0     # forwards that overflowed their capacity hint (their steps ran with zero gradients)
 
 
@@ -88,7 +92,7 @@ def _hint_key(dev, P, V, H, W):
     return (dev.index if dev.index is not None else torch.cuda.current_device(), P, V, H, W)
 
 
-def _pick_capacity(key, P, V):
+def _pick_capacity(key):
     last = _capacity_hint.get(key)
     if last is None:
         return None  # unknown: first call learns it synchronously
@@ -126,14 +130,6 @@ def _bucket_key(key):
     return key + (_exact_lists(),)
 
 
-def _learn_longest_list(bkey, max_tile):
-    """The hint is the longest list seen for the key and is never lowered: the cameras of a training run change from step to
-    step (distance 1.3-1.7, field of view 40-70 degrees), and with them the longest list by more than the stride's factor of
-    two, while a bucket's unused tail costs address space only.  (The capacity hint follows the last call instead: its rows are
-    written.)"""
-    _bucket_hint[bkey] = max(_bucket_hint.get(bkey, 0), int(max_tile))
-
-
 def _pick_stride(bkey, V, H, W):
     """The policy: 0 = dense."""
     last = _bucket_hint.get(bkey)
@@ -159,7 +155,7 @@ def _ptr(t):
     return ctypes.c_void_p(t.data_ptr())
 
 
-def _f32c(t, name, shape_last=None):
+def _f32c(t, name):
     if t is None:
         return None
     if not t.is_cuda:
@@ -170,25 +166,32 @@ def _f32c(t, name, shape_last=None):
 
 
 class _Plan:
-    """Everything one forward/backward pair shares."""
-    pass
+    """Everything one forward/backward pair shares: the call (_build_plan), then what the last forward ran with and learnt."""
+    means3D = shs = colors_precomp = opacities = scales = rotations = cov3D_precomp = None      # contiguous float32 on the device
+    viewmatrix = projmatrix = campos = bg = None        # [V,16], [V,16], [V,3], [3]
+    P = V = H = W = sh_degree = M = 0                   # M: SH coefficients given per channel
+    scale_modifier, tanfovx, tanfovy = 1.0, (), ()      # the tangents per view
+    prefiltered = debug = antialiasing = False
+    bucket_stride = capacity = 0                        # stride 0 = the dense key layout
+    cfg = state = host_header = None                    # host_header: ring slot `header_slot`, where that forward's header lands
+    header_slot = -1
+    dense_first_call = False                            # dense only for want of a hint: the shape's next call is bucketed
+    pending = None                                      # the deferred check, until the backward or a later call settles it
+    num_rendered, overflowed = None, False              # the verdict, once read
 
 
-def _make_config(P, V, H, W, sh_degree, M, scale_modifier, tanfovx, tanfovy, capacity, prefiltered, debug, forward_only=False,
-                 antialiasing=False):
+def _make_config(plan, capacity, forward_only):
     cfg = _lib.GipRasterConfig()
-    cfg.P, cfg.V, cfg.H, cfg.W = int(P), int(V), int(H), int(W)
-    cfg.sh_degree, cfg.sh_coeffs = int(sh_degree), int(M)
-    cfg.prefiltered, cfg.debug = int(bool(prefiltered)), int(bool(debug))
-    cfg.scale_modifier = float(scale_modifier)
-    for v in range(V):
-        cfg.tanfovx[v] = float(tanfovx[v])
-        cfg.tanfovy[v] = float(tanfovy[v])
+    cfg.P, cfg.V, cfg.H, cfg.W = plan.P, plan.V, plan.H, plan.W
+    cfg.sh_degree, cfg.sh_coeffs = plan.sh_degree, plan.M
+    cfg.prefiltered, cfg.debug = int(plan.prefiltered), int(plan.debug)
+    cfg.scale_modifier = plan.scale_modifier
+    cfg.tanfovx[:plan.V], cfg.tanfovy[:plan.V] = plan.tanfovx, plan.tanfovy
     cfg.capacity = int(capacity)
     cfg.exact_lists = 1 if _exact_lists() else 0
     cfg.forward_only = 1 if forward_only else 0
     cfg.sh_scalar = 1 if _sh_scalar() else 0
-    cfg.antialiasing = 1 if antialiasing else 0
+    cfg.antialiasing = 1 if plan.antialiasing else 0
     return cfg
 
 
@@ -200,36 +203,69 @@ def _check(rc, what):
         raise RuntimeError(msg)
 
 
-def _run_forward(plan, capacity, forward_only=False):
-    """`plan.bucket_stride` (set by the policy; absent or 0 = dense) chooses the key layout."""
-    lib = _lib.raster_lib()
-    stride = int(getattr(plan, "bucket_stride", 0))
+# The C-ABI calls.  Always the stride-taking entry points: stride 0 is the dense layout (include/gip_raster.h), and _lib counts
+# a `*_buckets` call under the plain entry point's name as well.
+def _marshal(plan):
+    """The plan as the library takes it: (config of its last forward, inputs, the current stream of its device)."""
+    ins = _lib.GipRasterInputs(_ptr(plan.means3D), _ptr(plan.shs), _ptr(plan.colors_precomp), _ptr(plan.opacities),
+                               _ptr(plan.scales), _ptr(plan.rotations), _ptr(plan.cov3D_precomp),
+                               _ptr(plan.viewmatrix), _ptr(plan.projmatrix), _ptr(plan.campos), _ptr(plan.bg))
+    return plan.cfg, ins, ctypes.c_void_p(torch.cuda.current_stream(plan.means3D.device).cuda_stream)
+
+
+def _backward_buffers(plan):
+    """The backward's scratch, the gradient of every input that was given (by the input's name) and their GipRasterGradsOut."""
     dev = plan.means3D.device
-    cfg = _make_config(plan.P, plan.V, plan.H, plan.W, plan.sh_degree, plan.M, plan.scale_modifier, plan.tanfovx,
-                       plan.tanfovy, capacity, plan.prefiltered, plan.debug, forward_only, plan.antialiasing)
-    nbytes = lib.gip_raster_state_bytes_buckets(ctypes.byref(cfg), stride) if stride else lib.gip_raster_state_bytes(ctypes.byref(cfg))
+    V, P, M = plan.V, plan.P, plan.M
+    scratch = torch.empty(_lib.raster_lib().gip_raster_scratch_bytes(ctypes.byref(plan.cfg)), dtype=torch.uint8, device=dev)
+
+    def mk(like, *shape):
+        return None if like is None else torch.empty(shape, dtype=torch.float32, device=dev)
+
+    g = dict(means3D=mk(plan.means3D, P, 3), means2D=mk(plan.means3D, V, P, 3), shs=mk(plan.shs, P, max(M, 1), 3),
+             colors_precomp=mk(plan.colors_precomp, P, 3), opacities=mk(plan.opacities, P, 1), scales=mk(plan.scales, P, 3),
+             rotations=mk(plan.rotations, P, 4), cov3D_precomp=mk(plan.cov3D_precomp, P, 6))
+    gout = _lib.GipRasterGradsOut(_ptr(g["means3D"]), _ptr(g["means2D"]), _ptr(g["shs"]), _ptr(g["colors_precomp"]),
+                                  _ptr(g["opacities"]), _ptr(g["scales"]), _ptr(g["rotations"]), _ptr(g["cov3D_precomp"]))
+    return scratch, g, gout
+
+
+def _launch_forward(plan, outs, times=None):
+    """`times`: a float array of len(STAGE_NAMES) = the profiled variant (hipEvent pairs around every stage; synchronises)."""
+    lib = _lib.raster_lib()
+    cfg, ins, stream = _marshal(plan)
+    args = (ctypes.byref(cfg), ctypes.byref(ins), ctypes.byref(outs), _ptr(plan.state), plan.state.numel(), stream, plan.bucket_stride)
+    rc = lib.gip_raster_forward_buckets(*args) if times is None else lib.gip_raster_forward_buckets_profiled(*args, times)
+    _check(rc, "gip_raster_forward")
+
+
+def _launch_backward(plan, gin, scratch, gout, times=None):
+    lib = _lib.raster_lib()
+    cfg, ins, stream = _marshal(plan)
+    args = (ctypes.byref(cfg), ctypes.byref(ins), ctypes.byref(gin), _ptr(plan.state), plan.state.numel(), _ptr(scratch), scratch.numel(),
+            ctypes.byref(gout), stream, plan.bucket_stride)
+    rc = lib.gip_raster_backward_buckets(*args) if times is None else lib.gip_raster_backward_buckets_profiled(*args, times)
+    _check(rc, "gip_raster_backward")
+
+
+def _run_forward(plan, capacity, forward_only=False):
+    """`plan.bucket_stride` (set by the policy; 0 = dense) chooses the key layout."""
+    dev = plan.means3D.device
+    plan.capacity = capacity
+    plan.cfg = _make_config(plan, capacity, forward_only)
+    nbytes = _lib.raster_lib().gip_raster_state_bytes_buckets(ctypes.byref(plan.cfg), plan.bucket_stride)
     if nbytes == 0:
         raise ValueError("invalid rasterizer configuration (P=%d V=%d H=%d W=%d sh_degree=%d)" %
                          (plan.P, plan.V, plan.H, plan.W, plan.sh_degree))
-    state = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    plan.state = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     V, P, H, W = plan.V, plan.P, plan.H, plan.W
     color = torch.empty((V, 3, H, W), dtype=torch.float32, device=dev)
     depth = torch.empty((V, 1, H, W), dtype=torch.float32, device=dev)
     alpha = torch.empty((V, 1, H, W), dtype=torch.float32, device=dev)
     radii = torch.empty((V, P), dtype=torch.int32, device=dev)
-    ins = _lib.GipRasterInputs(_ptr(plan.means3D), _ptr(plan.shs), _ptr(plan.colors_precomp), _ptr(plan.opacities),
-                               _ptr(plan.scales), _ptr(plan.rotations), _ptr(plan.cov3D_precomp),
-                               _ptr(plan.viewmatrix), _ptr(plan.projmatrix), _ptr(plan.campos), _ptr(plan.bg))
     plan.header_slot, plan.host_header = _header_slot()
-    outs = _lib.GipRasterOutputs(_ptr(color), _ptr(radii), _ptr(depth), _ptr(alpha),
-                                 ctypes.c_void_p(plan.host_header.data_ptr()))
-    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    if stride:
-        rc = lib.gip_raster_forward_buckets(ctypes.byref(cfg), ctypes.byref(ins), ctypes.byref(outs), _ptr(state), nbytes, stream, stride)
-    else:
-        rc = lib.gip_raster_forward(ctypes.byref(cfg), ctypes.byref(ins), ctypes.byref(outs), _ptr(state), nbytes, stream)
-    _check(rc, "gip_raster_forward")
-    plan.cfg, plan.state, plan.capacity, plan.bucket_stride = cfg, state, capacity, stride
+    _launch_forward(plan, _lib.GipRasterOutputs(_ptr(color), _ptr(radii), _ptr(depth), _ptr(alpha),
+                                                ctypes.c_void_p(plan.host_header.data_ptr())))
     return color, radii, depth, alpha
 
 
@@ -240,7 +276,18 @@ def _run_forward(plan, capacity, forward_only=False):
 _HEADER_SLOTS = 64
 _header_ring = None
 _header_next = 0
-_header_owner = [None] * _HEADER_SLOTS      # pending entry that still has to read slot i
+_header_owner = [None] * _HEADER_SLOTS      # the last _Pending deferred on slot i
+
+
+class _Pending:
+    """The deferred check of one forward: what `_settle` needs once the header has landed in its slot."""
+    __slots__ = ("event", "header", "slot", "key", "bucket_key", "capacity", "stride", "settled")
+
+    def __init__(self, event, header, slot, key, bucket_key, capacity, stride):
+        self.event, self.header, self.slot = event, header, slot            # recorded behind the forward; view of ring slot `slot`
+        self.key, self.bucket_key = key, bucket_key                         # of _capacity_hint and _bucket_hint
+        self.capacity, self.stride = capacity, stride                       # what the forward ran with
+        self.settled = False                                                # read and reported: no longer in _pending_checks
 
 
 def _header_slot():
@@ -250,57 +297,60 @@ def _header_slot():
     i = _header_next
     _header_next = (i + 1) % _HEADER_SLOTS
     owner = _header_owner[i]
-    if owner is not None and any(e is owner for e in _pending_checks):
-        owner[0].synchronize()              # 64 forwards ago and still unread: settle it before the slot is reused
-        _pending_checks[:] = [e for e in _pending_checks if e is not owner]
-        _settle(owner)
+    if owner is not None and not owner.settled:
+        _settle(owner, wait=True)           # 64 forwards ago and still unread: settle it before the slot is reused
     _header_owner[i] = None
     return i, _header_ring[i]
 
 
-def _read_header_async(plan):
-    ev = torch.cuda.Event()
-    ev.record(torch.cuda.current_stream(plan.means3D.device))
-    return ev, plan.host_header
+def _defer(p):
+    _pending_checks.append(p)
+    _header_owner[p.slot] = p
 
 
-def _settle(entry):
-    """Reads a completed header copy: teaches the capacity policy the real size; reports an overflow.  Returns the
-    overflow flag."""
-    global overflow_events
-    ev, host, key, cap, stride, bkey = entry
-    num_rendered, overflow, max_tile = int(host[1]), int(host[2]), int(host[3])
+def _read_header(header, key, bkey):
+    """The one reader of a landed header (GipRasterHeader words 1-3) and the one teacher of the two hints.  The capacity hint
+    follows the last call: its rows are written.  The bucket hint is the longest list seen for the key and is never lowered: the
+    cameras of a training run change from step to step (distance 1.3-1.7, field of view 40-70 degrees), and with them the longest
+    list by more than the stride's factor of two, while a bucket's unused tail costs address space only.
+    Returns (num_rendered, overflow, max_tile_count)."""
+    num_rendered, overflow, max_tile = int(header[1]), int(header[2]), int(header[3])
     _capacity_hint[key] = max(num_rendered, 1)
-    _learn_longest_list(bkey, max_tile)
+    _bucket_hint[bkey] = max(_bucket_hint.get(bkey, 0), max_tile)
+    return num_rendered, bool(overflow), max_tile
+
+
+def _settle(p, wait):
+    """The one way out of `_pending_checks`: reads the header of a deferred check whose event is complete (`wait`: waits for it
+    first) and reports an overflow.  Returns (num_rendered, overflow)."""
+    global overflow_events
+    if wait:
+        p.event.synchronize()
+    p.settled = True
+    _pending_checks.remove(p)
+    num_rendered, overflow, max_tile = _read_header(p.header, p.key, p.bucket_key)
     if overflow:
         overflow_events += 1
-        if num_rendered > cap or not stride:
+        if num_rendered > p.capacity or not p.stride:
             msg = ("gaussianip_amd rasterizer: %d tile instances exceeded the capacity hint %d; that forward's images are "
                    "truncated and its backward produced zero gradients (zero-gradient step). The hint has been raised." %
-                   (num_rendered, cap))
+                   (num_rendered, p.capacity))
         else:
             msg = ("gaussianip_amd rasterizer: a tile list of %d entries outgrew its bucket of %d; that forward's images are "
                    "truncated and its backward produced zero gradients (zero-gradient step). The bucket hint has been raised." %
-                   (max_tile, stride))
+                   (max_tile, p.stride))
         if _on_overflow() == "raise":
             raise RuntimeError(msg + " (GIP_RASTER_ON_OVERFLOW=raise)")
         warnings.warn(msg, RuntimeWarning, stacklevel=3)
-    return num_rendered, bool(overflow)
+    return num_rendered, overflow
 
 
 def _drain_pending(block=False):
     """Settles the deferred checks of earlier forwards whose header copy has landed — including grad-enabled renders
     that were never back-propagated (their check would otherwise never run)."""
-    i = 0
-    while i < len(_pending_checks):
-        entry = _pending_checks[i]
-        if block or entry[0].query():
-            if block:
-                entry[0].synchronize()
-            _pending_checks.pop(i)
-            _settle(entry)
-        else:
-            i += 1
+    for p in list(_pending_checks):
+        if block or p.event.query():
+            _settle(p, wait=block)
 
 
 def settle_pending():
@@ -317,81 +367,45 @@ def _forward_with_policy(plan, need_backward, forward_only=False):
     """`forward_only`: the state will never be handed to the backward (a render under torch.no_grad()): the kernel skips what
     only the backward reads (GipRasterConfig::forward_only).  Not set by forward_with_state, whose callers inspect the state."""
     _drain_pending()
-    key = _hint_key(plan.means3D.device, plan.P, plan.V, plan.H, plan.W)
-    cap = _pick_capacity(key, plan.P, plan.V)
+    dev = plan.means3D.device
+    key = _hint_key(dev, plan.P, plan.V, plan.H, plan.W)
+    cap = _pick_capacity(key)
     sync_now = _strict() or cap is None or not need_backward
     if cap is None:
         cap = max(_MIN_CAPACITY, 8 * plan.P * plan.V)
     while True:
         bkey = _bucket_key(key)
-        stride = plan.bucket_stride = _pick_stride(bkey, plan.V, plan.H, plan.W)
+        unhinted = bkey not in _bucket_hint
+        plan.bucket_stride = _pick_stride(bkey, plan.V, plan.H, plan.W)
         outs = _run_forward(plan, cap, forward_only and os.environ.get("GIP_RASTER_FORWARD_ONLY", "1") != "0")
-        ev, host = _read_header_async(plan)
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(dev))
         if not sync_now:
-            plan.pending = [ev, host, key, cap, stride, bkey]
-            _pending_checks.append(plan.pending)
-            _header_owner[plan.header_slot] = plan.pending
+            plan.pending = _Pending(ev, plan.host_header, plan.header_slot, key, bkey, cap, plan.bucket_stride)
+            _defer(plan.pending)
             return outs
         ev.synchronize()
-        num_rendered, overflow = int(host[1]), int(host[2])
-        _capacity_hint[key] = max(num_rendered, 1)
-        _learn_longest_list(bkey, int(host[3]))
+        plan.num_rendered, overflow, _ = _read_header(plan.host_header, key, bkey)
         if not overflow:
             plan.pending = None
-            plan.num_rendered = num_rendered
+            plan.dense_first_call = unhinted and _pick_stride(bkey, plan.V, plan.H, plan.W) != 0
             return outs
-        if num_rendered > cap:
-            cap = int(num_rendered * 1.25) + 65536  # exact requirement is known: re-run once (the bucket stride follows its hint)
+        if plan.num_rendered > cap:
+            cap = int(plan.num_rendered * 1.25) + 65536  # exact requirement is known: re-run once (the bucket stride follows its hint)
 
 
 def _verify_pending(plan):
     """Deferred overflow check, run once the backward kernels are enqueued (see _RasterizeGaussians.backward)."""
-    entry = getattr(plan, "pending", None)
-    if entry is None:
-        return
-    plan.pending = None
-    for i, e in enumerate(_pending_checks):
-        if e is entry:
-            _pending_checks.pop(i)
-            break
-    else:
-        return                      # already settled by _drain_pending
-    entry[0].synchronize()
-    plan.num_rendered, plan.overflowed = _settle(entry)
+    p, plan.pending = plan.pending, None
+    if p is not None and not p.settled:     # else: checked at once, or settled already by a later call
+        plan.num_rendered, plan.overflowed = _settle(p, wait=True)
 
 
 def _run_backward(plan, outs, g_color, g_depth, g_alpha):
-    lib = _lib.raster_lib()
-    dev = plan.means3D.device
-    V, P, M = plan.V, plan.P, plan.M
-    cfg = plan.cfg
-    sbytes = lib.gip_raster_scratch_bytes(ctypes.byref(cfg))
-    scratch = torch.empty(sbytes, dtype=torch.uint8, device=dev)
-
-    def mk(flag, shape):
-        return torch.empty(shape, dtype=torch.float32, device=dev) if flag else None
-
-    g = dict(means3D=mk(True, (P, 3)), means2D=mk(True, (V, P, 3)),
-             shs=mk(plan.shs is not None, (P, max(M, 1), 3)),
-             colors_precomp=mk(plan.colors_precomp is not None, (P, 3)), opacities=mk(True, (P, 1)),
-             scales=mk(plan.scales is not None, (P, 3)), rotations=mk(plan.rotations is not None, (P, 4)),
-             cov3D_precomp=mk(plan.cov3D_precomp is not None, (P, 6)))
-    ins = _lib.GipRasterInputs(_ptr(plan.means3D), _ptr(plan.shs), _ptr(plan.colors_precomp), _ptr(plan.opacities),
-                               _ptr(plan.scales), _ptr(plan.rotations), _ptr(plan.cov3D_precomp),
-                               _ptr(plan.viewmatrix), _ptr(plan.projmatrix), _ptr(plan.campos), _ptr(plan.bg))
+    scratch, g, gout = _backward_buffers(plan)
     color, depth, alpha = outs
     gin = _lib.GipRasterGradsIn(_ptr(g_color), _ptr(g_depth), _ptr(g_alpha), _ptr(alpha), _ptr(color), _ptr(depth))
-    gout = _lib.GipRasterGradsOut(_ptr(g["means3D"]), _ptr(g["means2D"]), _ptr(g["shs"]), _ptr(g["colors_precomp"]),
-                                  _ptr(g["opacities"]), _ptr(g["scales"]), _ptr(g["rotations"]),
-                                  _ptr(g["cov3D_precomp"]))
-    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    if plan.bucket_stride:
-        rc = lib.gip_raster_backward_buckets(ctypes.byref(cfg), ctypes.byref(ins), ctypes.byref(gin), _ptr(plan.state),
-                                             plan.state.numel(), _ptr(scratch), sbytes, ctypes.byref(gout), stream, plan.bucket_stride)
-    else:
-        rc = lib.gip_raster_backward(ctypes.byref(cfg), ctypes.byref(ins), ctypes.byref(gin), _ptr(plan.state),
-                                     plan.state.numel(), _ptr(scratch), sbytes, ctypes.byref(gout), stream)
-    _check(rc, "gip_raster_backward")
+    _launch_backward(plan, gin, scratch, gout)
     return g
 
 
@@ -563,7 +577,7 @@ def state_views(plan):
     mode `keys` is a copy compacted from the buckets to the positions `tile_start` gives."""
     lib = _lib.raster_lib()
     L = _lib.GipRasterStateLayout()
-    S = int(getattr(plan, "bucket_stride", 0))
+    S = plan.bucket_stride
     bucket_off = ctypes.c_size_t(0)
     _check(lib.gip_raster_state_layout_buckets(ctypes.byref(plan.cfg), S, ctypes.byref(L), ctypes.byref(bucket_off)),
            "gip_raster_state_layout_buckets")
@@ -619,48 +633,19 @@ def profile_stages(means3D, opacities, settings_list, g_color, g_depth=None, g_a
                    colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None, iters=10):
     """Runs forward+backward `iters` times with hipEvent pairs around every kernel stage (on the stream the kernels
     are launched on) and returns ({stage: mean ms}, num_rendered).  Synchronises; not for the training path."""
-    lib = _lib.raster_lib()
     _validate(shs, colors_precomp, scales, rotations, cov3D_precomp)
     plan = _build_plan(means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, list(settings_list))
     (color, radii, depth, alpha) = _forward_with_policy(plan, False)   # sizes the capacity synchronously
-    if not plan.bucket_stride and _pick_stride(_bucket_key(_hint_key(plan.means3D.device, plan.P, plan.V, plan.H, plan.W)), plan.V, plan.H, plan.W):
+    if plan.dense_first_call:
         (color, radii, depth, alpha) = _forward_with_policy(plan, False)   # the first call of a shape is dense: profile what follows it
-    S = plan.bucket_stride
-    dev = plan.means3D.device
-    cfg = plan.cfg
-    V, P, M = plan.V, plan.P, plan.M
-    sbytes = lib.gip_raster_scratch_bytes(ctypes.byref(cfg))
-    scratch = torch.empty(sbytes, dtype=torch.uint8, device=dev)
-    f = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)  # noqa: E731
-    g = dict(means3D=f(P, 3), means2D=f(V, P, 3), shs=f(P, max(M, 1), 3) if plan.shs is not None else None,
-             colors=f(P, 3) if plan.colors_precomp is not None else None, opac=f(P, 1),
-             scales=f(P, 3) if plan.scales is not None else None, rots=f(P, 4) if plan.rotations is not None else None,
-             cov=f(P, 6) if plan.cov3D_precomp is not None else None)
-    ins = _lib.GipRasterInputs(_ptr(plan.means3D), _ptr(plan.shs), _ptr(plan.colors_precomp), _ptr(plan.opacities),
-                               _ptr(plan.scales), _ptr(plan.rotations), _ptr(plan.cov3D_precomp),
-                               _ptr(plan.viewmatrix), _ptr(plan.projmatrix), _ptr(plan.campos), _ptr(plan.bg))
+    scratch, grads, gout = _backward_buffers(plan)      # `grads` owns what `gout` points to  # noqa: F841
     outs = _lib.GipRasterOutputs(_ptr(color), _ptr(radii), _ptr(depth), _ptr(alpha))
     gin = _lib.GipRasterGradsIn(_ptr(g_color), _ptr(g_depth), _ptr(g_alpha), _ptr(alpha), _ptr(color), _ptr(depth))
-    gout = _lib.GipRasterGradsOut(_ptr(g["means3D"]), _ptr(g["means2D"]), _ptr(g["shs"]), _ptr(g["colors"]),
-                                  _ptr(g["opac"]), _ptr(g["scales"]), _ptr(g["rots"]), _ptr(g["cov"]))
-    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    times = (ctypes.c_float * len(STAGE_NAMES))()
     acc = [0.0] * len(STAGE_NAMES)
     for it in range(iters + 1):
-        for i in range(len(STAGE_NAMES)):
-            times[i] = 0.0
-        if S:           # the stage that did not run (scatter) keeps its 0
-            _check(lib.gip_raster_forward_buckets_profiled(ctypes.byref(cfg), ctypes.byref(ins), ctypes.byref(outs),
-                                                           _ptr(plan.state), plan.state.numel(), stream, S, times), "forward_profiled")
-            _check(lib.gip_raster_backward_buckets_profiled(ctypes.byref(cfg), ctypes.byref(ins), ctypes.byref(gin),
-                                                            _ptr(plan.state), plan.state.numel(), _ptr(scratch), sbytes,
-                                                            ctypes.byref(gout), stream, S, times), "backward_profiled")
-        else:
-            _check(lib.gip_raster_forward_profiled(ctypes.byref(cfg), ctypes.byref(ins), ctypes.byref(outs),
-                                                   _ptr(plan.state), plan.state.numel(), stream, times), "forward_profiled")
-            _check(lib.gip_raster_backward_profiled(ctypes.byref(cfg), ctypes.byref(ins), ctypes.byref(gin),
-                                                    _ptr(plan.state), plan.state.numel(), _ptr(scratch), sbytes,
-                                                    ctypes.byref(gout), stream, times), "backward_profiled")
+        times = (ctypes.c_float * len(STAGE_NAMES))()   # zeros
+        _launch_forward(plan, outs, times)          # a stage that did not run (bucket mode: scatter) keeps its 0
+        _launch_backward(plan, gin, scratch, gout, times)
         if it > 0:  # first iteration is warm-up
             for i in range(len(STAGE_NAMES)):
                 acc[i] += float(times[i])
