@@ -290,6 +290,21 @@ def model_lib():
         lib.gip_mesh_cluster_count.argtypes = [_vp, _i64, _vp, _i64, _f32, _f32, _f32, _f32, _i32, _vp, _vp]
         lib.gip_mesh_cluster_place.restype = ctypes.c_int
         lib.gip_mesh_cluster_place.argtypes = [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _f32, _f32, _f32, _f32, _i32, _i32, _vp, _vp]
+        _sz = ctypes.c_size_t
+        lib.gip_mesh_geometry_workspace_size.restype = ctypes.c_int
+        lib.gip_mesh_geometry_workspace_size.argtypes = [_i64, ctypes.POINTER(_sz)]
+        lib.gip_mesh_vertex_normals.restype = ctypes.c_int
+        lib.gip_mesh_vertex_normals.argtypes = [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp]
+        lib.gip_mesh_vertex_normals_backward.restype = ctypes.c_int
+        lib.gip_mesh_vertex_normals_backward.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp]
+        lib.gip_mesh_laplacian_loss.restype = ctypes.c_int
+        lib.gip_mesh_laplacian_loss.argtypes = [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _sz, _vp]
+        lib.gip_mesh_laplacian_loss_backward.restype = ctypes.c_int
+        lib.gip_mesh_laplacian_loss_backward.argtypes = [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp]
+        lib.gip_mesh_normal_consistency.restype = ctypes.c_int
+        lib.gip_mesh_normal_consistency.argtypes = [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _sz, _vp]
+        lib.gip_mesh_normal_consistency_backward.restype = ctypes.c_int
+        lib.gip_mesh_normal_consistency_backward.argtypes = [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp]
         _model = _Counted(lib)
     return _model
 
@@ -446,3 +461,6 @@ MESH_MIP_SYMBOLS = ["gip_mesh_rast_db", "gip_mesh_interpolate_da", "gip_mesh_int
                     "gip_mesh_mip_build", "gip_mesh_mip_fold", "gip_mesh_texture_mip", "gip_mesh_texture_mip_backward"]
 MESH_CLEAN_SYMBOLS = ["gip_mesh_components_rounds", "gip_mesh_component_stats", "gip_mesh_cluster_keys", "gip_mesh_cluster_count",
                       "gip_mesh_cluster_place"]
+MESH_GEOM_SYMBOLS = ["gip_mesh_geometry_workspace_size", "gip_mesh_vertex_normals", "gip_mesh_vertex_normals_backward",
+                     "gip_mesh_laplacian_loss", "gip_mesh_laplacian_loss_backward", "gip_mesh_normal_consistency",
+                     "gip_mesh_normal_consistency_backward"]

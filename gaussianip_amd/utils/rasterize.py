@@ -19,6 +19,9 @@ Pixel differentials and mipmaps (csrc/mesh_mip.hip) are opt-in in the same way: 
 rasterize, takes rast_db / diff_attrs in interpolate and uv_da / mip_level_bias / mip / max_mip_level and the mipmap filter modes in
 texture, with their gradients.  The two other contexts raise NotImplementedError naming the argument when asked for any of them, and
 render_mesh stays bilinear: the baked atlas gives every face its own cell, and a mip level above 0 would mix unrelated faces.
+
+The regularisers that a loss on render_mesh(position_gradients=True) needs beside it (vertex normals, Laplacian, normal consistency) are
+in utils/mesh_geometry.py (csrc/mesh_geom.hip).
 """
 import ctypes
 

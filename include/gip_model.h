@@ -339,6 +339,38 @@ int gip_mesh_cluster_count(const float* vertices, int64_t V, const int32_t* face
 int gip_mesh_cluster_place(const float* vertices, int64_t V, const int32_t* faces, int64_t F, const int64_t* cell_key, int64_t C,
                            const int32_t* corner_order, const int32_t* corner_start, const int32_t* member_order, const int32_t* member_start,
                            float lo_x, float lo_y, float lo_z, float h, int32_t n, int32_t lanes, float* out, void* stream);
+/* Geometry terms of a mesh-fitting loop (csrc/mesh_geom.hip, whose header states the definitions; gaussianip_amd/utils/mesh_geometry.py
+ * MeshTopology, vertex_normals, laplacian_loss, normal_consistency): the reference's Mesh.v_nrm, Mesh.laplacian() and
+ * Mesh.normal_consistency() (threestudio/models/mesh.py) with their backward passes.  pos [V, 3] float32 of one mesh, faces [F, 3] int32,
+ * and the tables built once per face list: corner_start [V + 1] / corner_list [3 F] (the corners 3 f + k grouped by vertex, ascending),
+ * nbr_start [V + 1] / nbr_list [N] (per vertex its distinct neighbours, ascending), E the number of unique undirected edges (pairs
+ * (a, a) included).  Every kernel is a gather, one lane per vertex: no float atomics, forward and backward bitwise equal from run to run.
+ *   gip_mesh_geometry_workspace_size  *bytes = the partial sums of the two losses (one float per workgroup of 256 vertices).
+ *   gip_mesh_vertex_normals  n [V, 3] and len [V] (|s_v|, 0 where the default normal (0, 0, 1) was taken).  face_normals [F, 3] is the
+ *       caller's buffer for the per-face cross products, which a first pass fills and the gather reads.
+ *   gip_mesh_vertex_normals_backward  g_pos [V, 3] from g_n [V, 3]; g_s [V, 3] is the caller's buffer for the gradient behind the
+ *       normalisation.
+ *   gip_mesh_laplacian_loss  *loss (device) = mean_v |sum_j (p_v - p_j)|; unit [V, 3] = that vector normalised (0 where it is 0), kept
+ *       for gip_mesh_laplacian_loss_backward, which reads the upstream gradient from the device scalar g_loss.
+ *   gip_mesh_normal_consistency  *loss (device) = (1 / E) sum over the edges of 1 - cos(n_a, n_b); gip_mesh_normal_consistency_backward
+ *       gives g_n [V, 3].
+ * Status 1: a NULL required pointer, V, 3 F or N outside 0 .. 2^31 - 1, E < 0, a short workspace; a call that fails so launches nothing.
+ * V == 0 (and F == 0 for the normals, E == 0 for the consistency) is a success that launches nothing and writes nothing.  Status 3: a
+ * launch error. */
+int gip_mesh_geometry_workspace_size(int64_t V, size_t* bytes);
+int gip_mesh_vertex_normals(const float* pos, const int32_t* faces, const int32_t* corner_start, const int32_t* corner_list, int64_t V,
+                            int64_t F, float* face_normals, float* n, float* len, void* stream);
+int gip_mesh_vertex_normals_backward(const float* pos, const int32_t* faces, const int32_t* corner_start, const int32_t* corner_list,
+                                     const float* n, const float* len, const float* g_n, int64_t V, int64_t F, float* g_s, float* g_pos,
+                                     void* stream);
+int gip_mesh_laplacian_loss(const float* pos, const int32_t* nbr_start, const int32_t* nbr_list, int64_t V, int64_t N, float* unit,
+                            float* loss, void* workspace, size_t workspace_bytes, void* stream);
+int gip_mesh_laplacian_loss_backward(const float* unit, const int32_t* nbr_start, const int32_t* nbr_list, const float* g_loss, int64_t V,
+                                     int64_t N, float* g_pos, void* stream);
+int gip_mesh_normal_consistency(const float* n, const int32_t* nbr_start, const int32_t* nbr_list, int64_t V, int64_t N, int64_t E,
+                                float* loss, void* workspace, size_t workspace_bytes, void* stream);
+int gip_mesh_normal_consistency_backward(const float* n, const int32_t* nbr_start, const int32_t* nbr_list, const float* g_loss, int64_t V,
+                                         int64_t N, int64_t E, float* g_n, void* stream);
 #ifdef __cplusplus
 }
 #endif

@@ -711,6 +711,62 @@ def field():
     print("field fixtures written")
 
 
+def mesh_geometry():
+    """threestudio/models/mesh.py (Mesh.v_nrm, Mesh.edges, Mesh.normal_consistency(), Mesh.laplacian()) on the seeded meshes of
+    tests/mesh_geometry_inputs.py, on the CPU, once in float32 and once in float64.  The file is loaded by path with the permissive
+    stubs above; threestudio.utils.ops.dot is restated as the one-liner it is, sum(x * y, -1, keepdim=True).  Stored per mesh `m`:
+    m_v, m_f, m_w (the inputs, which tests/mesh_geometry_inputs.py must reproduce bit for bit), m_edges, the float64 values m_v_nrm,
+    m_lap, m_nc (the two losses), m_g_nrm = d(sum w . v_nrm) / dv, m_g_lap, m_g_nc, and per quantity q the reference's own float32
+    error m_err_q = max |float32 - float64|.  Outputs only."""
+    _install_threestudio_stubs()
+    sys.modules["threestudio.utils.ops"].dot = lambda x, y: torch.sum(x * y, -1, keepdim=True)
+    sys.path.insert(0, os.path.dirname(OUT))
+    import mesh_geometry_inputs as inputs
+    mod = _load_by_path("threestudio.models.mesh", "threestudio/models/mesh.py", "threestudio.models")
+
+    def run(v, f, w, dtype):
+        f = torch.from_numpy(f).long()
+        w = torch.from_numpy(w).to(dtype)
+        out = {}
+        for q in ("g_nrm", "g_lap", "g_nc"):                       # a fresh Mesh per gradient: nothing cached is shared
+            x = torch.from_numpy(v).to(dtype).requires_grad_(True)
+            m = mod.Mesh(x, f)
+            if q == "g_nrm":
+                out["v_nrm"] = m.v_nrm.detach()
+                val = (w * m.v_nrm).sum()
+            elif q == "g_lap":
+                val = m.laplacian()
+                out["lap"] = val.detach()
+            else:
+                val = m.normal_consistency()
+                out["nc"] = val.detach()
+                out["edges"] = m.edges
+            out[q], = torch.autograd.grad(val, x)
+        return out
+
+    data, lines = {}, []
+    for name in sorted(inputs.SPECS):
+        v, f, w, tags = inputs.mesh(name)
+        keys = np.sort(f.astype(np.int64), 1)
+        three = tags["three_face_edge"]
+        pairs = np.concatenate((keys[:, [0, 1]], keys[:, [1, 2]], keys[:, [0, 2]]))
+        assert (pairs == np.array(three)).all(1).sum() == 3, "the wing's edge must carry exactly three faces"
+        r32, r64 = run(v, f, w, torch.float32), run(v, f, w, torch.float64)
+        assert torch.equal(r32["edges"], r64["edges"])
+        data[name + "_v"], data[name + "_f"], data[name + "_w"] = v, f, w
+        data[name + "_edges"] = r64["edges"].numpy().astype(np.int32)
+        for q in inputs.QUANTITIES:
+            assert r64[q].dtype == torch.float64 and bool(torch.isfinite(r64[q]).all()) and bool(torch.isfinite(r32[q]).all()), (name, q)
+            data["%s_%s" % (name, q)] = r64[q].numpy()
+            err = float((r32[q].double() - r64[q]).abs().max())
+            data["%s_err_%s" % (name, q)] = np.float64(err)
+            lines.append("mesh %s (V %d, F %d, E %d) %-6s float32 error %.3e on a maximum of %.3e" % (
+                name, v.shape[0], f.shape[0], r64["edges"].shape[0], q, err, float(r64[q].abs().max())))
+    np.savez_compressed(os.path.join(OUT, "mesh_geometry.npz"), **data)
+    print("\n".join(lines))
+    print("mesh geometry fixtures written: %d bytes" % os.path.getsize(os.path.join(OUT, "mesh_geometry.npz")))
+
+
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "field":
         field()
@@ -726,5 +782,7 @@ if __name__ == "__main__":
         ply()
     elif len(sys.argv) > 1 and sys.argv[1] == "ssim":
         ssim()
+    elif len(sys.argv) > 1 and sys.argv[1] == "mesh_geometry":
+        mesh_geometry()
     else:
         main()
