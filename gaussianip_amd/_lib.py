@@ -305,6 +305,20 @@ def model_lib():
         lib.gip_mesh_normal_consistency.argtypes = [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _sz, _vp]
         lib.gip_mesh_normal_consistency_backward.restype = ctypes.c_int
         lib.gip_mesh_normal_consistency_backward.argtypes = [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp]
+        lib.gip_uv_face_classes.restype = ctypes.c_int
+        lib.gip_uv_face_classes.argtypes = [_vp, _vp, _vp, _i64, _i64, _i32, _f32, _vp, _vp, _vp, _vp, _vp]
+        lib.gip_uv_chart_rounds.restype = ctypes.c_int
+        lib.gip_uv_chart_rounds.argtypes = [_vp, _vp, _i64, _vp, _vp, _i32, _vp]
+        lib.gip_uv_chart_boxes.restype = ctypes.c_int
+        lib.gip_uv_chart_boxes.argtypes = [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp]
+        lib.gip_uv_place.restype = ctypes.c_int
+        lib.gip_uv_place.argtypes = [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _f32, _i32, _vp, _vp]
+        lib.gip_uv_vertex_tangents.restype = ctypes.c_int
+        lib.gip_uv_vertex_tangents.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp]
+        lib.gip_uv_vertex_tangents_backward.restype = ctypes.c_int
+        lib.gip_uv_vertex_tangents_backward.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp]
+        lib.gip_texture_dilate.restype = ctypes.c_int
+        lib.gip_texture_dilate.argtypes = [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]
         _model = _Counted(lib)
     return _model
 
@@ -464,3 +478,5 @@ MESH_CLEAN_SYMBOLS = ["gip_mesh_components_rounds", "gip_mesh_component_stats", 
 MESH_GEOM_SYMBOLS = ["gip_mesh_geometry_workspace_size", "gip_mesh_vertex_normals", "gip_mesh_vertex_normals_backward",
                      "gip_mesh_laplacian_loss", "gip_mesh_laplacian_loss_backward", "gip_mesh_normal_consistency",
                      "gip_mesh_normal_consistency_backward"]
+MESH_UV_SYMBOLS = ["gip_uv_face_classes", "gip_uv_chart_rounds", "gip_uv_chart_boxes", "gip_uv_place", "gip_uv_vertex_tangents",
+                   "gip_uv_vertex_tangents_backward", "gip_texture_dilate"]

@@ -455,6 +455,30 @@ class GaussianModel:
         return out
 
     @torch.no_grad()
+    def bake_chart_texture(self, vertices, faces, atlas, colors=None, resolution=128, num_blocks=16, relax_ratio=1.5):
+        """{"texture": [T, T, 3] float32, "covered": [T, T] bool, "filled": [T, T] bool, "uv": [F, 3, 2], "atlas": atlas}: the
+        weight-blended `colors` of the Gaussians baked into the chart atlas `atlas` (utils.uv_atlas.unwrap_charts of this mesh: vertices
+        [V, 3] float32 world coordinates, faces [F, 3] int32, on the GPU) — the reference's exporter (threestudio/models/exporters/
+        mesh_exporter.py:53-137) with the project's own unwrapping, rasteriser and seam padding.  atlas.texel_points gives the covered
+        texels and their points on the surface, sample_fields the colour there (`colors`, resolution, num_blocks, relax_ratio are
+        that method's), and utils.uv_atlas.dilate_texture pads the seams by atlas.pad rounds; `filled` marks what holds a colour
+        after that, every other texel is 0.  Raises like sample_fields, and ValueError for an atlas of another face list."""
+        from ..utils.mesh import _mesh_args
+        from ..utils.uv_atlas import ChartAtlas, dilate_texture
+        vertices, faces = _mesh_args("bake_chart_texture", vertices, faces)
+        if not isinstance(atlas, ChartAtlas) or tuple(atlas.t_tex_idx.shape) != tuple(faces.shape):
+            raise ValueError("bake_chart_texture: atlas must be the ChartAtlas of these faces")
+        T = int(atlas.texture_size)
+        dev = vertices.device
+        covered, points, _ = atlas.texel_points(vertices)
+        texture = torch.zeros((T, T, 3), dtype=torch.float32, device=dev)
+        at = points[covered].contiguous()
+        if at.shape[0]:
+            texture[covered] = self.sample_fields(at, colors, resolution, num_blocks, relax_ratio)["color"].to(dev)
+        texture, filled = dilate_texture(texture, covered, atlas.pad)
+        return {"texture": texture, "covered": covered, "filled": filled, "uv": atlas.uv, "atlas": atlas}
+
+    @torch.no_grad()
     def bake_texture_from_views(self, vertices, faces, cameras, pipe=None, texture_size=None, images=None, alphas=None, depth_tolerance=None,
                                 *, min_cos=0.2, min_alpha=0.5, two_sided=True, unpremultiply=None, colors=None, resolution=128,
                                 num_blocks=16, relax_ratio=1.5):
@@ -510,7 +534,7 @@ class GaussianModel:
     @torch.no_grad()
     def extract_textured_mesh(self, path=None, density_thresh=1.0, resolution=128, num_blocks=16, relax_ratio=1.5, texture_size=None,
                               colors=None, *, clean=False, min_faces=8, min_diameter=0.05, decimate_target=0, bake="field", cameras=None,
-                              pipe=None, **view_kwargs):
+                              pipe=None, atlas="faces", **view_kwargs):
         """(vertices [V, 3], faces [F, 3] int32, normals [V, 3], uv [F, 3, 2], texture [T, T, 3]): the mesh and normals of
         extract_mesh_with_attributes, bit for bit, with bake_texture's atlas and texture in place of vertex colours — the reference's
         export_obj_with_mtl (threestudio/models/exporters/mesh_exporter.py:53-137) without its third-party unwrapping, rasterising
@@ -519,10 +543,19 @@ class GaussianModel:
         decimated mesh (fewer faces: larger atlas cells at the same texture size), and the files follow it.
         bake="views": the texture is bake_texture_from_views' from `cameras` (ValueError without any) with `pipe` and the further
         keywords of that method (images, alphas, depth_tolerance, min_cos, min_alpha, two_sided, unpremultiply); the default
-        bake="field" takes none of them."""
+        bake="field" takes none of them.
+        atlas="charts": the mesh is unwrapped into a chart atlas (utils.uv_atlas.unwrap_charts at texture_size) and the texture is
+        bake_chart_texture's: continuous UVs that neighbouring faces share, which the mipmapped lookup and an image editor can use;
+        uv is still [F, 3, 2] (the atlas' v_tex[t_tex_idx]) and the OBJ shares its `vt` lines between faces.  The default
+        atlas="faces" is the fixed per-face atlas.  bake="views" with atlas="charts" raises NotImplementedError."""
         from ..utils import mesh
         if bake not in ("field", "views"):
             raise ValueError("extract_textured_mesh: bake must be 'field' or 'views', not %r" % (bake,))
+        if atlas not in ("faces", "charts"):
+            raise ValueError("extract_textured_mesh: atlas must be 'faces' or 'charts', not %r" % (atlas,))
+        if atlas == "charts" and bake == "views":
+            raise NotImplementedError("extract_textured_mesh: bake='views' is not available with atlas='charts': project_views is built on "
+                                      "the per-face atlas; use bake='field' or atlas='faces'")
         if bake == "views" and (cameras is None or (isinstance(cameras, (list, tuple)) and len(cameras) == 0)):
             raise ValueError("extract_textured_mesh: bake='views' needs cameras")
         if bake == "field" and (cameras is not None or pipe is not None or view_kwargs):
@@ -530,6 +563,15 @@ class GaussianModel:
         vertices, faces, normals, _ = self.extract_mesh_with_attributes(None, density_thresh, resolution, num_blocks, relax_ratio, colors,
                                                                         clean=clean, min_faces=min_faces, min_diameter=min_diameter,
                                                                         decimate_target=decimate_target)
+        if atlas == "charts":
+            from ..utils.uv_atlas import unwrap_charts
+            size = self._default_texture_size(int(faces.shape[0])) if texture_size is None else int(texture_size)
+            charts = unwrap_charts(vertices, faces, size)
+            baked = self.bake_chart_texture(vertices, faces, charts, colors, resolution, num_blocks, relax_ratio)
+            if path is not None:
+                os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+                mesh.write_obj_textured(path, vertices, faces, charts.v_tex, baked["texture"], normals=normals, uv_idx=charts.t_tex_idx)
+            return vertices, faces, normals, baked["uv"], baked["texture"]
         if bake == "views":
             baked = self.bake_texture_from_views(vertices, faces, cameras, pipe, texture_size, colors=colors, resolution=resolution,
                                                  num_blocks=num_blocks, relax_ratio=relax_ratio, **view_kwargs)

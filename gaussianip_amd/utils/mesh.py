@@ -477,14 +477,16 @@ def read_ply_mesh(path):
     return vertices, tris["idx"].astype(np.int32).reshape(-1, 3), colors, normals
 
 
-def write_obj_textured(path, vertices, faces, uv, texture, normals=None):
+def write_obj_textured(path, vertices, faces, uv, texture, normals=None, uv_idx=None):
     """Wavefront OBJ with a material and a texture, the layout of the reference's exporter (threestudio/utils/saving.py:519-545):
     `path` = dir/name.obj gets `mtllib name.mtl`, `g object`, `usemtl default`, the `v` lines, `vn` lines (with `normals`, one per
     vertex) and `vt u v` lines (uv [F, 3, 2]: three per face, none shared; numbers with 9 significant digits as write_obj), then
     `f a/t/a b/t/b c/t/c` (`f a/t b/t c/t` without normals) with t = 3 f + 1 .. 3 f + 3.  dir/name.mtl holds the reference's
     statements in its order and names dir/name_kd.png, the texture ([H, W, 3] in [0, 1], row 0 on top) as an 8-bit PNG.  The
     reference calls every texture `texture_kd.*`; here the name follows the OBJ's, because two exports into one directory would
-    otherwise overwrite each other's texture."""
+    otherwise overwrite each other's texture.
+    uv_idx [F, 3] (a chart atlas' t_tex_idx): uv is then [Vt, 2], one `vt` line per texture vertex, and a face's corners name
+    t = uv_idx + 1, so faces share their texture vertices."""
     import os
 
     from .texture import write_png_rgb
@@ -492,8 +494,14 @@ def write_obj_textured(path, vertices, faces, uv, texture, normals=None):
     f = _array(faces, np.int64).reshape(-1, 3) + 1
     vt = _array(uv, np.float32).reshape(-1, 2)
     nrm = None if normals is None else _array(normals, np.float32).reshape(-1, 3)
-    if vt.shape[0] != 3 * f.shape[0]:
-        raise ValueError("write_obj_textured: uv needs three rows per face")
+    if uv_idx is None:
+        if vt.shape[0] != 3 * f.shape[0]:
+            raise ValueError("write_obj_textured: uv needs three rows per face")
+        ft = np.arange(1, 3 * f.shape[0] + 1, dtype=np.int64).reshape(-1, 3)
+    else:
+        ft = _array(uv_idx, np.int64).reshape(-1, 3) + 1
+        if ft.shape[0] != f.shape[0] or (ft.size and (ft.min() < 1 or ft.max() > vt.shape[0])):
+            raise ValueError("write_obj_textured: uv_idx needs one row per face with indices into uv")
     if nrm is not None and nrm.shape[0] != v.shape[0]:
         raise ValueError("write_obj_textured: normals need one row per vertex")
     stem = os.path.splitext(os.path.abspath(path))[0]
@@ -505,18 +513,18 @@ def write_obj_textured(path, vertices, faces, uv, texture, normals=None):
             out.write("".join("vn %.9g %.9g %.9g\n" % (float(a), float(b), float(c)) for a, b, c in nrm))
         out.write("".join("vt %.9g %.9g\n" % (float(a), float(b)) for a, b in vt))
         if nrm is None:
-            out.write("".join("f %d/%d %d/%d %d/%d\n" % (a, 3 * i + 1, b, 3 * i + 2, c, 3 * i + 3) for i, (a, b, c) in enumerate(f)))
+            out.write("".join("f %d/%d %d/%d %d/%d\n" % (a, ta, b, tb, c, tc) for (a, b, c), (ta, tb, tc) in zip(f, ft)))
         else:
-            out.write("".join("f %d/%d/%d %d/%d/%d %d/%d/%d\n" % (a, 3 * i + 1, a, b, 3 * i + 2, b, c, 3 * i + 3, c)
-                              for i, (a, b, c) in enumerate(f)))
+            out.write("".join("f %d/%d/%d %d/%d/%d %d/%d/%d\n" % (a, ta, a, b, tb, b, c, tc, c) for (a, b, c), (ta, tb, tc) in zip(f, ft)))
     with open(stem + ".mtl", "w") as out:
         out.write("newmtl default\nKa 0.0 0.0 0.0\nmap_Kd %s_kd.png\nKs 0.0 0.0 0.0\n" % name)
     write_png_rgb(stem + "_kd.png", texture)
 
 
-def read_obj_textured(path):
+def read_obj_textured(path, return_index=False):
     """(vertices [V, 3] float32, faces [F, 3] int32 0-based, normals [V, 3] float32 or None, uv [F, 3, 2] float32, texture [H, W, 3]
-    float32 in [0, 1]) of what write_obj_textured wrote: the texture is the `map_Kd` of the file that `mtllib` names."""
+    float32 in [0, 1]) of what write_obj_textured wrote: the texture is the `map_Kd` of the file that `mtllib` names.
+    return_index=True appends (v_tex [Vt, 2] float32, t_tex_idx [F, 3] int32): the `vt` lines and the faces' indices into them."""
     import os
 
     from .texture import read_png_rgb
@@ -549,5 +557,8 @@ def read_obj_textured(path):
         raise ValueError("%s has no map_Kd" % mtl)
     uv = np.asarray(vt, np.float32).reshape(-1, 2)[np.asarray(ft, np.int64).reshape(-1, 3)]
     texture = read_png_rgb(os.path.join(folder, image)).astype(np.float32) / 255
-    return (np.asarray(v, np.float32).reshape(-1, 3), np.asarray(f, np.int32).reshape(-1, 3),
-            np.asarray(n, np.float32).reshape(-1, 3) if n else None, uv.reshape(-1, 3, 2), texture)
+    out = (np.asarray(v, np.float32).reshape(-1, 3), np.asarray(f, np.int32).reshape(-1, 3),
+           np.asarray(n, np.float32).reshape(-1, 3) if n else None, uv.reshape(-1, 3, 2), texture)
+    if return_index:
+        out += (np.asarray(vt, np.float32).reshape(-1, 2), np.asarray(ft, np.int32).reshape(-1, 3))
+    return out

@@ -371,6 +371,49 @@ int gip_mesh_normal_consistency(const float* n, const int32_t* nbr_start, const 
                                 float* loss, void* workspace, size_t workspace_bytes, void* stream);
 int gip_mesh_normal_consistency_backward(const float* n, const int32_t* nbr_start, const int32_t* nbr_list, const float* g_loss, int64_t V,
                                          int64_t N, int64_t E, float* g_n, void* stream);
+/* Unwrapping the mesh into a chart atlas, tangents and seam padding (csrc/mesh_uv.hip, whose header states the definitions and the
+ * float32 arithmetic; gaussianip_amd/utils/uv_atlas.py unwrap_charts, vertex_tangents, dilate_texture).  pos [V, 3] float32, faces
+ * [F, 3] int32, face_nbr [F, 3] int32 (the face across edge (k, k + 1 mod 3) or -1: uv_atlas.face_adjacency), everything on the device.
+ *   gip_uv_face_classes  with gip_uv_chart_rounds, gip_uv_chart_boxes and gip_uv_place in place of xatlas' chart and pack passes
+ *       (threestudio/models/mesh.py:207-250, Mesh._unwrap_uv).  normals [F, 3] = cross(p1 - p0, p2 - p0); smooth_rounds (0 .. 64)
+ *       gather rounds over face_nbr ping-pong between smooth_a and smooth_b [F, 3] (unused and may be NULL at 0 rounds); face_class [F]
+ *       = 2 axis + sign of the smoothed normal where the face keeps min_cos (0 .. 0.5) of its area in that projection, else of its own
+ *       normal; 4 for a face with |n|^2 <= 1e-20.
+ *   gip_uv_chart_rounds  `rounds` (1 .. 64) rounds of hook + compress on labels [F] int32, WHICH THE CALLER HAS SET TO 0 .. F - 1 before
+ *       the first call, over the face_nbr entries that join two faces of one class; *changed (device int32, zeroed by the caller) is
+ *       raised when a label moved.  At the fixed point labels[f] is the smallest face index of f's chart.
+ *   gip_uv_chart_boxes  box_keys [C, 4] uint32 = (min u, min v, max u, max v) of every chart's corners in the projection of
+ *       chart_class [C], as order-preserving keys (a non-negative float's bits | 0x80000000, a negative one's bits inverted); THE
+ *       CALLER INITIALISES the minima to 0xffffffff and the maxima to 0 and decodes.  Integer atomics only: order-independent.
+ *   gip_uv_place  v_tex [Vt, 2]: texture vertex t is position vertex vmapping[t] in chart vt_chart[t], placed with the chart's row of
+ *       chart_origin [C, 4] = (umin, vmin, x0 + pad, y0 + pad) and `scale` texels per unit, as OBJ coordinates of a texture_size^2 image.
+ *   gip_uv_vertex_tangents  the reference's Mesh._compute_vertex_tangent (mesh.py:162-205) as a gather over corner_start [V + 1] /
+ *       corner_list [3 F] (MeshTopology): tangents [V, 3] from pos, nrm [V, 3], v_tex [Vt, 2] and tex_idx [F, 3]; face_tangents [F, 3]
+ *       is the caller's buffer, kept for the backward.  A vertex without a corner gets (1, 0, 0).
+ *   gip_uv_vertex_tangents_backward  g_pos [V, 3] and g_nrm [V, 3] from g_tangents [V, 3] (autograd through mesh.py:162-205 with v_tex
+ *       constant); g_sum [V, 3] and g_edge [F, 6] are the caller's buffers.  No float atomics in either direction.
+ *   gip_texture_dilate  in place of cv2.inpaint (mesh_exporter.py:113-121): `rounds` rounds that give an unfilled texel with a filled
+ *       8-neighbour their mean; tex_a [H, W, C] / mask_a [H, W] uint8 hold the input, round r writes the other pair, so the result is
+ *       in (tex_a, mask_a) when rounds is even and in (tex_b, mask_b) when it is odd.
+ * Status 1: a NULL required pointer, V or 3 F above 2^31 - 1, smooth_rounds, min_cos, rounds, C or texture_size out of range, scale not
+ * positive, H or W outside 1 .. 16384, channels outside 1 .. 64; a call that fails so launches nothing.  Empty input (F == 0, Vt == 0,
+ * V == 0, rounds == 0 of the dilation) is a success that launches nothing.  Status 3: a launch error. */
+int gip_uv_face_classes(const float* pos, const int32_t* faces, const int32_t* face_nbr, int64_t V, int64_t F, int32_t smooth_rounds,
+                        float min_cos, float* normals, float* smooth_a, float* smooth_b, int32_t* face_class, void* stream);
+int gip_uv_chart_rounds(const int32_t* face_nbr, const int32_t* face_class, int64_t F, int32_t* labels, int32_t* changed, int32_t rounds,
+                        void* stream);
+int gip_uv_chart_boxes(const float* pos, const int32_t* faces, const int32_t* face_chart, const int32_t* chart_class, int64_t V, int64_t F,
+                       int64_t C, uint32_t* box_keys, void* stream);
+int gip_uv_place(const float* pos, const int32_t* vmapping, const int32_t* vt_chart, const int32_t* chart_class, const float* chart_origin,
+                 int64_t V, int64_t Vt, int64_t C, float scale, int32_t texture_size, float* v_tex, void* stream);
+int gip_uv_vertex_tangents(const float* pos, const int32_t* faces, const int32_t* corner_start, const int32_t* corner_list,
+                           const int32_t* tex_idx, const float* v_tex, const float* nrm, int64_t V, int64_t F, int64_t Vt,
+                           float* face_tangents, float* tangents, void* stream);
+int gip_uv_vertex_tangents_backward(const int32_t* faces, const int32_t* corner_start, const int32_t* corner_list, const int32_t* tex_idx,
+                                    const float* v_tex, const float* nrm, const float* face_tangents, const float* g_tangents, int64_t V,
+                                    int64_t F, int64_t Vt, float* g_sum, float* g_edge, float* g_pos, float* g_nrm, void* stream);
+int gip_texture_dilate(float* tex_a, uint8_t* mask_a, float* tex_b, uint8_t* mask_b, int32_t H, int32_t W, int32_t C, int32_t rounds,
+                       void* stream);
 #ifdef __cplusplus
 }
 #endif

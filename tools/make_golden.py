@@ -767,6 +767,52 @@ def mesh_geometry():
     print("mesh geometry fixtures written: %d bytes" % os.path.getsize(os.path.join(OUT, "mesh_geometry.npz")))
 
 
+def uv_tangents():
+    """threestudio/models/mesh.py Mesh._compute_vertex_tangent (mesh.py:162-205) and autograd on the seeded meshes of
+    tests/mesh_geometry_inputs.py, on the CPU, once in float32 and once in float64, loaded as in mesh_geometry().  The mesh's _v_tex and
+    _t_tex_idx are set to the atlas of tests/uv_atlas_reference.py (texture size 256, 4 smoothing rounds) and its _v_nrm to a leaf
+    holding the reference's own float32 normals, so the two gradients are separate.  Stored per mesh `m`, for the referenced vertices
+    m_rows only (the reference gives NaN elsewhere): m_nrm (the float32 normals that were the input, all V rows), the float64 values
+    m_v_tng, m_g_v = d(sum w . v_tng) / dv, m_g_nrm = d(sum w . v_tng) / dv_nrm (w of the inputs), and per quantity q the reference's own
+    float32 error m_err_q = max |float32 - float64|.  Outputs only."""
+    _install_threestudio_stubs()
+    sys.modules["threestudio.utils.ops"].dot = lambda x, y: torch.sum(x * y, -1, keepdim=True)
+    sys.path.insert(0, os.path.dirname(OUT))
+    import mesh_geometry_inputs as inputs
+    import uv_atlas_reference as atlas_reference
+    mod = _load_by_path("threestudio.models.mesh", "threestudio/models/mesh.py", "threestudio.models")
+    data, lines = {}, []
+    for name in sorted(inputs.SPECS):
+        v, f, w, tags = inputs.mesh(name)
+        atlas = atlas_reference.unwrap(v, f, 256, 4)
+        rows = np.setdiff1d(np.arange(v.shape[0]), np.array(tags["unreferenced"], np.int64))
+        nrm = mod.Mesh(torch.from_numpy(v), torch.from_numpy(f).long()).v_nrm.numpy().astype(np.float32)
+
+        def run(dtype):
+            x = torch.from_numpy(v).to(dtype).requires_grad_(True)
+            n = torch.from_numpy(nrm).to(dtype).requires_grad_(True)
+            m = mod.Mesh(x, torch.from_numpy(f).long())
+            m._v_nrm = n
+            m._v_tex = torch.from_numpy(atlas["v_tex"]).to(dtype)
+            m._t_tex_idx = torch.from_numpy(atlas["t_tex_idx"]).long()
+            t = m.v_tng
+            pick = torch.from_numpy(rows)
+            g_v, g_n = torch.autograd.grad((torch.from_numpy(w).to(dtype)[pick] * t[pick]).sum(), (x, n))
+            return {"v_tng": t.detach()[pick], "g_v": g_v[pick], "g_nrm": g_n[pick]}
+        r32, r64 = run(torch.float32), run(torch.float64)
+        data[name + "_rows"], data[name + "_nrm"] = rows.astype(np.int32), nrm
+        for q in ("v_tng", "g_v", "g_nrm"):
+            assert r64[q].dtype == torch.float64 and bool(torch.isfinite(r64[q]).all()) and bool(torch.isfinite(r32[q]).all()), (name, q)
+            data["%s_%s" % (name, q)] = r64[q].numpy()
+            err = float((r32[q].double() - r64[q]).abs().max())
+            data["%s_err_%s" % (name, q)] = np.float64(err)
+            lines.append("mesh %s (V %d, F %d, Vt %d) %-6s float32 error %.3e on a maximum of %.3e" % (
+                name, v.shape[0], f.shape[0], atlas["v_tex"].shape[0], q, err, float(r64[q].abs().max())))
+    np.savez_compressed(os.path.join(OUT, "uv_tangents.npz"), **data)
+    print("\n".join(lines))
+    print("uv tangent fixtures written: %d bytes" % os.path.getsize(os.path.join(OUT, "uv_tangents.npz")))
+
+
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "field":
         field()
@@ -784,5 +830,7 @@ if __name__ == "__main__":
         ssim()
     elif len(sys.argv) > 1 and sys.argv[1] == "mesh_geometry":
         mesh_geometry()
+    elif len(sys.argv) > 1 and sys.argv[1] == "uv_tangents":
+        uv_tangents()
     else:
         main()
