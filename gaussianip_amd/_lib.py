@@ -323,6 +323,20 @@ def model_lib():
     return _model
 
 
+def ptr(t):
+    """The address of tensor t for a C-ABI call; null for None or an empty tensor."""
+    return ctypes.c_void_p(t.data_ptr() if t is not None and t.numel() else None)
+
+
+def call_model(dev, name, *args):
+    """libgip_model.so's entry point `name` with args and, as its last argument, dev's current stream; RuntimeError unless it returns 0."""
+    import torch
+    with torch.cuda.device(dev):
+        rc = getattr(model_lib(), name)(*args, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    if rc != 0:
+        raise RuntimeError("%s failed with status %d" % (name, rc))
+
+
 _nn = None
 
 

@@ -4,23 +4,14 @@
 // Linked into libgip_model.so.  No kernel here spins, waits on another workgroup or uses a grid-wide barrier; every loop over rounds
 // lives on the host.
 //
-// Connected components.  label[v] starts as v (the caller's arange).  One round = mc_hook_kernel, then mc_compress_kernel:
+// Connected components.  label[v] starts as v (the caller's arange).  One round = mc_hook_kernel, then mc_compress_kernel, the scheme
+//   of mesh_common.h "Labels", which proves that the fixed point is the component's smallest vertex whatever the interleaving:
 //   hook      one lane per face: m = min(label[a], label[b], label[c]); for each corner x an integer atomicMin of m into
 //             label[label[x]] and into label[x].  A face with an index outside [0, V) is skipped.
-//   compress  one lane per vertex: label[v] = the end of the chain v -> label[v] -> label[label[v]] -> ...
-//   Either raises *changed when it lowered a label.  The host stops after rounds that changed nothing.
-//   Why the fixed point is the component's minimum.  Three invariants hold at every moment, whatever the interleaving: (1) labels only
-//   decrease (every write is an atomicMin or a compress store of a value further down the vertex's own chain); (2) label[v] <= v
-//   (true at the start, kept by 1), so every chain is strictly decreasing until it reaches an r with label[r] == r and the compress
-//   loop ends after at most V steps; (3) label[v] names a vertex of v's own component (a hook copies a label between corners of one
-//   face or onto the vertex that one of them names, compress follows names).  When a round changes nothing, every face's three corners
-//   carry one label (else the hook's atomicMin into label[x] would have lowered one) and every label is a root (else compress would
-//   have moved it); labels are therefore constant on a component, the common value r is a member of it by 3 and r <= every member by 2:
-//   r is the minimum.  Races change the number of rounds, never the result.
+//   compress  one lane per vertex: mesh_label_compress.
 //
 // Statistics.  mc_stats_kernel, one lane per face: an integer atomicAdd into count[label] and atomicMin / atomicMax of its three
-//   corners' coordinates into box[label], on the order-preserving 32-bit image of a float that mesh_raster.hip uses for its depth keys
-//   (bits | 0x80000000 for a non-negative value, ~bits for a negative one; -0 counts as +0).  Integer atomics only: order-independent.
+//   corners' coordinates into box[label], on mesh_common.h's float key.  Integer atomics only: order-independent.
 //   mc_box_decode_kernel turns the keys back into floats (rows of components without a face are not defined).
 //
 // Clustering.  The grid: per axis i = min((int) floorf((p - lo) / h), n - 1), float32, that operand order, a correctly rounded
@@ -44,18 +35,18 @@
 #include <stdint.h>
 
 #include "../../include/gip_model.h"
+#include "mesh_common.h"
 
-#define MC_THREADS 256
 #define MC_MAX_GRID 2048
 #define MC_LAMBDA 1e-3f
 
 // ------------------------------------------------------------------------------------------------------------------ components
-__global__ void __launch_bounds__(MC_THREADS)
+__global__ void __launch_bounds__(MESH_THREADS)
 mc_hook_kernel(const int32_t* __restrict__ faces, int F, int V, int32_t* label, int32_t* __restrict__ changed) {
-  const int f = blockIdx.x * MC_THREADS + threadIdx.x;
+  const int f = blockIdx.x * MESH_THREADS + threadIdx.x;
   if (f >= F) return;
-  const int a = faces[(int64_t)f * 3], b = faces[(int64_t)f * 3 + 1], c = faces[(int64_t)f * 3 + 2];
-  if (a < 0 || a >= V || b < 0 || b >= V || c < 0 || c >= V) return;
+  int32_t a, b, c;
+  if (!mesh_face(faces, f, V, &a, &b, &c)) return;
   // volatile reads: other lanes lower these words while this kernel runs; any value seen is a valid (later or earlier) label in [0, V)
   const int la = __atomic_load_n(label + a, __ATOMIC_RELAXED), lb = __atomic_load_n(label + b, __ATOMIC_RELAXED),
             lc = __atomic_load_n(label + c, __ATOMIC_RELAXED);
@@ -71,34 +62,15 @@ mc_hook_kernel(const int32_t* __restrict__ faces, int F, int V, int32_t* label, 
   if (moved) *changed = 1;
 }
 
-__global__ void __launch_bounds__(MC_THREADS)
+__global__ void __launch_bounds__(MESH_THREADS)
 mc_compress_kernel(int V, int32_t* label, int32_t* __restrict__ changed) {
-  const int v = blockIdx.x * MC_THREADS + threadIdx.x;
-  if (v >= V) return;
-  const int first = __atomic_load_n(label + v, __ATOMIC_RELAXED);
-  int l = first;
-  // strictly decreasing (label[x] <= x always): at most V steps, whatever other lanes store meanwhile
-  for (int step = 0; step < V; step++) {
-    const int next = __atomic_load_n(label + l, __ATOMIC_RELAXED);
-    if (next >= l) break;
-    l = next;
-  }
-  if (l < first) {
-    atomicMin(label + v, l);
-    *changed = 1;
-  }
+  mesh_label_compress(label, blockIdx.x * MESH_THREADS + threadIdx.x, V, changed);
 }
 
 // ------------------------------------------------------------------------------------------------------------------ statistics
-__device__ __forceinline__ uint32_t mc_float_key(float d) {
-  uint32_t u = __float_as_uint(d);
-  if ((u & 0x7fffffffu) == 0) u = 0;
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-__global__ void __launch_bounds__(MC_THREADS)
+__global__ void __launch_bounds__(MESH_THREADS)
 mc_stats_init_kernel(int V, int32_t* __restrict__ count, uint32_t* __restrict__ box) {
-  const int v = blockIdx.x * MC_THREADS + threadIdx.x;
+  const int v = blockIdx.x * MESH_THREADS + threadIdx.x;
   if (v >= V) return;
   count[v] = 0;
 #pragma unroll
@@ -108,13 +80,13 @@ mc_stats_init_kernel(int V, int32_t* __restrict__ count, uint32_t* __restrict__ 
   }
 }
 
-__global__ void __launch_bounds__(MC_THREADS)
+__global__ void __launch_bounds__(MESH_THREADS)
 mc_stats_kernel(const float* __restrict__ vertices, const int32_t* __restrict__ faces, int F, int V, const int32_t* __restrict__ label,
                 int32_t* __restrict__ count, uint32_t* __restrict__ box) {
-  const int f = blockIdx.x * MC_THREADS + threadIdx.x;
+  const int f = blockIdx.x * MESH_THREADS + threadIdx.x;
   if (f >= F) return;
-  const int x[3] = {faces[(int64_t)f * 3], faces[(int64_t)f * 3 + 1], faces[(int64_t)f * 3 + 2]};
-  if (x[0] < 0 || x[0] >= V || x[1] < 0 || x[1] >= V || x[2] < 0 || x[2] >= V) return;
+  int32_t x[3];
+  if (!mesh_face(faces, f, V, &x[0], &x[1], &x[2])) return;
   const int l = label[x[0]];
   if (l < 0 || l >= V) return;   // not a label of connected_components: nothing is written outside the arrays
   atomicAdd(count + l, 1);
@@ -122,18 +94,17 @@ mc_stats_kernel(const float* __restrict__ vertices, const int32_t* __restrict__ 
   for (int k = 0; k < 3; k++)
 #pragma unroll
     for (int ax = 0; ax < 3; ax++) {
-      const uint32_t key = mc_float_key(vertices[(int64_t)x[k] * 3 + ax]);
+      const uint32_t key = mesh_float_key(vertices[(int64_t)x[k] * 3 + ax]);
       atomicMin(box + (int64_t)l * 6 + ax, key);
       atomicMax(box + (int64_t)l * 6 + 3 + ax, key);
     }
 }
 
-__global__ void __launch_bounds__(MC_THREADS)
+__global__ void __launch_bounds__(MESH_THREADS)
 mc_box_decode_kernel(int64_t N, uint32_t* __restrict__ box) {
-  const int64_t i = (int64_t)blockIdx.x * MC_THREADS + threadIdx.x;
+  const int64_t i = (int64_t)blockIdx.x * MESH_THREADS + threadIdx.x;
   if (i >= N) return;
-  const uint32_t u = box[i];
-  box[i] = (u & 0x80000000u) ? (u ^ 0x80000000u) : ~u;
+  box[i] = __float_as_uint(mesh_key_float(box[i]));
 }
 
 // ------------------------------------------------------------------------------------------------------------------ the grid
@@ -143,23 +114,23 @@ __device__ __forceinline__ int mc_cell(float p, float lo, float h, int n) {
   return t >= (float)n ? n - 1 : (int)t;
 }
 
-__global__ void __launch_bounds__(MC_THREADS)
+__global__ void __launch_bounds__(MESH_THREADS)
 mc_keys_kernel(const float* __restrict__ vertices, int V, float lox, float loy, float loz, float h, int n, int64_t* __restrict__ key) {
-  const int v = blockIdx.x * MC_THREADS + threadIdx.x;
+  const int v = blockIdx.x * MESH_THREADS + threadIdx.x;
   if (v >= V) return;
   const int ix = mc_cell(vertices[(int64_t)v * 3], lox, h, n), iy = mc_cell(vertices[(int64_t)v * 3 + 1], loy, h, n),
             iz = mc_cell(vertices[(int64_t)v * 3 + 2], loz, h, n);
   key[v] = ((int64_t)iz * n + iy) * n + ix;
 }
 
-__global__ void __launch_bounds__(MC_THREADS)
+__global__ void __launch_bounds__(MESH_THREADS)
 mc_count_kernel(const float* __restrict__ vertices, int V, const int32_t* __restrict__ faces, int F, float lox, float loy, float loz, float h,
                 int n, int32_t* __restrict__ count) {
-  const int f = blockIdx.x * MC_THREADS + threadIdx.x;
+  const int f = blockIdx.x * MESH_THREADS + threadIdx.x;
   bool alive = false;
   if (f < F) {
-    const int x[3] = {faces[(int64_t)f * 3], faces[(int64_t)f * 3 + 1], faces[(int64_t)f * 3 + 2]};
-    if (x[0] >= 0 && x[0] < V && x[1] >= 0 && x[1] < V && x[2] >= 0 && x[2] < V) {
+    int32_t x[3];
+    if (mesh_face(faces, f, V, &x[0], &x[1], &x[2])) {
       int64_t k[3];
 #pragma unroll
       for (int c = 0; c < 3; c++) {
@@ -175,11 +146,11 @@ mc_count_kernel(const float* __restrict__ vertices, int V, const int32_t* __rest
 
 // ------------------------------------------------------------------------------------------------------------------ placement
 template <int LPC>
-__global__ void __launch_bounds__(MC_THREADS)
+__global__ void __launch_bounds__(MESH_THREADS)
 mc_place_kernel(const float* __restrict__ vertices, int V, const int32_t* __restrict__ faces, int F, const int64_t* __restrict__ cell_key, int C,
                 const int32_t* __restrict__ corner_order, const int32_t* __restrict__ corner_start, const int32_t* __restrict__ member_order,
                 const int32_t* __restrict__ member_start, float lox, float loy, float loz, float h, int n, float* __restrict__ out) {
-  const int cell = (int)(((int64_t)blockIdx.x * MC_THREADS + threadIdx.x) / LPC), j = threadIdx.x & (LPC - 1);
+  const int cell = (int)(((int64_t)blockIdx.x * MESH_THREADS + threadIdx.x) / LPC), j = threadIdx.x & (LPC - 1);
   // a cell past the end does the arithmetic on empty runs (the shuffles below need whole groups) and writes nothing
   const bool live = cell < C;
   const int64_t key = live ? cell_key[cell] : 0;
@@ -258,79 +229,69 @@ mc_place_kernel(const float* __restrict__ vertices, int V, const int32_t* __rest
 }
 
 // ------------------------------------------------------------------------------------------------------------------ entry points
-static inline unsigned mc_blocks(int64_t items) { return (unsigned)((items + MC_THREADS - 1) / MC_THREADS); }
-
-static int mc_mesh_ok(int64_t V, int64_t F) { return V >= 0 && V <= INT32_MAX && F >= 0 && F <= INT32_MAX / 3; }
-
 static int mc_grid_ok(float h, int32_t n) { return n >= 1 && n <= MC_MAX_GRID && h > 0.f && h <= 3.0e38f; }
+
+// workgroups for a count that may pass INT32_MAX (6 V box words, C * lanes placement lanes), which mesh_blocks refuses
+static int64_t mc_wide_blocks(int64_t items) { return (items + MESH_THREADS - 1) / MESH_THREADS; }
 
 extern "C" int gip_mesh_components_rounds(const int32_t* faces, int64_t F, int64_t V, int32_t* labels, int32_t* changed, int32_t rounds,
                                           void* stream) {
-  if (!mc_mesh_ok(V, F) || rounds < 1 || rounds > 64) return 1;
+  if (!mesh_sizes_ok(V, F) || rounds < 1 || rounds > 64) return 1;
   if (F == 0 || V == 0) return 0;
   if (!faces || !labels || !changed) return 1;
-  hipStream_t st = (hipStream_t)stream;
   for (int r = 0; r < rounds; r++) {
-    hipLaunchKernelGGL(mc_hook_kernel, dim3(mc_blocks(F)), dim3(MC_THREADS), 0, st, faces, (int)F, (int)V, labels, changed);
-    hipLaunchKernelGGL(mc_compress_kernel, dim3(mc_blocks(V)), dim3(MC_THREADS), 0, st, (int)V, labels, changed);
+    MESH_LAUNCH(mc_hook_kernel, mesh_blocks(F), stream, faces, (int)F, (int)V, labels, changed);
+    MESH_LAUNCH(mc_compress_kernel, mesh_blocks(V), stream, (int)V, labels, changed);
   }
-  return hipGetLastError() == hipSuccess ? 0 : 3;
+  return mesh_done();
 }
 
 extern "C" int gip_mesh_component_stats(const float* vertices, const int32_t* faces, int64_t F, int64_t V, const int32_t* labels,
                                         int32_t* face_count, float* box, void* stream) {
-  if (!mc_mesh_ok(V, F)) return 1;
+  if (!mesh_sizes_ok(V, F)) return 1;
   if (V == 0) return 0;
   if (!face_count || !box) return 1;
   if (F > 0 && (!vertices || !faces || !labels)) return 1;
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(mc_stats_init_kernel, dim3(mc_blocks(V)), dim3(MC_THREADS), 0, st, (int)V, face_count, (uint32_t*)box);
-  if (F > 0)
-    hipLaunchKernelGGL(mc_stats_kernel, dim3(mc_blocks(F)), dim3(MC_THREADS), 0, st, vertices, faces, (int)F, (int)V, labels, face_count,
-                       (uint32_t*)box);
-  hipLaunchKernelGGL(mc_box_decode_kernel, dim3(mc_blocks(V * 6)), dim3(MC_THREADS), 0, st, V * 6, (uint32_t*)box);
-  return hipGetLastError() == hipSuccess ? 0 : 3;
+  MESH_LAUNCH(mc_stats_init_kernel, mesh_blocks(V), stream, (int)V, face_count, (uint32_t*)box);
+  if (F > 0) MESH_LAUNCH(mc_stats_kernel, mesh_blocks(F), stream, vertices, faces, (int)F, (int)V, labels, face_count, (uint32_t*)box);
+  MESH_LAUNCH(mc_box_decode_kernel, mc_wide_blocks(V * 6), stream, V * 6, (uint32_t*)box);
+  return mesh_done();
 }
 
 extern "C" int gip_mesh_cluster_keys(const float* vertices, int64_t V, float lo_x, float lo_y, float lo_z, float h, int32_t n, int64_t* keys,
                                      void* stream) {
-  if (!mc_mesh_ok(V, 0) || !mc_grid_ok(h, n)) return 1;
+  if (!mesh_count_ok(V) || !mc_grid_ok(h, n)) return 1;
   if (V == 0) return 0;
   if (!vertices || !keys) return 1;
-  hipLaunchKernelGGL(mc_keys_kernel, dim3(mc_blocks(V)), dim3(MC_THREADS), 0, (hipStream_t)stream, vertices, (int)V, lo_x, lo_y, lo_z, h, (int)n,
-                     keys);
-  return hipGetLastError() == hipSuccess ? 0 : 3;
+  MESH_LAUNCH(mc_keys_kernel, mesh_blocks(V), stream, vertices, (int)V, lo_x, lo_y, lo_z, h, (int)n, keys);
+  return mesh_done();
 }
 
 extern "C" int gip_mesh_cluster_count(const float* vertices, int64_t V, const int32_t* faces, int64_t F, float lo_x, float lo_y, float lo_z,
                                       float h, int32_t n, int32_t* count, void* stream) {
-  if (!mc_mesh_ok(V, F) || !mc_grid_ok(h, n) || !count) return 1;
+  if (!mesh_sizes_ok(V, F) || !mc_grid_ok(h, n) || !count) return 1;
   if (F > 0 && (!vertices || !faces || V == 0)) return 1;
-  hipStream_t st = (hipStream_t)stream;
-  if (hipMemsetAsync(count, 0, sizeof(int32_t), st) != hipSuccess) return 3;
+  if (hipMemsetAsync(count, 0, sizeof(int32_t), (hipStream_t)stream) != hipSuccess) return 3;
   if (F == 0) return 0;
-  hipLaunchKernelGGL(mc_count_kernel, dim3(mc_blocks(F)), dim3(MC_THREADS), 0, st, vertices, (int)V, faces, (int)F, lo_x, lo_y, lo_z, h, (int)n,
-                     count);
-  return hipGetLastError() == hipSuccess ? 0 : 3;
+  MESH_LAUNCH(mc_count_kernel, mesh_blocks(F), stream, vertices, (int)V, faces, (int)F, lo_x, lo_y, lo_z, h, (int)n, count);
+  return mesh_done();
 }
 
 extern "C" int gip_mesh_cluster_place(const float* vertices, int64_t V, const int32_t* faces, int64_t F, const int64_t* cell_key, int64_t C,
                                       const int32_t* corner_order, const int32_t* corner_start, const int32_t* member_order,
                                       const int32_t* member_start, float lo_x, float lo_y, float lo_z, float h, int32_t n, int32_t lanes,
                                       float* out, void* stream) {
-  if (!mc_mesh_ok(V, F) || !mc_grid_ok(h, n) || C < 0 || C > V) return 1;
+  if (!mesh_sizes_ok(V, F) || !mc_grid_ok(h, n) || C < 0 || C > V) return 1;
   if (lanes != 16 && lanes != 32 && lanes != 64) return 1;
   if (C == 0) return 0;
   if (!vertices || !cell_key || !corner_start || !member_order || !member_start || !out) return 1;
   if (F > 0 && (!faces || !corner_order)) return 1;
-  hipStream_t st = (hipStream_t)stream;
-  const dim3 grid(mc_blocks(C * lanes)), block(MC_THREADS);
-#define MC_PLACE(L)                                                                                                                      \
-  hipLaunchKernelGGL((mc_place_kernel<L>), grid, block, 0, st, vertices, (int)V, faces, (int)F, cell_key, (int)C, corner_order, corner_start, \
-                     member_order, member_start, lo_x, lo_y, lo_z, h, (int)n, out)
+#define MC_PLACE(L)                                                                                                                    \
+  MESH_LAUNCH((mc_place_kernel<L>), mc_wide_blocks(C * lanes), stream, vertices, (int)V, faces, (int)F, cell_key, (int)C, corner_order, \
+              corner_start, member_order, member_start, lo_x, lo_y, lo_z, h, (int)n, out)
   if (lanes == 16) MC_PLACE(16);
   else if (lanes == 32) MC_PLACE(32);
   else MC_PLACE(64);
 #undef MC_PLACE
-  return hipGetLastError() == hipSuccess ? 0 : 3;
+  return mesh_done();
 }

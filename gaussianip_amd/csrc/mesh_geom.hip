@@ -36,41 +36,11 @@
 #include <stdint.h>
 
 #include "../../include/gip_model.h"
-
-#define MG_THREADS 256
-
-struct MgVec { float x, y, z; };
-
-__device__ __forceinline__ MgVec mg_load(const float* __restrict__ p, int64_t i) { return MgVec{p[3 * i], p[3 * i + 1], p[3 * i + 2]}; }
-__device__ __forceinline__ void mg_store(float* __restrict__ p, int64_t i, MgVec v) { p[3 * i] = v.x; p[3 * i + 1] = v.y; p[3 * i + 2] = v.z; }
-__device__ __forceinline__ MgVec mg_add(MgVec a, MgVec b) { return MgVec{a.x + b.x, a.y + b.y, a.z + b.z}; }
-__device__ __forceinline__ MgVec mg_sub(MgVec a, MgVec b) { return MgVec{a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ MgVec mg_scale(MgVec a, float s) { return MgVec{a.x * s, a.y * s, a.z * s}; }
-__device__ __forceinline__ float mg_dot(MgVec a, MgVec b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-__device__ __forceinline__ MgVec mg_cross(MgVec a, MgVec b) {
-  return MgVec{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
-}
-
-// the row [start[v], start[v + 1]) of a table of `total` entries, clamped to it
-__device__ __forceinline__ void mg_row(const int32_t* __restrict__ start, int64_t v, int64_t total, int64_t* lo, int64_t* hi) {
-  int64_t a = start[v], b = start[v + 1];
-  a = a < 0 ? 0 : a;
-  b = b > total ? total : b;
-  *lo = a;
-  *hi = b;
-}
-
-// a face's three indices; false when one lies outside [0, V)
-__device__ __forceinline__ bool mg_face(const int32_t* __restrict__ faces, int64_t f, int64_t V, int32_t* i0, int32_t* i1, int32_t* i2) {
-  *i0 = faces[3 * f];
-  *i1 = faces[3 * f + 1];
-  *i2 = faces[3 * f + 2];
-  return (uint64_t)*i0 < (uint64_t)V && (uint64_t)*i1 < (uint64_t)V && (uint64_t)*i2 < (uint64_t)V;
-}
+#include "mesh_common.h"
 
 // the workgroup's sum of `value` to partial[blockIdx.x], in one fixed order
 __device__ __forceinline__ void mg_block_sum(float value, float* __restrict__ partial) {
-  __shared__ float s_red[MG_THREADS / 64];
+  __shared__ float s_red[MESH_THREADS / 64];
 #pragma unroll
   for (int d = 32; d >= 1; d >>= 1) value += __shfl_xor(value, d, 64);
   if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = value;
@@ -78,187 +48,170 @@ __device__ __forceinline__ void mg_block_sum(float value, float* __restrict__ pa
   if (threadIdx.x == 0) partial[blockIdx.x] = (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
 }
 
-__global__ void __launch_bounds__(MG_THREADS)
+__global__ void __launch_bounds__(MESH_THREADS)
 mesh_geom_face_normals_kernel(const float* __restrict__ pos, const int32_t* __restrict__ faces, int64_t V, int64_t F,
                               float* __restrict__ face_normals) {
-  const int64_t f = (int64_t)blockIdx.x * MG_THREADS + threadIdx.x;
-  if (f >= F) return;
-  int32_t i0, i1, i2;
-  MgVec c = MgVec{0.f, 0.f, 0.f};
-  if (mg_face(faces, f, V, &i0, &i1, &i2)) {
-    const MgVec p0 = mg_load(pos, i0);
-    c = mg_cross(mg_sub(mg_load(pos, i1), p0), mg_sub(mg_load(pos, i2), p0));
-  }
-  mg_store(face_normals, f, c);
+  const int64_t f = (int64_t)blockIdx.x * MESH_THREADS + threadIdx.x;
+  if (f < F) mesh_store(face_normals, f, mesh_face_cross(pos, faces, f, V));
 }
 
-__global__ void __launch_bounds__(MG_THREADS)
+__global__ void __launch_bounds__(MESH_THREADS)
 mesh_geom_normals_kernel(const int32_t* __restrict__ corner_start, const int32_t* __restrict__ corner_list,
                          const float* __restrict__ face_normals, int64_t V, int64_t F, float* __restrict__ n, float* __restrict__ len) {
-  const int64_t v = (int64_t)blockIdx.x * MG_THREADS + threadIdx.x;
+  const int64_t v = (int64_t)blockIdx.x * MESH_THREADS + threadIdx.x;
   if (v >= V) return;
   int64_t lo, hi;
-  mg_row(corner_start, v, 3 * F, &lo, &hi);
-  MgVec s = MgVec{0.f, 0.f, 0.f};
+  mesh_row(corner_start, v, 3 * F, &lo, &hi);
+  MeshVec s = MeshVec{0.f, 0.f, 0.f};
   for (int64_t at = lo; at < hi; at++) {
     const int64_t c = corner_list[at];
     if ((uint64_t)c >= (uint64_t)(3 * F)) continue;
-    s = mg_add(s, mg_load(face_normals, c / 3));
+    s = mesh_add(s, mesh_load(face_normals, c / 3));
   }
-  const float d = mg_dot(s, s);
+  const float d = mesh_dot(s, s);
   if (d > 1e-20f) {
     const float l = sqrtf(d);
     const float q = fmaxf(l, 1e-12f);
-    mg_store(n, v, MgVec{s.x / q, s.y / q, s.z / q});
+    mesh_store(n, v, mesh_div(s, q));
     len[v] = l;
   } else {
-    mg_store(n, v, MgVec{0.f, 0.f, 1.f});
+    mesh_store(n, v, MeshVec{0.f, 0.f, 1.f});
     len[v] = 0.f;
   }
 }
 
 // g_s = (g_n - n (n . g_n)) / len through the normalisation; 0 where the default normal was taken
-__global__ void __launch_bounds__(MG_THREADS)
+__global__ void __launch_bounds__(MESH_THREADS)
 mesh_geom_normalize_backward_kernel(const float* __restrict__ n, const float* __restrict__ len, const float* __restrict__ g_n, int64_t V,
                                     float* __restrict__ g_s) {
-  const int64_t v = (int64_t)blockIdx.x * MG_THREADS + threadIdx.x;
+  const int64_t v = (int64_t)blockIdx.x * MESH_THREADS + threadIdx.x;
   if (v >= V) return;
   const float l = len[v];
-  MgVec out = MgVec{0.f, 0.f, 0.f};
+  MeshVec out = MeshVec{0.f, 0.f, 0.f};
   if (l > 0.f) {
-    const MgVec nv = mg_load(n, v), g = mg_load(g_n, v);
-    const MgVec t = mg_sub(g, mg_scale(nv, mg_dot(nv, g)));
+    const MeshVec nv = mesh_load(n, v), g = mesh_load(g_n, v);
+    const MeshVec t = mesh_sub(g, mesh_scale(nv, mesh_dot(nv, g)));
     const float q = fmaxf(l, 1e-12f);
-    out = MgVec{t.x / q, t.y / q, t.z / q};
+    out = mesh_div(t, q);
   }
-  mg_store(g_s, v, out);
+  mesh_store(g_s, v, out);
 }
 
-__global__ void __launch_bounds__(MG_THREADS)
+__global__ void __launch_bounds__(MESH_THREADS)
 mesh_geom_normals_backward_kernel(const float* __restrict__ pos, const int32_t* __restrict__ faces, const int32_t* __restrict__ corner_start,
                                   const int32_t* __restrict__ corner_list, const float* __restrict__ g_s, int64_t V, int64_t F,
                                   float* __restrict__ g_pos) {
-  const int64_t v = (int64_t)blockIdx.x * MG_THREADS + threadIdx.x;
+  const int64_t v = (int64_t)blockIdx.x * MESH_THREADS + threadIdx.x;
   if (v >= V) return;
   int64_t lo, hi;
-  mg_row(corner_start, v, 3 * F, &lo, &hi);
-  MgVec acc = MgVec{0.f, 0.f, 0.f};
+  mesh_row(corner_start, v, 3 * F, &lo, &hi);
+  MeshVec acc = MeshVec{0.f, 0.f, 0.f};
   for (int64_t at = lo; at < hi; at++) {
     const int64_t c = corner_list[at];
     if ((uint64_t)c >= (uint64_t)(3 * F)) continue;
     const int64_t f = c / 3;
     const int k = (int)(c - 3 * f);
     int32_t i0, i1, i2;
-    if (!mg_face(faces, f, V, &i0, &i1, &i2)) continue;
-    const MgVec g = mg_add(mg_add(mg_load(g_s, i0), mg_load(g_s, i1)), mg_load(g_s, i2));
-    const MgVec p0 = mg_load(pos, i0);
-    const MgVec e1 = mg_sub(mg_load(pos, i1), p0), e2 = mg_sub(mg_load(pos, i2), p0);
-    const MgVec g1 = mg_cross(e2, g), g2 = mg_cross(g, e1);
-    MgVec share;
-    if (k == 1) {
-      share = g1;
-    } else if (k == 2) {
-      share = g2;
-    } else {
-      const MgVec t = mg_add(g1, g2);
-      share = MgVec{-t.x, -t.y, -t.z};
-    }
-    acc = mg_add(acc, share);
+    if (!mesh_face(faces, f, V, &i0, &i1, &i2)) continue;
+    const MeshVec g = mesh_add(mesh_add(mesh_load(g_s, i0), mesh_load(g_s, i1)), mesh_load(g_s, i2));
+    const MeshVec p0 = mesh_load(pos, i0);
+    const MeshVec e1 = mesh_sub(mesh_load(pos, i1), p0), e2 = mesh_sub(mesh_load(pos, i2), p0);
+    acc = mesh_add(acc, mesh_corner_share(k, mesh_cross(e2, g), mesh_cross(g, e1)));
   }
-  mg_store(g_pos, v, acc);
+  mesh_store(g_pos, v, acc);
 }
 
-__global__ void __launch_bounds__(MG_THREADS)
+__global__ void __launch_bounds__(MESH_THREADS)
 mesh_geom_laplacian_kernel(const float* __restrict__ pos, const int32_t* __restrict__ nbr_start, const int32_t* __restrict__ nbr_list,
                            int64_t V, int64_t N, float* __restrict__ unit, float* __restrict__ partial) {
-  const int64_t v = (int64_t)blockIdx.x * MG_THREADS + threadIdx.x;
+  const int64_t v = (int64_t)blockIdx.x * MESH_THREADS + threadIdx.x;
   float norm = 0.f;
   if (v < V) {
     int64_t lo, hi;
-    mg_row(nbr_start, v, N, &lo, &hi);
-    const MgVec p = mg_load(pos, v);
-    MgVec lp = MgVec{0.f, 0.f, 0.f};
+    mesh_row(nbr_start, v, N, &lo, &hi);
+    const MeshVec p = mesh_load(pos, v);
+    MeshVec lp = MeshVec{0.f, 0.f, 0.f};
     for (int64_t at = lo; at < hi; at++) {
       const int64_t j = nbr_list[at];
       if ((uint64_t)j >= (uint64_t)V) continue;
-      lp = mg_add(lp, mg_sub(p, mg_load(pos, j)));
+      lp = mesh_add(lp, mesh_sub(p, mesh_load(pos, j)));
     }
-    norm = sqrtf(mg_dot(lp, lp));
-    mg_store(unit, v, norm > 0.f ? MgVec{lp.x / norm, lp.y / norm, lp.z / norm} : MgVec{0.f, 0.f, 0.f});
+    norm = sqrtf(mesh_dot(lp, lp));
+    mesh_store(unit, v, norm > 0.f ? mesh_div(lp, norm) : MeshVec{0.f, 0.f, 0.f});
   }
   mg_block_sum(norm, partial);
 }
 
-__global__ void __launch_bounds__(MG_THREADS)
+__global__ void __launch_bounds__(MESH_THREADS)
 mesh_geom_laplacian_backward_kernel(const float* __restrict__ unit, const int32_t* __restrict__ nbr_start,
                                     const int32_t* __restrict__ nbr_list, const float* __restrict__ g_loss, int64_t V, int64_t N,
                                     float* __restrict__ g_pos) {
-  const int64_t v = (int64_t)blockIdx.x * MG_THREADS + threadIdx.x;
+  const int64_t v = (int64_t)blockIdx.x * MESH_THREADS + threadIdx.x;
   if (v >= V) return;
   int64_t lo, hi;
-  mg_row(nbr_start, v, N, &lo, &hi);
-  const MgVec u = mg_load(unit, v);
-  MgVec acc = MgVec{0.f, 0.f, 0.f};
+  mesh_row(nbr_start, v, N, &lo, &hi);
+  const MeshVec u = mesh_load(unit, v);
+  MeshVec acc = MeshVec{0.f, 0.f, 0.f};
   for (int64_t at = lo; at < hi; at++) {
     const int64_t j = nbr_list[at];
     if ((uint64_t)j >= (uint64_t)V) continue;
-    acc = mg_add(acc, mg_sub(u, mg_load(unit, j)));
+    acc = mesh_add(acc, mesh_sub(u, mesh_load(unit, j)));
   }
-  mg_store(g_pos, v, mg_scale(acc, g_loss[0] / (float)V));
+  mesh_store(g_pos, v, mesh_scale(acc, g_loss[0] / (float)V));
 }
 
-__global__ void __launch_bounds__(MG_THREADS)
+__global__ void __launch_bounds__(MESH_THREADS)
 mesh_geom_consistency_kernel(const float* __restrict__ n, const int32_t* __restrict__ nbr_start, const int32_t* __restrict__ nbr_list,
                              int64_t V, int64_t N, float* __restrict__ partial) {
-  const int64_t v = (int64_t)blockIdx.x * MG_THREADS + threadIdx.x;
+  const int64_t v = (int64_t)blockIdx.x * MESH_THREADS + threadIdx.x;
   float sum = 0.f;
   if (v < V) {
     int64_t lo, hi;
-    mg_row(nbr_start, v, N, &lo, &hi);
-    const MgVec a = mg_load(n, v);
-    const float la = fmaxf(sqrtf(mg_dot(a, a)), 1e-8f);
+    mesh_row(nbr_start, v, N, &lo, &hi);
+    const MeshVec a = mesh_load(n, v);
+    const float la = fmaxf(sqrtf(mesh_dot(a, a)), 1e-8f);
     for (int64_t at = lo; at < hi; at++) {
       const int64_t j = nbr_list[at];
       if ((uint64_t)j >= (uint64_t)V) continue;
-      const MgVec b = mg_load(n, j);
-      const float lb = fmaxf(sqrtf(mg_dot(b, b)), 1e-8f);
-      sum += 1.f - mg_dot(a, b) / (la * lb);
+      const MeshVec b = mesh_load(n, j);
+      const float lb = fmaxf(sqrtf(mesh_dot(b, b)), 1e-8f);
+      sum += 1.f - mesh_dot(a, b) / (la * lb);
     }
     sum *= 0.5f;      // the other half comes from the neighbour's row
   }
   mg_block_sum(sum, partial);
 }
 
-__global__ void __launch_bounds__(MG_THREADS)
+__global__ void __launch_bounds__(MESH_THREADS)
 mesh_geom_consistency_backward_kernel(const float* __restrict__ n, const int32_t* __restrict__ nbr_start,
                                       const int32_t* __restrict__ nbr_list, const float* __restrict__ g_loss, int64_t V, int64_t N,
                                       double edges, float* __restrict__ g_n) {
-  const int64_t v = (int64_t)blockIdx.x * MG_THREADS + threadIdx.x;
+  const int64_t v = (int64_t)blockIdx.x * MESH_THREADS + threadIdx.x;
   if (v >= V) return;
   int64_t lo, hi;
-  mg_row(nbr_start, v, N, &lo, &hi);
-  const MgVec a = mg_load(n, v);
-  const float la = fmaxf(sqrtf(mg_dot(a, a)), 1e-8f);
-  const MgVec ua = MgVec{a.x / la, a.y / la, a.z / la};
-  MgVec acc = MgVec{0.f, 0.f, 0.f};
+  mesh_row(nbr_start, v, N, &lo, &hi);
+  const MeshVec a = mesh_load(n, v);
+  const float la = fmaxf(sqrtf(mesh_dot(a, a)), 1e-8f);
+  const MeshVec ua = mesh_div(a, la);
+  MeshVec acc = MeshVec{0.f, 0.f, 0.f};
   for (int64_t at = lo; at < hi; at++) {
     const int64_t j = nbr_list[at];
     if ((uint64_t)j >= (uint64_t)V) continue;
-    const MgVec b = mg_load(n, j);
-    const float lb = fmaxf(sqrtf(mg_dot(b, b)), 1e-8f);
-    const float c = mg_dot(a, b) / (la * lb);
-    acc = mg_add(acc, mg_sub(MgVec{b.x / lb, b.y / lb, b.z / lb}, mg_scale(ua, c)));
+    const MeshVec b = mesh_load(n, j);
+    const float lb = fmaxf(sqrtf(mesh_dot(b, b)), 1e-8f);
+    const float c = mesh_dot(a, b) / (la * lb);
+    acc = mesh_add(acc, mesh_sub(mesh_div(b, lb), mesh_scale(ua, c)));
   }
   const float s = -(g_loss[0] / (float)edges) / la;
-  mg_store(g_n, v, mg_scale(acc, s));
+  mesh_store(g_n, v, mesh_scale(acc, s));
 }
 
 // the mean: the partials in index order, in double, divided by count; one workgroup
-__global__ void __launch_bounds__(MG_THREADS)
+__global__ void __launch_bounds__(MESH_THREADS)
 mesh_geom_finish_kernel(const float* __restrict__ partial, int64_t blocks, double count, float* __restrict__ loss) {
-  __shared__ double s_red[MG_THREADS / 64];
+  __shared__ double s_red[MESH_THREADS / 64];
   double acc = 0.0;
-  for (int64_t i = threadIdx.x; i < blocks; i += MG_THREADS) acc += (double)partial[i];
+  for (int64_t i = threadIdx.x; i < blocks; i += MESH_THREADS) acc += (double)partial[i];
 #pragma unroll
   for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, 64);
   if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = acc;
@@ -266,82 +219,71 @@ mesh_geom_finish_kernel(const float* __restrict__ partial, int64_t blocks, doubl
   if (threadIdx.x == 0) loss[0] = (float)(((s_red[0] + s_red[1]) + (s_red[2] + s_red[3])) / count);
 }
 
-// workgroups of one lane per item; 0 when the count is not launchable
-static int64_t mg_blocks(int64_t items) {
-  if (items < 1 || items > INT32_MAX) return 0;
-  return (items + MG_THREADS - 1) / MG_THREADS;
-}
-
-static bool mg_sizes_ok(int64_t V, int64_t rows) { return V >= 0 && V <= INT32_MAX && rows >= 0 && rows <= INT32_MAX; }
-
-#define MG_LAUNCH(kernel, blocks, stream, ...) \
-  hipLaunchKernelGGL(kernel, dim3((unsigned)(blocks)), dim3(MG_THREADS), 0, (hipStream_t)(stream), __VA_ARGS__)
-
 extern "C" int gip_mesh_geometry_workspace_size(int64_t V, size_t* bytes) {
-  if (!bytes || V < 0 || V > INT32_MAX) return 1;
-  *bytes = (size_t)mg_blocks(V) * sizeof(float);
+  if (!bytes || !mesh_count_ok(V)) return 1;
+  *bytes = (size_t)mesh_blocks(V) * sizeof(float);
   return 0;
 }
 
 extern "C" int gip_mesh_vertex_normals(const float* pos, const int32_t* faces, const int32_t* corner_start, const int32_t* corner_list,
                                        int64_t V, int64_t F, float* face_normals, float* n, float* len, void* stream) {
-  if (F < 0 || F > INT32_MAX / 3 || !mg_sizes_ok(V, 3 * F)) return 1;
+  if (!mesh_sizes_ok(V, F)) return 1;
   if (V == 0 || F == 0) return 0;
   if (!pos || !faces || !corner_start || !corner_list || !face_normals || !n || !len) return 1;
-  MG_LAUNCH(mesh_geom_face_normals_kernel, mg_blocks(F), stream, pos, faces, V, F, face_normals);
-  MG_LAUNCH(mesh_geom_normals_kernel, mg_blocks(V), stream, corner_start, corner_list, (const float*)face_normals, V, F, n, len);
-  return hipGetLastError() == hipSuccess ? 0 : 3;
+  MESH_LAUNCH(mesh_geom_face_normals_kernel, mesh_blocks(F), stream, pos, faces, V, F, face_normals);
+  MESH_LAUNCH(mesh_geom_normals_kernel, mesh_blocks(V), stream, corner_start, corner_list, (const float*)face_normals, V, F, n, len);
+  return mesh_done();
 }
 
 extern "C" int gip_mesh_vertex_normals_backward(const float* pos, const int32_t* faces, const int32_t* corner_start,
                                                 const int32_t* corner_list, const float* n, const float* len, const float* g_n, int64_t V,
                                                 int64_t F, float* g_s, float* g_pos, void* stream) {
-  if (F < 0 || F > INT32_MAX / 3 || !mg_sizes_ok(V, 3 * F)) return 1;
+  if (!mesh_sizes_ok(V, F)) return 1;
   if (V == 0 || F == 0) return 0;
   if (!pos || !faces || !corner_start || !corner_list || !n || !len || !g_n || !g_s || !g_pos) return 1;
-  MG_LAUNCH(mesh_geom_normalize_backward_kernel, mg_blocks(V), stream, n, len, g_n, V, g_s);
-  MG_LAUNCH(mesh_geom_normals_backward_kernel, mg_blocks(V), stream, pos, faces, corner_start, corner_list, (const float*)g_s, V, F, g_pos);
-  return hipGetLastError() == hipSuccess ? 0 : 3;
+  MESH_LAUNCH(mesh_geom_normalize_backward_kernel, mesh_blocks(V), stream, n, len, g_n, V, g_s);
+  MESH_LAUNCH(mesh_geom_normals_backward_kernel, mesh_blocks(V), stream, pos, faces, corner_start, corner_list, (const float*)g_s, V, F, g_pos);
+  return mesh_done();
 }
 
 extern "C" int gip_mesh_laplacian_loss(const float* pos, const int32_t* nbr_start, const int32_t* nbr_list, int64_t V, int64_t N,
                                        float* unit, float* loss, void* workspace, size_t workspace_bytes, void* stream) {
-  if (!mg_sizes_ok(V, N)) return 1;
+  if (!mesh_count_ok(V) || !mesh_count_ok(N)) return 1;
   if (V == 0) return 0;
   if (!pos || !nbr_start || (N > 0 && !nbr_list) || !unit || !loss || !workspace) return 1;
-  const int64_t blocks = mg_blocks(V);
+  const int64_t blocks = mesh_blocks(V);
   if (workspace_bytes < (size_t)blocks * sizeof(float)) return 1;
-  MG_LAUNCH(mesh_geom_laplacian_kernel, blocks, stream, pos, nbr_start, nbr_list, V, N, unit, (float*)workspace);
-  MG_LAUNCH(mesh_geom_finish_kernel, 1, stream, (const float*)workspace, blocks, (double)V, loss);
-  return hipGetLastError() == hipSuccess ? 0 : 3;
+  MESH_LAUNCH(mesh_geom_laplacian_kernel, blocks, stream, pos, nbr_start, nbr_list, V, N, unit, (float*)workspace);
+  MESH_LAUNCH(mesh_geom_finish_kernel, 1, stream, (const float*)workspace, blocks, (double)V, loss);
+  return mesh_done();
 }
 
 extern "C" int gip_mesh_laplacian_loss_backward(const float* unit, const int32_t* nbr_start, const int32_t* nbr_list, const float* g_loss,
                                                 int64_t V, int64_t N, float* g_pos, void* stream) {
-  if (!mg_sizes_ok(V, N)) return 1;
+  if (!mesh_count_ok(V) || !mesh_count_ok(N)) return 1;
   if (V == 0) return 0;
   if (!unit || !nbr_start || (N > 0 && !nbr_list) || !g_loss || !g_pos) return 1;
-  MG_LAUNCH(mesh_geom_laplacian_backward_kernel, mg_blocks(V), stream, unit, nbr_start, nbr_list, g_loss, V, N, g_pos);
-  return hipGetLastError() == hipSuccess ? 0 : 3;
+  MESH_LAUNCH(mesh_geom_laplacian_backward_kernel, mesh_blocks(V), stream, unit, nbr_start, nbr_list, g_loss, V, N, g_pos);
+  return mesh_done();
 }
 
 extern "C" int gip_mesh_normal_consistency(const float* n, const int32_t* nbr_start, const int32_t* nbr_list, int64_t V, int64_t N,
                                            int64_t E, float* loss, void* workspace, size_t workspace_bytes, void* stream) {
-  if (!mg_sizes_ok(V, N) || E < 0) return 1;
+  if (!mesh_count_ok(V) || !mesh_count_ok(N) || E < 0) return 1;
   if (V == 0 || E == 0) return 0;
   if (!n || !nbr_start || (N > 0 && !nbr_list) || !loss || !workspace) return 1;
-  const int64_t blocks = mg_blocks(V);
+  const int64_t blocks = mesh_blocks(V);
   if (workspace_bytes < (size_t)blocks * sizeof(float)) return 1;
-  MG_LAUNCH(mesh_geom_consistency_kernel, blocks, stream, n, nbr_start, nbr_list, V, N, (float*)workspace);
-  MG_LAUNCH(mesh_geom_finish_kernel, 1, stream, (const float*)workspace, blocks, (double)E, loss);
-  return hipGetLastError() == hipSuccess ? 0 : 3;
+  MESH_LAUNCH(mesh_geom_consistency_kernel, blocks, stream, n, nbr_start, nbr_list, V, N, (float*)workspace);
+  MESH_LAUNCH(mesh_geom_finish_kernel, 1, stream, (const float*)workspace, blocks, (double)E, loss);
+  return mesh_done();
 }
 
 extern "C" int gip_mesh_normal_consistency_backward(const float* n, const int32_t* nbr_start, const int32_t* nbr_list, const float* g_loss,
                                                     int64_t V, int64_t N, int64_t E, float* g_n, void* stream) {
-  if (!mg_sizes_ok(V, N) || E < 0) return 1;
+  if (!mesh_count_ok(V) || !mesh_count_ok(N) || E < 0) return 1;
   if (V == 0 || E == 0) return 0;
   if (!n || !nbr_start || (N > 0 && !nbr_list) || !g_loss || !g_n) return 1;
-  MG_LAUNCH(mesh_geom_consistency_backward_kernel, mg_blocks(V), stream, n, nbr_start, nbr_list, g_loss, V, N, (double)E, g_n);
-  return hipGetLastError() == hipSuccess ? 0 : 3;
+  MESH_LAUNCH(mesh_geom_consistency_backward_kernel, mesh_blocks(V), stream, n, nbr_start, nbr_list, g_loss, V, N, (double)E, g_n);
+  return mesh_done();
 }

@@ -326,9 +326,9 @@ extern "C" int gip_mesh_rasterize_backward(const float* pos, const int32_t* tri,
   if (F == 0 || V == 0) return 0;
   if (!pos || !tri || !g_pos) return 1;
   const int64_t pixels = (int64_t)B * H * W;
-  hipLaunchKernelGGL(mesh_rasterize_backward_kernel, dim3(mr_blocks(pixels)), dim3(MR_THREADS), 0, (hipStream_t)stream, pos, tri, (int)B,
+  hipLaunchKernelGGL(mesh_rasterize_backward_kernel, dim3(mesh_blocks(pixels)), dim3(MR_THREADS), 0, (hipStream_t)stream, pos, tri, (int)B,
                      (int)V, (int)F, (int)H, (int)W, (const float4*)rast, (const float4*)g_rast, g_pos);
-  return mr_done();
+  return mesh_done();
 }
 
 extern "C" int gip_mesh_interpolate_backward_rast(const float* g_out, const float* attr, int32_t attr_batch, int64_t N, int32_t C,
@@ -336,10 +336,10 @@ extern "C" int gip_mesh_interpolate_backward_rast(const float* g_out, const floa
                                                   float* g_rast, void* stream) {
   if (!mr_attr_ok(attr, attr_batch, N, C, idx, F, B, H, W) || !rast || !g_out || !g_rast) return 1;
   const int64_t pixels = (int64_t)B * H * W;
-  hipLaunchKernelGGL(mesh_interpolate_backward_rast_kernel, dim3(mr_blocks(pixels)), dim3(MR_THREADS), 0, (hipStream_t)stream, g_out, attr,
+  hipLaunchKernelGGL(mesh_interpolate_backward_rast_kernel, dim3(mesh_blocks(pixels)), dim3(MR_THREADS), 0, (hipStream_t)stream, g_out, attr,
                      mr_stride(attr_batch, N * C), idx, (const float4*)rast, pixels, (int64_t)H * W, (int)F, (int)N, (int)C,
                      (float4*)g_rast);
-  return mr_done();
+  return mesh_done();
 }
 
 extern "C" int gip_mesh_shade_backward_rast(const float* rast, const float* uv, int64_t F, int32_t flip_v, const float* tex, int32_t Th,
@@ -347,9 +347,9 @@ extern "C" int gip_mesh_shade_backward_rast(const float* rast, const float* uv, 
   if (!mr_image_ok(B, H, W) || !mr_tex_ok(Th, Tw, 3) || F < 0 || F > MR_MAX_FACES || !rast || !tex || !g_shaded || !g_rast) return 1;
   if (F > 0 && !uv) return 1;
   const int64_t pixels = (int64_t)B * H * W;
-  hipLaunchKernelGGL(mesh_shade_backward_rast_kernel, dim3(mr_blocks(pixels)), dim3(MR_THREADS), 0, (hipStream_t)stream, (const float4*)rast,
+  hipLaunchKernelGGL(mesh_shade_backward_rast_kernel, dim3(mesh_blocks(pixels)), dim3(MR_THREADS), 0, (hipStream_t)stream, (const float4*)rast,
                      uv, tex, (const float4*)g_shaded, pixels, (int)F, (int)(flip_v != 0), (int)Th, (int)Tw, (float4*)g_rast);
-  return mr_done();
+  return mesh_done();
 }
 
 static int mg_antialias_ok(const float* color, int32_t C, const float* rast, const float* pos, const int32_t* tri, const int32_t* topo,
@@ -362,9 +362,9 @@ extern "C" int gip_mesh_antialias(const float* color, int32_t C, const float* ra
                                   int32_t B, int64_t V, int64_t F, int32_t H, int32_t W, float* out, void* stream) {
   if (!mg_antialias_ok(color, C, rast, pos, tri, topo, B, V, F, H, W) || !out) return 1;
   const int64_t pixels = (int64_t)B * H * W;
-  hipLaunchKernelGGL(mesh_antialias_kernel, dim3(mr_blocks(pixels)), dim3(MR_THREADS), 0, (hipStream_t)stream, color, (int)C,
+  hipLaunchKernelGGL(mesh_antialias_kernel, dim3(mesh_blocks(pixels)), dim3(MR_THREADS), 0, (hipStream_t)stream, color, (int)C,
                      (const float4*)rast, pos, tri, topo, (int)B, (int)V, (int)F, (int)H, (int)W, out);
-  return mr_done();
+  return mesh_done();
 }
 
 extern "C" int gip_mesh_antialias_backward(const float* color, int32_t C, const float* rast, const float* pos, const int32_t* tri,
@@ -373,7 +373,7 @@ extern "C" int gip_mesh_antialias_backward(const float* color, int32_t C, const 
   if (!mg_antialias_ok(color, C, rast, pos, tri, topo, B, V, F, H, W) || !g_out) return 1;
   if (!g_color && !g_pos) return 0;
   const int64_t pixels = (int64_t)B * H * W;
-  hipLaunchKernelGGL(mesh_antialias_backward_kernel, dim3(mr_blocks(pixels)), dim3(MR_THREADS), 0, (hipStream_t)stream, color, (int)C,
+  hipLaunchKernelGGL(mesh_antialias_backward_kernel, dim3(mesh_blocks(pixels)), dim3(MR_THREADS), 0, (hipStream_t)stream, color, (int)C,
                      (const float4*)rast, pos, tri, topo, (int)B, (int)V, (int)F, (int)H, (int)W, g_out, g_color, g_pos);
-  return mr_done();
+  return mesh_done();
 }

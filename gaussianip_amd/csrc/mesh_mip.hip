@@ -355,9 +355,9 @@ extern "C" int gip_mesh_rast_db(const float* pos, const int32_t* tri, int32_t B,
   const int64_t pixels = (int64_t)B * H * W;
   if (F == 0 || V == 0) return hipMemsetAsync(rast_db, 0, (size_t)pixels * 16, st) == hipSuccess ? 0 : 3;
   if (!pos || !tri) return 1;
-  hipLaunchKernelGGL(mesh_rast_db_kernel, dim3(mr_blocks(pixels)), dim3(MR_THREADS), 0, st, pos, tri, (int)B, (int)V, (int)F, (int)H, (int)W,
+  hipLaunchKernelGGL(mesh_rast_db_kernel, dim3(mesh_blocks(pixels)), dim3(MR_THREADS), 0, st, pos, tri, (int)B, (int)V, (int)F, (int)H, (int)W,
                      (const float4*)rast, (float4*)rast_db);
-  return mr_done();
+  return mesh_done();
 }
 
 static int mm_attr_ok(const float* rows, int32_t attr_batch, int64_t N, int32_t C, const int32_t* idx, int64_t F, int32_t K, int32_t B, int32_t H,
@@ -370,10 +370,10 @@ extern "C" int gip_mesh_interpolate_da(const float* attr, int32_t attr_batch, in
                                        int32_t W, float* out_da, void* stream) {
   if (!mm_attr_ok(attr, attr_batch, N, C, idx, F, K, B, H, W) || !rast || !rast_db || !out_da) return 1;
   const int64_t pixels = (int64_t)B * H * W;
-  hipLaunchKernelGGL(mesh_interpolate_da_kernel, dim3(mr_blocks(pixels)), dim3(MR_THREADS), 0, (hipStream_t)stream, attr,
+  hipLaunchKernelGGL(mesh_interpolate_da_kernel, dim3(mesh_blocks(pixels)), dim3(MR_THREADS), 0, (hipStream_t)stream, attr,
                      mr_stride(attr_batch, N * C), idx, (const float4*)rast, (const float4*)rast_db, channels, (int)K, pixels,
                      (int64_t)H * W, (int)F, (int)N, (int)C, (float2*)out_da);
-  return mr_done();
+  return mesh_done();
 }
 
 extern "C" int gip_mesh_interpolate_da_backward(const float* g_da, int32_t attr_batch, int64_t N, int32_t C, const int32_t* idx, int64_t F,
@@ -385,10 +385,10 @@ extern "C" int gip_mesh_interpolate_da_backward(const float* g_da, int32_t attr_
   hipStream_t st = (hipStream_t)stream;
   if (hipMemsetAsync(g_attr, 0, (size_t)attr_batch * N * C * sizeof(float), st) != hipSuccess) return 3;
   const int64_t pixels = (int64_t)B * H * W;
-  hipLaunchKernelGGL(mesh_interpolate_da_backward_kernel, dim3(mr_blocks(pixels)), dim3(MR_THREADS), 0, st, (const float2*)g_da, idx,
+  hipLaunchKernelGGL(mesh_interpolate_da_backward_kernel, dim3(mesh_blocks(pixels)), dim3(MR_THREADS), 0, st, (const float2*)g_da, idx,
                      (const float4*)rast, (const float4*)rast_db, channels, (int)K, pixels, (int64_t)H * W, (int)F, (int)N, (int)C, g_attr,
                      mr_stride(attr_batch, N * C));
-  return mr_done();
+  return mesh_done();
 }
 
 extern "C" int gip_mesh_mip_levels(int32_t Th, int32_t Tw, int32_t max_level, int32_t* levels, int64_t* texels) {
@@ -418,11 +418,11 @@ extern "C" int gip_mesh_mip_build(const float* tex, int32_t tex_batch, int32_t T
   for (int l = 0; l < L; l++) {
     const MmLevel lo = mm_level(Th, Tw, l), hi = mm_level(Th, Tw, l + 1);
     const int64_t n = (int64_t)tex_batch * hi.h * hi.w * C;
-    hipLaunchKernelGGL(mesh_mip_build_kernel, dim3(mr_blocks(n)), dim3(MR_THREADS), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(mesh_mip_build_kernel, dim3(mesh_blocks(n)), dim3(MR_THREADS), 0, (hipStream_t)stream,
                        l == 0 ? tex : (const float*)(mip + lo.off * C), l == 0 ? (int64_t)Th * Tw * C : mip_texels * C, mip + hi.off * C,
                        mip_texels * C, lo.h, lo.w, (int)C, n);
   }
-  return mr_done();
+  return mesh_done();
 }
 
 extern "C" int gip_mesh_mip_fold(float* g_tex, int32_t tex_batch, int32_t Th, int32_t Tw, int32_t C, int32_t max_level, float* g_mip,
@@ -434,11 +434,11 @@ extern "C" int gip_mesh_mip_fold(float* g_tex, int32_t tex_batch, int32_t Th, in
   for (int l = L - 1; l >= 0; l--) {
     const MmLevel lo = mm_level(Th, Tw, l), hi = mm_level(Th, Tw, l + 1);
     const int64_t n = (int64_t)tex_batch * lo.h * lo.w * C;
-    hipLaunchKernelGGL(mesh_mip_fold_kernel, dim3(mr_blocks(n)), dim3(MR_THREADS), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(mesh_mip_fold_kernel, dim3(mesh_blocks(n)), dim3(MR_THREADS), 0, (hipStream_t)stream,
                        l == 0 ? g_tex : g_mip + lo.off * C, l == 0 ? (int64_t)Th * Tw * C : mip_texels * C,
                        (const float*)(g_mip + hi.off * C), mip_texels * C, lo.h, lo.w, (int)C, n);
   }
-  return mr_done();
+  return mesh_done();
 }
 
 extern "C" int gip_mesh_texture_mip(const float* tex, int32_t tex_batch, int32_t Th, int32_t Tw, int32_t C, const float* mip,
@@ -448,10 +448,10 @@ extern "C" int gip_mesh_texture_mip(const float* tex, int32_t tex_batch, int32_t
   if (!mr_batch_ok(B, H, W, tex_batch) || !mm_stack_ok(tex_batch, Th, Tw, C, max_level, mip_texels, L) || !tex || !uv || !out) return 1;
   if (L > 0 && !mip) return 1;
   const int64_t pixels = (int64_t)B * H * W;
-  hipLaunchKernelGGL(mesh_texture_mip_kernel, dim3(mr_blocks(pixels)), dim3(MR_THREADS), 0, (hipStream_t)stream, tex,
+  hipLaunchKernelGGL(mesh_texture_mip_kernel, dim3(mesh_blocks(pixels)), dim3(MR_THREADS), 0, (hipStream_t)stream, tex,
                      mr_stride(tex_batch, (int64_t)Th * Tw * C), mip, mr_stride(tex_batch, mip_texels * C), (const float2*)uv,
                      (const float4*)uv_da, bias, pixels, (int64_t)H * W, (int)Th, (int)Tw, (int)C, L, (int)(nearest != 0), out);
-  return mr_done();
+  return mesh_done();
 }
 
 extern "C" int gip_mesh_texture_mip_backward(const float* tex, int32_t tex_batch, int32_t Th, int32_t Tw, int32_t C, const float* mip,
@@ -466,9 +466,9 @@ extern "C" int gip_mesh_texture_mip_backward(const float* tex, int32_t tex_batch
   if (g_tex && hipMemsetAsync(g_tex, 0, (size_t)tex_batch * Th * Tw * C * sizeof(float), st) != hipSuccess) return 3;
   if (g_tex && L > 0 && hipMemsetAsync(g_mip, 0, (size_t)tex_batch * mip_texels * C * sizeof(float), st) != hipSuccess) return 3;
   const int64_t pixels = (int64_t)B * H * W;
-  hipLaunchKernelGGL(mesh_texture_mip_backward_kernel, dim3(mr_blocks(pixels)), dim3(MR_THREADS), 0, st, tex,
+  hipLaunchKernelGGL(mesh_texture_mip_backward_kernel, dim3(mesh_blocks(pixels)), dim3(MR_THREADS), 0, st, tex,
                      mr_stride(tex_batch, (int64_t)Th * Tw * C), mip, mr_stride(tex_batch, mip_texels * C), (const float2*)uv,
                      (const float4*)uv_da, bias, g_out, pixels, (int64_t)H * W, (int)Th, (int)Tw, (int)C, L, (int)(nearest != 0), g_tex,
                      L > 0 ? g_mip : (float*)nullptr, (float2*)g_uv, (float4*)g_uv_da, g_bias);
-  return mr_done();
+  return mesh_done();
 }

@@ -64,10 +64,7 @@ __device__ __forceinline__ void mr_fragment(const MrTri& t, int64_t e0, int64_t 
   mr_weights(t, e0, e1, e2, b0, b1, b2);
   const float d = b0 * t.zw0 + b1 * t.zw1 + b2 * t.zw2;
   if (!(d >= -1.f && d <= 1.f)) return;
-  uint32_t u = __float_as_uint(d);
-  if ((u & 0x7fffffffu) == 0) u = 0;
-  u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-  atomicMin(at, ((mr_key)u << 32) | f);
+  atomicMin(at, ((mr_key)mesh_float_key(d) << 32) | f);
 }
 
 // the pixel centres inside the bounding box, clipped to the image; false when there is none
@@ -165,8 +162,7 @@ mesh_resolve_kernel(const float* __restrict__ pos, const int32_t* __restrict__ t
     const MrPixel p = mr_pixel(g, H, W);
     MrTri t;
     if (mr_load(pos + (int64_t)p.b * V * 4, tri, (int)f, V, H, W, 0, t)) {
-      const uint32_t u = (uint32_t)(key >> 32);
-      const float d = __uint_as_float((u & 0x80000000u) ? (u ^ 0x80000000u) : ~u);
+      const float d = mesh_key_float((uint32_t)(key >> 32));
       const MrPersp w = mr_persp(t, p.px, p.py);
       out = make_float4(w.q0 / w.S, w.q1 / w.S, d, (float)(f + 1));
     }
@@ -310,24 +306,24 @@ extern "C" int gip_mesh_rasterize(const float* pos, const int32_t* tri, int32_t 
   int32_t* list = (int32_t*)(count + 4);
   if (hipMemsetAsync(keys, 0xFF, (size_t)pixels * sizeof(mr_key), st) != hipSuccess) return 3;
   if (hipMemsetAsync(count, 0, 16, st) != hipSuccess) return 3;
-  hipLaunchKernelGGL(mesh_setup_kernel, dim3(mr_blocks((int64_t)B * F)), dim3(MR_THREADS), 0, st, pos, tri, (int)B, (int)V, (int)F, (int)H,
+  hipLaunchKernelGGL(mesh_setup_kernel, dim3(mesh_blocks((int64_t)B * F)), dim3(MR_THREADS), 0, st, pos, tri, (int)B, (int)V, (int)F, (int)H,
                      (int)W, (int)(cull_backfaces != 0), keys, count, list);
   const int64_t waves = (int64_t)B * F;
   const unsigned large = (unsigned)((waves + 3) / 4 < MR_LARGE_BLOCKS ? (waves + 3) / 4 : MR_LARGE_BLOCKS);
   hipLaunchKernelGGL(mesh_large_kernel, dim3(large), dim3(MR_THREADS), 0, st, pos, tri, (int)B, (int)V, (int)F, (int)H, (int)W,
                      (int)(cull_backfaces != 0), keys, (const uint32_t*)count, (const int32_t*)list);
-  hipLaunchKernelGGL(mesh_resolve_kernel, dim3(mr_blocks(pixels)), dim3(MR_THREADS), 0, st, pos, tri, (int)B, (int)V, (int)F, (int)H, (int)W,
+  hipLaunchKernelGGL(mesh_resolve_kernel, dim3(mesh_blocks(pixels)), dim3(MR_THREADS), 0, st, pos, tri, (int)B, (int)V, (int)F, (int)H, (int)W,
                      (const mr_key*)keys, (float4*)rast);
-  return mr_done();
+  return mesh_done();
 }
 
 extern "C" int gip_mesh_interpolate(const float* attr, int32_t attr_batch, int64_t N, int32_t C, const int32_t* idx, int64_t F,
                                     const float* rast, int32_t B, int32_t H, int32_t W, float* out, void* stream) {
   if (!mr_attr_ok(attr, attr_batch, N, C, idx, F, B, H, W) || !rast || !out) return 1;
   const int64_t pixels = (int64_t)B * H * W;
-  hipLaunchKernelGGL(mesh_interpolate_kernel, dim3(mr_blocks(pixels)), dim3(MR_THREADS), 0, (hipStream_t)stream, attr,
+  hipLaunchKernelGGL(mesh_interpolate_kernel, dim3(mesh_blocks(pixels)), dim3(MR_THREADS), 0, (hipStream_t)stream, attr,
                      mr_stride(attr_batch, N * C), idx, (const float4*)rast, pixels, (int64_t)H * W, (int)F, (int)N, (int)C, out);
-  return mr_done();
+  return mesh_done();
 }
 
 extern "C" int gip_mesh_interpolate_backward(const float* g_out, int32_t attr_batch, int64_t N, int32_t C, const int32_t* idx, int64_t F,
@@ -338,19 +334,19 @@ extern "C" int gip_mesh_interpolate_backward(const float* g_out, int32_t attr_ba
   hipStream_t st = (hipStream_t)stream;
   if (hipMemsetAsync(g_attr, 0, (size_t)attr_batch * N * C * sizeof(float), st) != hipSuccess) return 3;
   const int64_t pixels = (int64_t)B * H * W;
-  hipLaunchKernelGGL(mesh_interpolate_backward_kernel, dim3(mr_blocks(pixels)), dim3(MR_THREADS), 0, st, g_out, idx, (const float4*)rast,
+  hipLaunchKernelGGL(mesh_interpolate_backward_kernel, dim3(mesh_blocks(pixels)), dim3(MR_THREADS), 0, st, g_out, idx, (const float4*)rast,
                      pixels, (int64_t)H * W, (int)F, (int)N, (int)C, g_attr, mr_stride(attr_batch, N * C));
-  return mr_done();
+  return mesh_done();
 }
 
 extern "C" int gip_mesh_texture(const float* tex, int32_t tex_batch, int32_t Th, int32_t Tw, int32_t C, const float* uv, int32_t B,
                                 int32_t H, int32_t W, float* out, void* stream) {
   if (!mr_batch_ok(B, H, W, tex_batch) || !mr_tex_ok(Th, Tw, C) || !tex || !uv || !out) return 1;
   const int64_t pixels = (int64_t)B * H * W;
-  hipLaunchKernelGGL(mesh_texture_kernel, dim3(mr_blocks(pixels)), dim3(MR_THREADS), 0, (hipStream_t)stream, tex,
+  hipLaunchKernelGGL(mesh_texture_kernel, dim3(mesh_blocks(pixels)), dim3(MR_THREADS), 0, (hipStream_t)stream, tex,
                      mr_stride(tex_batch, (int64_t)Th * Tw * C), (const float2*)uv, pixels, (int64_t)H * W, (int)Th, (int)Tw, (int)C,
                      out);
-  return mr_done();
+  return mesh_done();
 }
 
 extern "C" int gip_mesh_texture_backward(const float* tex, int32_t tex_batch, int32_t Th, int32_t Tw, int32_t C, const float* uv,
@@ -360,10 +356,10 @@ extern "C" int gip_mesh_texture_backward(const float* tex, int32_t tex_batch, in
   hipStream_t st = (hipStream_t)stream;
   if (g_tex && hipMemsetAsync(g_tex, 0, (size_t)tex_batch * Th * Tw * C * sizeof(float), st) != hipSuccess) return 3;
   const int64_t pixels = (int64_t)B * H * W;
-  hipLaunchKernelGGL(mesh_texture_backward_kernel, dim3(mr_blocks(pixels)), dim3(MR_THREADS), 0, st, tex,
+  hipLaunchKernelGGL(mesh_texture_backward_kernel, dim3(mesh_blocks(pixels)), dim3(MR_THREADS), 0, st, tex,
                      mr_stride(tex_batch, (int64_t)Th * Tw * C), (const float2*)uv, g_out, pixels, (int64_t)H * W, (int)Th, (int)Tw,
                      (int)C, g_tex, (float2*)g_uv);
-  return mr_done();
+  return mesh_done();
 }
 
 extern "C" int gip_mesh_shade(const float* rast, const float* uv, int64_t F, int32_t flip_v, const float* tex, int32_t Th, int32_t Tw, const float* bg,
@@ -371,9 +367,9 @@ extern "C" int gip_mesh_shade(const float* rast, const float* uv, int64_t F, int
   if (!mr_image_ok(B, H, W) || !mr_tex_ok(Th, Tw, 3) || F < 0 || F > MR_MAX_FACES || !rast || !tex || !bg || !shaded) return 1;
   if (F > 0 && !uv) return 1;
   const int64_t pixels = (int64_t)B * H * W;
-  hipLaunchKernelGGL(mesh_shade_kernel, dim3(mr_blocks(pixels)), dim3(MR_THREADS), 0, (hipStream_t)stream, (const float4*)rast, uv, tex, bg,
+  hipLaunchKernelGGL(mesh_shade_kernel, dim3(mesh_blocks(pixels)), dim3(MR_THREADS), 0, (hipStream_t)stream, (const float4*)rast, uv, tex, bg,
                      pixels, (int)F, (int)(flip_v != 0), (int)Th, (int)Tw, (float4*)shaded);
-  return mr_done();
+  return mesh_done();
 }
 
 extern "C" int gip_mesh_shade_backward(const float* rast, const float* uv, int64_t F, int32_t flip_v, const float* tex, int32_t Th, int32_t Tw,
@@ -386,7 +382,7 @@ extern "C" int gip_mesh_shade_backward(const float* rast, const float* uv, int64
   if (g_uv && F > 0 && hipMemsetAsync(g_uv, 0, (size_t)F * 6 * sizeof(float), st) != hipSuccess) return 3;
   if (F == 0) return 0;
   const int64_t pixels = (int64_t)B * H * W;
-  hipLaunchKernelGGL(mesh_shade_backward_kernel, dim3(mr_blocks(pixels)), dim3(MR_THREADS), 0, st, (const float4*)rast, uv, tex,
+  hipLaunchKernelGGL(mesh_shade_backward_kernel, dim3(mesh_blocks(pixels)), dim3(MR_THREADS), 0, st, (const float4*)rast, uv, tex,
                      (const float4*)g_shaded, pixels, (int)F, (int)(flip_v != 0), (int)Th, (int)Tw, g_tex, g_uv);
-  return mr_done();
+  return mesh_done();
 }

@@ -7,8 +7,9 @@
 #include <stdint.h>
 
 #include "../../include/gip_model.h"
+#include "mesh_common.h"      // the depth test's float key; mesh_blocks (the *_ok checks below keep every count inside INT32_MAX), mesh_done
 
-#define MR_THREADS 256
+#define MR_THREADS MESH_THREADS
 #define MR_GUARD 4194304.f     // 2^22: the guard band of snapped coordinates
 #define MR_MAX_SIZE 16384      // image side: 256 * side + 128 stays inside the guard band
 #define MR_MAX_FACES 16777215  // triangle index + 1 must be exact in float32
@@ -220,10 +221,6 @@ static int mr_attr_ok(const float* rows, int32_t attr_batch, int64_t N, int32_t 
   return mr_batch_ok(B, H, W, attr_batch) && N >= 0 && N <= INT32_MAX && C >= 1 && F >= 0 && F <= MR_MAX_FACES && (idx || N == 3 * F) &&
          N * C <= INT32_MAX && (rows || F == 0 || N == 0);
 }
-
-static unsigned mr_blocks(int64_t n) { return (unsigned)((n + MR_THREADS - 1) / MR_THREADS); }
-
-static int mr_done(void) { return hipGetLastError() == hipSuccess ? 0 : 3; }
 
 static int mr_tex_ok(int32_t Th, int32_t Tw, int32_t C) {
   return Th >= 1 && Tw >= 1 && C >= 1 && Th <= MR_MAX_SIZE && Tw <= MR_MAX_SIZE && (int64_t)Th * Tw * C <= INT32_MAX;

@@ -5,14 +5,10 @@ clean_mesh, cluster_decimate, decimate_mesh.
 
 The reference hands its density grid to the third-party `mcubes` (gs_renderer.py:338-340); here the surface is extracted on the
 GPU.  There is no CPU path: a tensor that is not a float32 GPU tensor is an error."""
-import ctypes
-
 import numpy as np
 import torch
 
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr())
+from .._lib import call_model, ptr
 
 
 def extract_surface(field, threshold):
@@ -21,7 +17,6 @@ def extract_surface(field, threshold):
     A grid point is inside when field >= threshold; a vertex sits on a grid edge (cube edge, face diagonal or body diagonal) whose
     ends differ, at t = (threshold - f0) / (f1 - f0); normals point toward decreasing values; the surface is closed wherever it does
     not reach the grid boundary.  Vertex and face order are fixed by the grid, so two calls return identical tensors."""
-    from .. import _lib
     if not (isinstance(field, torch.Tensor) and field.is_cuda and field.dtype == torch.float32 and field.dim() == 3 and
             field.shape[0] == field.shape[1] == field.shape[2]):
         raise ValueError("extract_surface needs an [R, R, R] float32 GPU tensor")
@@ -29,14 +24,11 @@ def extract_surface(field, threshold):
     if R < 2 or 7 * R ** 3 > 2 ** 31 - 1:
         raise ValueError("extract_surface: resolution %d is outside 2 .. 674" % R)
     field = field.detach().contiguous()
-    dev, lib = field.device, _lib.model_lib()
+    dev = field.device
     with torch.cuda.device(dev):
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         edge_flag = torch.empty(R ** 3 * 7, dtype=torch.int32, device=dev)
         tri_count = torch.empty((R - 1) ** 3, dtype=torch.int32, device=dev)
-        rc = lib.gip_surface_count(_ptr(field), R, float(threshold), _ptr(edge_flag), _ptr(tri_count), stream)
-        if rc != 0:
-            raise RuntimeError("gip_surface_count failed with status %d" % rc)
+        call_model(dev, "gip_surface_count", ptr(field), R, float(threshold), ptr(edge_flag), ptr(tri_count))
         edge_end = torch.cumsum(edge_flag, 0, dtype=torch.int32)
         tri_end = torch.cumsum(tri_count, 0, dtype=torch.int32)
         V, F = (int(n) for n in torch.stack((edge_end[-1], tri_end[-1])).cpu())      # the host read that sizes the outputs
@@ -45,10 +37,8 @@ def extract_surface(field, threshold):
         if V == 0 or F == 0:
             return vertices, faces
         edge_index, tri_offset = edge_end - edge_flag, tri_end - tri_count           # exclusive scans
-        rc = lib.gip_surface_emit(_ptr(field), R, float(threshold), _ptr(edge_flag), _ptr(edge_index), _ptr(tri_offset), _ptr(vertices),
-                                  _ptr(faces), stream)
-        if rc != 0:
-            raise RuntimeError("gip_surface_emit failed with status %d" % rc)
+        call_model(dev, "gip_surface_emit", ptr(field), R, float(threshold), ptr(edge_flag), ptr(edge_index), ptr(tri_offset), ptr(vertices),
+                   ptr(faces))
     return vertices, faces
 
 
@@ -57,11 +47,6 @@ _CC_BATCH = 4             # rounds of hook + compress between two reads of the `
 MAX_GRID = 2048
 MAX_CLUSTER_VERTICES = 2 ** 21 - 1      # three ids are packed into one 63-bit sort key
 PLACE_LANES = 16          # lanes per cell of the placement kernel (DESIGN.md "Cleaning and decimating the mesh" has the measurement)
-
-
-def _check(rc, name):
-    if rc != 0:
-        raise RuntimeError("%s failed with status %d" % (name, rc))
 
 
 def _mesh_args(what, vertices, faces):
@@ -78,8 +63,20 @@ def _mesh_args(what, vertices, faces):
     return (None if vertices is None else vertices.detach().contiguous()), faces.detach().contiguous()
 
 
-def _stream(dev):
-    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+def settle_labels(step, limit, batch, what):
+    """The host loop of a label propagation (csrc/mesh_common.h "Labels"): step() launches `batch` rounds and returns the `changed` flag
+    tensor, which the caller creates as 0 and the loop zeroes again before every further call.  Returns once a call changed nothing;
+    RuntimeError("<what> did not settle in %d rounds") after more than limit + 1 + batch rounds (whole batches, and the batch that
+    confirms), which cannot happen for `limit` items because labels only decrease."""
+    rounds = 0
+    while True:
+        changed = step()
+        rounds += batch
+        if int(changed.item()) == 0:
+            return
+        if rounds > limit + 1 + batch:
+            raise RuntimeError("%s did not settle in %d rounds" % (what, rounds))
+        changed.zero_()
 
 
 def _compact(keep, rank, count, values):
@@ -94,10 +91,9 @@ def connected_components(faces, num_vertices):
     """labels [V] int32: labels[v] is the smallest vertex index of v's connected component.  Two vertices are connected when a face
     names both (so components that touch at one vertex are one component, and a face with a repeated index connects what it names); a
     vertex that no face names is its own component; a face with an index outside [0, V) is ignored.  The result depends on nothing
-    but `faces`.  Rounds of a hook and a compress kernel (csrc/mesh_clean.hip, whose header says why the fixed point is the minimum)
-    until one changes nothing; the flag is read once every %d rounds.  RuntimeError if that takes more than V + 1 rounds (whole batches,
-    and the batch that confirms): it cannot, because labels only decrease."""
-    from .. import _lib
+    but `faces`.  Rounds of a hook and a compress kernel (csrc/mesh_clean.hip; csrc/mesh_common.h says why the fixed point is the
+    minimum) until one changes nothing; the flag is read once every %d rounds.  RuntimeError if that takes more than V + 1 rounds (whole
+    batches, and the batch that confirms): it cannot, because labels only decrease."""
     _, faces = _mesh_args("connected_components", None, faces)
     V, F = int(num_vertices), int(faces.shape[0])
     if V < 0 or V > 2 ** 31 - 1:
@@ -106,19 +102,13 @@ def connected_components(faces, num_vertices):
     labels = torch.arange(V, dtype=torch.int32, device=dev)
     if F == 0 or V == 0:
         return labels
-    lib = _lib.model_lib()
     changed = torch.zeros(1, dtype=torch.int32, device=dev)
-    rounds = 0
-    with torch.cuda.device(dev):
-        while True:
-            changed.zero_()
-            _check(lib.gip_mesh_components_rounds(_ptr(faces), F, V, _ptr(labels), _ptr(changed), _CC_BATCH, _stream(dev)),
-                   "gip_mesh_components_rounds")
-            rounds += _CC_BATCH
-            if int(changed.item()) == 0:
-                return labels
-            if rounds > V + 1 + _CC_BATCH:
-                raise RuntimeError("connected_components did not settle in %d rounds" % rounds)
+
+    def rounds():
+        call_model(dev, "gip_mesh_components_rounds", ptr(faces), F, V, ptr(labels), ptr(changed), _CC_BATCH)
+        return changed
+    settle_labels(rounds, V, _CC_BATCH, "connected_components")
+    return labels
 
 
 connected_components.__doc__ %= _CC_BATCH
@@ -141,7 +131,6 @@ def clean_mesh(vertices, faces, min_faces=8, min_diameter=0.05, keep_largest=Fal
     face), "num_components" (components with at least one face) and "num_kept".
     validate: one host read checks that every index lies in [0, V) (ValueError otherwise); the kernels skip such a face regardless,
     and it is dropped.  F == 0 returns empty tensors without a launch.  One host read sizes the outputs."""
-    from .. import _lib
     vertices, faces = _mesh_args("clean_mesh", vertices, faces)
     if int(min_faces) < 0 or not float(min_diameter) >= 0:
         raise ValueError("clean_mesh: min_faces and min_diameter must not be negative")
@@ -160,9 +149,7 @@ def clean_mesh(vertices, faces, min_faces=8, min_diameter=0.05, keep_largest=Fal
     labels = connected_components(faces, V)
     count = torch.empty(V, dtype=torch.int32, device=dev)
     box = torch.empty((V, 6), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        _check(_lib.model_lib().gip_mesh_component_stats(_ptr(vertices), _ptr(faces), F, V, _ptr(labels), _ptr(count), _ptr(box), _stream(dev)),
-               "gip_mesh_component_stats")
+    call_model(dev, "gip_mesh_component_stats", ptr(vertices), ptr(faces), F, V, ptr(labels), ptr(count), ptr(box))
     has = count > 0
     inf = torch.full_like(box[:, :3], float("inf"))
     mn, mx = torch.where(has[:, None], box[:, :3], inf), torch.where(has[:, None], box[:, 3:], -inf)
@@ -211,7 +198,6 @@ def _cell_size(L, n):
 def cluster_face_count(vertices, faces, grid, frame=None):
     """The faces whose three corners fall in three different cells of cluster_decimate's grid: what decimate_mesh bisects on (before the
     removal of duplicates, so an upper bound of cluster_decimate's face count).  One kernel and one host read."""
-    from .. import _lib
     vertices, faces = _mesh_args("cluster_face_count", vertices, faces)
     n = _grid_arg("cluster_face_count", grid)
     if int(faces.shape[0]) == 0:
@@ -219,23 +205,19 @@ def cluster_face_count(vertices, faces, grid, frame=None):
     lo, L = _grid_frame("cluster_face_count", vertices) if frame is None else frame
     dev = vertices.device
     count = torch.empty(1, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        _check(_lib.model_lib().gip_mesh_cluster_count(_ptr(vertices), int(vertices.shape[0]), _ptr(faces), int(faces.shape[0]), float(lo[0]),
-                                                       float(lo[1]), float(lo[2]), _cell_size(L, n), n, _ptr(count), _stream(dev)),
-               "gip_mesh_cluster_count")
+    call_model(dev, "gip_mesh_cluster_count", ptr(vertices), int(vertices.shape[0]), ptr(faces), int(faces.shape[0]), float(lo[0]),
+               float(lo[1]), float(lo[2]), _cell_size(L, n), n, ptr(count))
     return int(count.item())
 
 
 def _cluster_runs(vertices, faces, n):
     """What the placement kernel walks: the occupied cells' keys in ascending order, every vertex's cell id, and the face corners and
     the vertices stably sorted by cell with the cells' offsets (csrc/mesh_clean.hip mc_place_kernel)."""
-    from .. import _lib
     V, dev = int(vertices.shape[0]), vertices.device
     lo, L = _grid_frame("cluster_decimate", vertices)
     frame = (float(lo[0]), float(lo[1]), float(lo[2]), _cell_size(L, n), n)
     keys = torch.empty(V, dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        _check(_lib.model_lib().gip_mesh_cluster_keys(_ptr(vertices), V, *frame, _ptr(keys), _stream(dev)), "gip_mesh_cluster_keys")
+    call_model(dev, "gip_mesh_cluster_keys", ptr(vertices), V, *frame, ptr(keys))
     cell_key, cell_of = torch.unique(keys, sorted=True, return_inverse=True)      # the host read for the count is in here
     C = int(cell_key.shape[0])
     fl = faces.long()
@@ -250,14 +232,11 @@ def _cluster_runs(vertices, faces, n):
 
 def _cluster_place(vertices, faces, runs, lanes):
     """[C, 3]: one launch of gip_mesh_cluster_place on the runs of _cluster_runs."""
-    from .. import _lib
     dev, C = vertices.device, int(runs["cell_key"].shape[0])
     placed = torch.empty((C, 3), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        _check(_lib.model_lib().gip_mesh_cluster_place(
-            _ptr(vertices), int(vertices.shape[0]), _ptr(faces), int(faces.shape[0]), _ptr(runs["cell_key"]), C, _ptr(runs["corner_order"]),
-            _ptr(runs["corner_start"]), _ptr(runs["member_order"]), _ptr(runs["member_start"]), *runs["frame"], lanes, _ptr(placed),
-            _stream(dev)), "gip_mesh_cluster_place")
+    call_model(dev, "gip_mesh_cluster_place", ptr(vertices), int(vertices.shape[0]), ptr(faces), int(faces.shape[0]), ptr(runs["cell_key"]), C,
+               ptr(runs["corner_order"]), ptr(runs["corner_start"]), ptr(runs["member_order"]), ptr(runs["member_start"]), *runs["frame"], lanes,
+               ptr(placed))
     return placed
 
 

@@ -13,22 +13,11 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from .. import _lib
+from .._lib import call_model, ptr
 
 __all__ = ["MeshTopology", "vertex_normals", "laplacian_loss", "normal_consistency", "Mesh"]
 
 _INT32_MAX = 2 ** 31 - 1
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr() if t is not None and t.numel() else None)
-
-
-def _call(dev, name, *args):
-    """The library's entry point `name` with args and, as its last argument, dev's current stream; RuntimeError unless it returns 0."""
-    with torch.cuda.device(dev):
-        rc = getattr(_lib.model_lib(), name)(*args, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    if rc != 0:
-        raise RuntimeError("%s failed with status %d" % (name, rc))
 
 
 def _row_starts(owner, V):
@@ -100,7 +89,7 @@ class MeshTopology:
         return other
 
 
-def _args(what, vertices, topology):
+def check_topology(what, vertices, topology):
     if not (isinstance(vertices, torch.Tensor) and vertices.is_cuda and vertices.dtype == torch.float32 and vertices.dim() == 2 and
             vertices.shape[1] == 3):
         raise ValueError("%s: vertices must be a [V, 3] float32 GPU tensor" % what)
@@ -128,8 +117,8 @@ class _VertexNormals(torch.autograd.Function):
         n = torch.empty((V, 3), dtype=torch.float32, device=pos.device)
         length = torch.empty(V, dtype=torch.float32, device=pos.device)
         face_normals = torch.empty((F, 3), dtype=torch.float32, device=pos.device)      # the per-face pass's output, read by the gather
-        _call(pos.device, "gip_mesh_vertex_normals", _p(pos), _p(topo.faces), _p(topo.corner_start), _p(topo.corner_list), V, F,
-              _p(face_normals), _p(n), _p(length))
+        call_model(pos.device, "gip_mesh_vertex_normals", ptr(pos), ptr(topo.faces), ptr(topo.corner_start), ptr(topo.corner_list), V, F,
+                   ptr(face_normals), ptr(n), ptr(length))
         ctx.save_for_backward(pos, n, length)
         ctx.topo = topo
         return n
@@ -141,8 +130,8 @@ class _VertexNormals(torch.autograd.Function):
         topo = ctx.topo
         g = g.contiguous().float()
         g_s, g_pos = torch.empty_like(pos), torch.empty_like(pos)
-        _call(pos.device, "gip_mesh_vertex_normals_backward", _p(pos), _p(topo.faces), _p(topo.corner_start), _p(topo.corner_list), _p(n),
-              _p(length), _p(g), topo.num_vertices, topo.num_faces, _p(g_s), _p(g_pos))
+        call_model(pos.device, "gip_mesh_vertex_normals_backward", ptr(pos), ptr(topo.faces), ptr(topo.corner_start), ptr(topo.corner_list), ptr(n),
+                   ptr(length), ptr(g), topo.num_vertices, topo.num_faces, ptr(g_s), ptr(g_pos))
         return g_pos, None
 
 
@@ -154,8 +143,8 @@ class _Laplacian(torch.autograd.Function):
         unit = torch.empty_like(pos)
         loss = torch.empty((), dtype=torch.float32, device=pos.device)
         ws, need = _workspace(V, pos.device)
-        _call(pos.device, "gip_mesh_laplacian_loss", _p(pos), _p(topo.nbr_start), _p(topo.nbr_list), V, topo.num_neighbours, _p(unit),
-              _p(loss), _p(ws), need)
+        call_model(pos.device, "gip_mesh_laplacian_loss", ptr(pos), ptr(topo.nbr_start), ptr(topo.nbr_list), V, topo.num_neighbours, ptr(unit),
+                   ptr(loss), ptr(ws), need)
         ctx.save_for_backward(unit)
         ctx.topo = topo
         return loss
@@ -167,8 +156,8 @@ class _Laplacian(torch.autograd.Function):
         topo = ctx.topo
         g = g.contiguous().float()
         g_pos = torch.empty_like(unit)
-        _call(unit.device, "gip_mesh_laplacian_loss_backward", _p(unit), _p(topo.nbr_start), _p(topo.nbr_list), _p(g), topo.num_vertices,
-              topo.num_neighbours, _p(g_pos))
+        call_model(unit.device, "gip_mesh_laplacian_loss_backward", ptr(unit), ptr(topo.nbr_start), ptr(topo.nbr_list), ptr(g), topo.num_vertices,
+                   topo.num_neighbours, ptr(g_pos))
         return g_pos, None
 
 
@@ -179,8 +168,8 @@ class _Consistency(torch.autograd.Function):
         V = topo.num_vertices
         loss = torch.empty((), dtype=torch.float32, device=n.device)
         ws, need = _workspace(V, n.device)
-        _call(n.device, "gip_mesh_normal_consistency", _p(n), _p(topo.nbr_start), _p(topo.nbr_list), V, topo.num_neighbours, topo.num_edges,
-              _p(loss), _p(ws), need)
+        call_model(n.device, "gip_mesh_normal_consistency", ptr(n), ptr(topo.nbr_start), ptr(topo.nbr_list), V, topo.num_neighbours, topo.num_edges,
+                   ptr(loss), ptr(ws), need)
         ctx.save_for_backward(n)
         ctx.topo = topo
         return loss
@@ -192,8 +181,8 @@ class _Consistency(torch.autograd.Function):
         topo = ctx.topo
         g = g.contiguous().float()
         g_n = torch.empty_like(n)
-        _call(n.device, "gip_mesh_normal_consistency_backward", _p(n), _p(topo.nbr_start), _p(topo.nbr_list), _p(g), topo.num_vertices,
-              topo.num_neighbours, topo.num_edges, _p(g_n))
+        call_model(n.device, "gip_mesh_normal_consistency_backward", ptr(n), ptr(topo.nbr_start), ptr(topo.nbr_list), ptr(g), topo.num_vertices,
+                   topo.num_neighbours, topo.num_edges, ptr(g_n))
         return g_n, None
 
 
@@ -206,7 +195,7 @@ def vertex_normals(vertices, topology):
     """n [V, 3]: the area-weighted vertex normals of the reference's Mesh.v_nrm.  The face cross products cross(p1 - p0, p2 - p0) are
     summed over a vertex's corners and normalised; a vertex whose sum has a squared length of at most 1e-20 (an isolated one, say) gets
     (0, 0, 1) and sends no gradient.  Differentiable in vertices, bit-reproducible in both directions."""
-    _args("vertex_normals", vertices, topology)
+    check_topology("vertex_normals", vertices, topology)
     if topology.num_faces == 0 or topology.num_vertices == 0:      # no face: every normal is the default; no launch
         default = torch.tensor([0.0, 0.0, 1.0], dtype=torch.float32, device=vertices.device)
         return default.expand(topology.num_vertices, 3) + vertices * 0.0
@@ -216,7 +205,7 @@ def vertex_normals(vertices, topology):
 def laplacian_loss(vertices, topology):
     """The scalar of the reference's Mesh.laplacian(): the mean over all vertices of |deg_v p_v - sum of v's neighbours| (the uniform
     Laplacian; an isolated vertex adds 0).  Differentiable in vertices, bit-reproducible in both directions."""
-    _args("laplacian_loss", vertices, topology)
+    check_topology("laplacian_loss", vertices, topology)
     if topology.num_faces == 0 or topology.num_vertices == 0:
         return _zero_of(vertices)
     return _Laplacian.apply(vertices, topology)
@@ -231,7 +220,7 @@ def _consistency_of(normals, topology):
 def normal_consistency(vertices, topology):
     """The scalar of the reference's Mesh.normal_consistency(): the mean over topology.edges of 1 - cos(n_a, n_b) of vertex_normals.
     Differentiable in vertices, bit-reproducible in both directions."""
-    _args("normal_consistency", vertices, topology)
+    check_topology("normal_consistency", vertices, topology)
     return _consistency_of(vertex_normals(vertices, topology), topology)
 
 
@@ -283,7 +272,7 @@ class Mesh:
         self._v_rgb = v_rgb
 
     def normal_consistency(self):
-        _args("normal_consistency", self.v_pos, self.topology)
+        check_topology("normal_consistency", self.v_pos, self.topology)
         return _consistency_of(self.v_nrm, self.topology)
 
     def laplacian(self):

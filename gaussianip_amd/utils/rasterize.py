@@ -28,27 +28,13 @@ import ctypes
 import torch
 
 from .. import _lib
+from .._lib import call_model, ptr
 
 __all__ = ["MeshRasterizerContext", "DiffMeshRasterizerContext", "MipMeshRasterizerContext", "MipStack", "edge_topology", "render_mesh"]
 
 
 _MAX_SIDE = 16384             # of an image or a texture: the library's MR_MAX_SIZE
 _INT32_MAX = 2 ** 31 - 1      # the most pixels, or values of one tensor, the library indexes
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr() if t is not None and t.numel() else None)
-
-
-def _check(rc, name):
-    if rc != 0:
-        raise RuntimeError("%s failed with status %d" % (name, rc))
-
-
-def _call(dev, name, *args):
-    """The library's entry point `name` with args and, as its last argument, dev's current stream; RuntimeError unless it returns 0."""
-    with torch.cuda.device(dev):
-        _check(getattr(_lib.model_lib(), name)(*args, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), name)
 
 
 def _is_gpu_float(t):
@@ -126,7 +112,7 @@ def _rasterize_launch(pos, tri, H, W, cull_backfaces):
     need = _workspace_bytes(B, H, W, F)
     ws = torch.empty(need, dtype=torch.uint8, device=pos.device)
     rast = torch.empty((B, H, W, 4), dtype=torch.float32, device=pos.device)
-    _call(pos.device, "gip_mesh_rasterize", _p(pos), _p(tri), B, V, F, H, W, int(bool(cull_backfaces)), _p(ws), need, _p(rast))
+    call_model(pos.device, "gip_mesh_rasterize", ptr(pos), ptr(tri), B, V, F, H, W, int(bool(cull_backfaces)), ptr(ws), need, ptr(rast))
     return rast
 
 
@@ -147,7 +133,7 @@ class _RasterizeGrad(torch.autograd.Function):
         V, F = int(pos.shape[1]), int(tri.shape[0])
         g = g.contiguous().float()
         g_pos = torch.zeros_like(pos)
-        _call(pos.device, "gip_mesh_rasterize_backward", _p(pos), _p(tri), B, V, F, H, W, _p(rast), _p(g), _p(g_pos))
+        call_model(pos.device, "gip_mesh_rasterize_backward", ptr(pos), ptr(tri), B, V, F, H, W, ptr(rast), ptr(g), ptr(g_pos))
         return g_pos, None, None, None, None
 
 
@@ -161,7 +147,7 @@ class _Interpolate(torch.autograd.Function):
         B, H, W, _ = rast.shape
         nb, N, C = attr.shape
         out = torch.empty((B, H, W, C), dtype=torch.float32, device=rast.device)
-        _call(rast.device, "gip_mesh_interpolate", _p(attr), nb, N, C, _p(idx), F, _p(rast), B, H, W, _p(out))
+        call_model(rast.device, "gip_mesh_interpolate", ptr(attr), nb, N, C, ptr(idx), F, ptr(rast), B, H, W, ptr(out))
         ctx.save_for_backward(rast, idx, attr)
         ctx.shape, ctx.F = (nb, N, C), F
         return out
@@ -175,10 +161,11 @@ class _Interpolate(torch.autograd.Function):
         g_attr = g_rast = None
         if ctx.needs_input_grad[0]:
             g_attr = torch.empty((nb, N, C), dtype=torch.float32, device=rast.device)
-            _call(rast.device, "gip_mesh_interpolate_backward", _p(g), nb, N, C, _p(idx), ctx.F, _p(rast), B, H, W, _p(g_attr))
+            call_model(rast.device, "gip_mesh_interpolate_backward", ptr(g), nb, N, C, ptr(idx), ctx.F, ptr(rast), B, H, W, ptr(g_attr))
         if ctx.needs_input_grad[1]:      # only a rast of DiffMeshRasterizerContext carries a gradient
             g_rast = torch.empty_like(rast)
-            _call(rast.device, "gip_mesh_interpolate_backward_rast", _p(g), _p(attr), nb, N, C, _p(idx), ctx.F, _p(rast), B, H, W, _p(g_rast))
+            call_model(rast.device, "gip_mesh_interpolate_backward_rast", ptr(g), ptr(attr), nb, N, C, ptr(idx), ctx.F, ptr(rast), B, H, W,
+                       ptr(g_rast))
         return g_attr, g_rast, None, None
 
 
@@ -188,7 +175,7 @@ class _Texture(torch.autograd.Function):
         nb, Th, Tw, C = tex.shape
         B, H, W, _ = uv.shape
         out = torch.empty((B, H, W, C), dtype=torch.float32, device=uv.device)
-        _call(uv.device, "gip_mesh_texture", _p(tex), nb, Th, Tw, C, _p(uv), B, H, W, _p(out))
+        call_model(uv.device, "gip_mesh_texture", ptr(tex), nb, Th, Tw, C, ptr(uv), B, H, W, ptr(out))
         ctx.save_for_backward(tex, uv)
         return out
 
@@ -200,7 +187,7 @@ class _Texture(torch.autograd.Function):
         g = g.contiguous().float()
         g_tex = torch.empty_like(tex) if ctx.needs_input_grad[0] else None
         g_uv = torch.empty_like(uv) if ctx.needs_input_grad[1] else None
-        _call(uv.device, "gip_mesh_texture_backward", _p(tex), nb, Th, Tw, C, _p(uv), _p(g), B, H, W, _p(g_tex), _p(g_uv))
+        call_model(uv.device, "gip_mesh_texture_backward", ptr(tex), nb, Th, Tw, C, ptr(uv), ptr(g), B, H, W, ptr(g_tex), ptr(g_uv))
         return g_tex, g_uv
 
 
@@ -213,7 +200,7 @@ class _Shade(torch.autograd.Function):
         B, H, W, _ = rast.shape
         F = int(uv.shape[0])
         shaded = torch.empty((B, H, W, 4), dtype=torch.float32, device=rast.device)
-        _call(rast.device, "gip_mesh_shade", _p(rast), _p(uv), F, int(flip_v), _p(tex), Th, Tw, _p(bg), B, H, W, _p(shaded))
+        call_model(rast.device, "gip_mesh_shade", ptr(rast), ptr(uv), F, int(flip_v), ptr(tex), Th, Tw, ptr(bg), B, H, W, ptr(shaded))
         ctx.save_for_backward(tex, uv, rast)
         ctx.flip_v = int(flip_v)
         return shaded
@@ -232,9 +219,10 @@ class _Shade(torch.autograd.Function):
             return ((None if g_tex is None else torch.zeros_like(tex)), (None if g_uv is None else torch.zeros_like(uv)),
                     (None if g_rast is None else torch.zeros_like(rast)), None, None)
         if g_tex is not None or g_uv is not None:
-            _call(rast.device, "gip_mesh_shade_backward", _p(rast), _p(uv), F, ctx.flip_v, _p(tex), Th, Tw, _p(g), B, H, W, _p(g_tex), _p(g_uv))
+            call_model(rast.device, "gip_mesh_shade_backward", ptr(rast), ptr(uv), F, ctx.flip_v, ptr(tex), Th, Tw, ptr(g), B, H, W, ptr(g_tex),
+                       ptr(g_uv))
         if g_rast is not None:
-            _call(rast.device, "gip_mesh_shade_backward_rast", _p(rast), _p(uv), F, ctx.flip_v, _p(tex), Th, Tw, _p(g), B, H, W, _p(g_rast))
+            call_model(rast.device, "gip_mesh_shade_backward_rast", ptr(rast), ptr(uv), F, ctx.flip_v, ptr(tex), Th, Tw, ptr(g), B, H, W, ptr(g_rast))
         return g_tex, g_uv, g_rast, None, None
 
 
@@ -284,7 +272,7 @@ class _Antialias(torch.autograd.Function):
         V, F = int(pos.shape[1]), int(tri.shape[0])
         color, pos = color.detach().contiguous(), pos.detach().contiguous()
         out = torch.empty_like(color)
-        _call(color.device, "gip_mesh_antialias", _p(color), C, _p(rast), _p(pos), _p(tri), _p(topo), B, V, F, H, W, _p(out))
+        call_model(color.device, "gip_mesh_antialias", ptr(color), C, ptr(rast), ptr(pos), ptr(tri), ptr(topo), B, V, F, H, W, ptr(out))
         ctx.save_for_backward(color, pos, rast, tri, topo)
         return out
 
@@ -296,8 +284,8 @@ class _Antialias(torch.autograd.Function):
         g = g.contiguous().float()
         g_color = torch.empty_like(color) if ctx.needs_input_grad[0] else None
         g_pos = torch.zeros_like(pos) if ctx.needs_input_grad[1] else None
-        _call(color.device, "gip_mesh_antialias_backward", _p(color), C, _p(rast), _p(pos), _p(tri), _p(topo), B, V, F, H, W, _p(g), _p(g_color),
-              _p(g_pos))
+        call_model(color.device, "gip_mesh_antialias_backward", ptr(color), C, ptr(rast), ptr(pos), ptr(tri), ptr(topo), B, V, F, H, W, ptr(g),
+                   ptr(g_color), ptr(g_pos))
         return g_color, g_pos, None, None, None
 
 
@@ -456,7 +444,7 @@ def _rast_db_launch(pos, tri, rast):
     B, H, W, _ = rast.shape
     V, F = int(pos.shape[1]), int(tri.shape[0])
     rast_db = torch.empty_like(rast)
-    _call(rast.device, "gip_mesh_rast_db", _p(pos), _p(tri), B, V, F, H, W, _p(rast), _p(rast_db))
+    call_model(rast.device, "gip_mesh_rast_db", ptr(pos), ptr(tri), B, V, F, H, W, ptr(rast), ptr(rast_db))
     return rast_db
 
 
@@ -468,7 +456,8 @@ class _InterpolateDa(torch.autograd.Function):
         B, H, W, _ = rast.shape
         nb, N, C = attr.shape
         out = torch.empty((B, H, W, 2 * K), dtype=torch.float32, device=rast.device)
-        _call(rast.device, "gip_mesh_interpolate_da", _p(attr), nb, N, C, _p(idx), F, _p(rast), _p(rast_db), _p(channels), K, B, H, W, _p(out))
+        call_model(rast.device, "gip_mesh_interpolate_da", ptr(attr), nb, N, C, ptr(idx), F, ptr(rast), ptr(rast_db), ptr(channels), K, B, H, W,
+                   ptr(out))
         ctx.save_for_backward(rast, rast_db, idx, channels)
         ctx.shape, ctx.K, ctx.F = (nb, N, C), K, F
         return out
@@ -480,8 +469,8 @@ class _InterpolateDa(torch.autograd.Function):
         B, H, W, _ = rast.shape
         g = g.contiguous().float()
         g_attr = torch.empty((nb, N, C), dtype=torch.float32, device=rast.device)
-        _call(rast.device, "gip_mesh_interpolate_da_backward", _p(g), nb, N, C, _p(idx), ctx.F, _p(rast), _p(rast_db), _p(channels), ctx.K, B, H,
-              W, _p(g_attr))
+        call_model(rast.device, "gip_mesh_interpolate_da_backward", ptr(g), nb, N, C, ptr(idx), ctx.F, ptr(rast), ptr(rast_db), ptr(channels), ctx.K,
+                   B, H, W, ptr(g_attr))
         return g_attr, None, None, None, None, None, None
 
 
@@ -494,7 +483,9 @@ def _mip_levels(Th, Tw, max_mip_level):
         if cap < 0:
             raise ValueError("max_mip_level must be None or >= 0")
     L, texels = ctypes.c_int32(0), ctypes.c_int64(0)
-    _check(_lib.model_lib().gip_mesh_mip_levels(Th, Tw, cap, ctypes.byref(L), ctypes.byref(texels)), "gip_mesh_mip_levels")
+    rc = _lib.model_lib().gip_mesh_mip_levels(Th, Tw, cap, ctypes.byref(L), ctypes.byref(texels))      # no launch: it takes no stream
+    if rc != 0:
+        raise RuntimeError("gip_mesh_mip_levels failed with status %d" % rc)
     return cap, int(L.value), int(texels.value)
 
 
@@ -521,7 +512,7 @@ def _construct_mip(t, max_mip_level):
     cap, L, texels = _mip_levels(Th, Tw, max_mip_level)
     buffer = torch.empty((nb, texels, C), dtype=torch.float32, device=t.device)
     if L:
-        _call(t.device, "gip_mesh_mip_build", _p(t), nb, Th, Tw, C, cap, _p(buffer), texels)
+        call_model(t.device, "gip_mesh_mip_build", ptr(t), nb, Th, Tw, C, cap, ptr(buffer), texels)
     return MipStack((nb, Th, Tw, C), cap, L, texels, buffer)
 
 
@@ -533,8 +524,8 @@ class _TextureMip(torch.autograd.Function):
         nb, Th, Tw, C = tex.shape
         B, H, W, _ = uv.shape
         out = torch.empty((B, H, W, C), dtype=torch.float32, device=uv.device)
-        _call(uv.device, "gip_mesh_texture_mip", _p(tex), nb, Th, Tw, C, _p(stack.buffer), stack.texels, stack.max_level, _p(uv), _p(uv_da),
-              _p(bias), int(nearest), B, H, W, _p(out))
+        call_model(uv.device, "gip_mesh_texture_mip", ptr(tex), nb, Th, Tw, C, ptr(stack.buffer), stack.texels, stack.max_level, ptr(uv), ptr(uv_da),
+                   ptr(bias), int(nearest), B, H, W, ptr(out))
         ctx.save_for_backward(tex, uv, uv_da, bias)
         ctx.stack, ctx.nearest = stack, int(nearest)
         return out
@@ -551,10 +542,10 @@ class _TextureMip(torch.autograd.Function):
         g_uv = torch.empty_like(uv) if ctx.needs_input_grad[1] else None
         g_da = torch.empty_like(uv_da) if uv_da is not None and ctx.needs_input_grad[2] else None
         g_bias = torch.empty_like(bias) if bias is not None and ctx.needs_input_grad[3] else None
-        _call(uv.device, "gip_mesh_texture_mip_backward", _p(tex), nb, Th, Tw, C, _p(stack.buffer), stack.texels, stack.max_level, _p(uv),
-              _p(uv_da), _p(bias), ctx.nearest, _p(g), B, H, W, _p(g_tex), _p(g_mip), _p(g_uv), _p(g_da), _p(g_bias))
+        call_model(uv.device, "gip_mesh_texture_mip_backward", ptr(tex), nb, Th, Tw, C, ptr(stack.buffer), stack.texels, stack.max_level, ptr(uv),
+                   ptr(uv_da), ptr(bias), ctx.nearest, ptr(g), B, H, W, ptr(g_tex), ptr(g_mip), ptr(g_uv), ptr(g_da), ptr(g_bias))
         if g_mip is not None:
-            _call(uv.device, "gip_mesh_mip_fold", _p(g_tex), nb, Th, Tw, C, stack.max_level, _p(g_mip), stack.texels)
+            call_model(uv.device, "gip_mesh_mip_fold", ptr(g_tex), nb, Th, Tw, C, stack.max_level, ptr(g_mip), stack.texels)
         return g_tex, g_uv, g_da, g_bias, None, None
 
 

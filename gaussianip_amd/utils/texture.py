@@ -153,9 +153,7 @@ def project_views(vertices, faces, texture_size, cameras, images, vis_depth, *, 
     colour = color_sum / weight_sum where count > 0.  Unowned texels stay 0.  One host read (the faces' index range) and exactly one
     call of gip_texture_project.  ValueError for K outside 1 .. 64, tensors of the wrong dtype, device or shape, cameras of different
     sizes, faces that do not fit the texture or index outside [0, V)."""
-    import ctypes
-
-    from .. import _lib
+    from .._lib import call_model, ptr
     cams, K, H, W = _view_size("project_views", cameras)
     min_alpha, min_cos, depth_tolerance = float(min_alpha), float(min_cos), float(depth_tolerance)
     if unpremultiply and not min_alpha > 0:
@@ -185,13 +183,9 @@ def project_views(vertices, faces, texture_size, cameras, images, vis_depth, *, 
         raise ValueError("project_views: face indices must lie in [0, %d)" % V)
     packed = torch.cat((images, alphas), 1).permute(0, 2, 3, 1).contiguous()      # [K, H, W, 4]: a bilinear tap is one 16-byte load
     table = pack_views(cams, dev)
-    p = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
-    with torch.cuda.device(dev):
-        rc = _lib.model_lib().gip_texture_project(p(vertices), V, p(faces), F, T, c, K, p(table), p(packed), p(vis_depth), H, W, depth_tolerance,
-                                                  min_cos, min_alpha, int(bool(two_sided)), int(bool(unpremultiply)), p(out["color_sum"]),
-                                                  p(out["weight_sum"]), p(out["count"]), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    if rc != 0:
-        raise RuntimeError("gip_texture_project failed with status %d" % rc)
+    call_model(dev, "gip_texture_project", ptr(vertices), V, ptr(faces), F, T, c, K, ptr(table), ptr(packed), ptr(vis_depth), H, W, depth_tolerance,
+               min_cos, min_alpha, int(bool(two_sided)), int(bool(unpremultiply)), ptr(out["color_sum"]), ptr(out["weight_sum"]),
+               ptr(out["count"]))
     return out
 
 

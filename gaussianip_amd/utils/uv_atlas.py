@@ -20,7 +20,9 @@ import numpy as np
 import torch
 from torch.autograd.function import once_differentiable
 
-from .mesh_geometry import Mesh, _args, _call, _p
+from .._lib import call_model, ptr
+from .mesh import settle_labels
+from .mesh_geometry import Mesh, check_topology
 
 __all__ = ["face_adjacency", "chart_sizes", "pack_charts", "search_scale", "unwrap_charts", "ChartAtlas", "vertex_tangents",
            "dilate_texture", "UVMesh"]
@@ -110,7 +112,7 @@ def search_scale(box, area, size, pad):
 
 
 def _decode_keys(keys):
-    """float32 of the order-preserving uint32 keys of csrc/mesh_uv.hip."""
+    """float32 of the order-preserving uint32 keys: mesh_key_float of csrc/mesh_common.h, the one definition, restated for the host."""
     k = np.ascontiguousarray(keys).view(np.uint32)
     return np.where(k & np.uint32(0x80000000), k & np.uint32(0x7FFFFFFF), ~k).astype(np.uint32).view(np.float32)
 
@@ -203,19 +205,15 @@ def unwrap_charts(vertices, faces, texture_size=None, *, smooth_rounds=DEFAULT_S
     normals = torch.empty((F, 3), dtype=torch.float32, device=dev)
     smooth = torch.empty((2, F, 3), dtype=torch.float32, device=dev) if smooth_rounds else None
     face_class = torch.empty(F, **i32)
-    _call(dev, "gip_uv_face_classes", _p(vertices), _p(faces), _p(face_nbr), V, F, smooth_rounds, min_cos, _p(normals),
-          _p(smooth[0] if smooth_rounds else None), _p(smooth[1] if smooth_rounds else None), _p(face_class))
+    call_model(dev, "gip_uv_face_classes", ptr(vertices), ptr(faces), ptr(face_nbr), V, F, smooth_rounds, min_cos, ptr(normals),
+               ptr(smooth[0] if smooth_rounds else None), ptr(smooth[1] if smooth_rounds else None), ptr(face_class))
     labels = torch.arange(F, **i32)
     changed = torch.zeros(1, **i32)
-    rounds = 0
-    while True:
-        changed.zero_()
-        _call(dev, "gip_uv_chart_rounds", _p(face_nbr), _p(face_class), F, _p(labels), _p(changed), _ROUNDS_BATCH)
-        rounds += _ROUNDS_BATCH
-        if int(changed.item()) == 0:
-            break
-        if rounds > F + 1 + _ROUNDS_BATCH:
-            raise RuntimeError("unwrap_charts: the chart labels did not settle in %d rounds" % rounds)
+
+    def rounds():
+        call_model(dev, "gip_uv_chart_rounds", ptr(face_nbr), ptr(face_class), F, ptr(labels), ptr(changed), _ROUNDS_BATCH)
+        return changed
+    settle_labels(rounds, F, _ROUNDS_BATCH, "unwrap_charts: the chart labels")
     roots, face_chart = torch.unique(labels.long(), return_inverse=True)          # sorted: a chart's id is the rank of its smallest face
     C = int(roots.shape[0])
     chart_class = face_class[roots].contiguous()
@@ -223,7 +221,7 @@ def unwrap_charts(vertices, faces, texture_size=None, *, smooth_rounds=DEFAULT_S
     keys = torch.empty((C, 4), **i32)
     keys[:, :2] = -1                                                               # 0xffffffff
     keys[:, 2:] = 0
-    _call(dev, "gip_uv_chart_boxes", _p(vertices), _p(faces), _p(face_chart32), _p(chart_class), V, F, C, _p(keys))
+    call_model(dev, "gip_uv_chart_boxes", ptr(vertices), ptr(faces), ptr(face_chart32), ptr(chart_class), V, F, C, ptr(keys))
     axis = (chart_class[face_chart].long() >> 1).unsqueeze(1)
     area = math.fsum((normals.gather(1, axis).abs().reshape(-1) * 0.5).cpu().tolist())      # exactly rounded: order-independent
     box = _decode_keys(keys.cpu().numpy())
@@ -252,7 +250,7 @@ def unwrap_charts(vertices, faces, texture_size=None, *, smooth_rounds=DEFAULT_S
     origin = np.stack((box[:, 0], box[:, 1], (rect[:, 0] + pad).astype(np.float32), (rect[:, 1] + pad).astype(np.float32)), 1)
     origin = torch.from_numpy(np.ascontiguousarray(origin, np.float32)).to(dev)
     v_tex = torch.empty((Vt, 2), dtype=torch.float32, device=dev)
-    _call(dev, "gip_uv_place", _p(vertices), _p(vmapping), _p(vt_chart), _p(chart_class), _p(origin), V, Vt, C, float(scale), T, _p(v_tex))
+    call_model(dev, "gip_uv_place", ptr(vertices), ptr(vmapping), ptr(vt_chart), ptr(chart_class), ptr(origin), V, Vt, C, float(scale), T, ptr(v_tex))
     return ChartAtlas(v_tex=v_tex, t_tex_idx=t_tex_idx.reshape(F, 3).to(torch.int32).contiguous(), vmapping=vmapping,
                       face_chart=face_chart32, chart_class=chart_class, face_nbr=face_nbr, faces=faces, chart_rect=rect, chart_box=box,
                       scale=float(scale), texture_size=T, pad=pad, num_charts=C)
@@ -266,8 +264,8 @@ class _VertexTangents(torch.autograd.Function):
         V, F, Vt = topo.num_vertices, topo.num_faces, int(v_tex.shape[0])
         face_tangents = torch.empty((F, 3), dtype=torch.float32, device=pos.device)
         out = torch.empty((V, 3), dtype=torch.float32, device=pos.device)
-        _call(pos.device, "gip_uv_vertex_tangents", _p(pos), _p(topo.faces), _p(topo.corner_start), _p(topo.corner_list), _p(t_tex_idx),
-              _p(v_tex), _p(nrm), V, F, Vt, _p(face_tangents), _p(out))
+        call_model(pos.device, "gip_uv_vertex_tangents", ptr(pos), ptr(topo.faces), ptr(topo.corner_start), ptr(topo.corner_list), ptr(t_tex_idx),
+                   ptr(v_tex), ptr(nrm), V, F, Vt, ptr(face_tangents), ptr(out))
         ctx.save_for_backward(nrm, face_tangents, v_tex, t_tex_idx)
         ctx.topo = topo
         return out
@@ -281,8 +279,8 @@ class _VertexTangents(torch.autograd.Function):
         g = g.contiguous().float()
         g_sum, g_pos, g_nrm = torch.empty_like(nrm), torch.empty_like(nrm), torch.empty_like(nrm)
         g_edge = torch.empty((F, 6), dtype=torch.float32, device=nrm.device)
-        _call(nrm.device, "gip_uv_vertex_tangents_backward", _p(topo.faces), _p(topo.corner_start), _p(topo.corner_list), _p(t_tex_idx),
-              _p(v_tex), _p(nrm), _p(face_tangents), _p(g), V, F, Vt, _p(g_sum), _p(g_edge), _p(g_pos), _p(g_nrm))
+        call_model(nrm.device, "gip_uv_vertex_tangents_backward", ptr(topo.faces), ptr(topo.corner_start), ptr(topo.corner_list), ptr(t_tex_idx),
+                   ptr(v_tex), ptr(nrm), ptr(face_tangents), ptr(g), V, F, Vt, ptr(g_sum), ptr(g_edge), ptr(g_pos), ptr(g_nrm))
         return g_pos, g_nrm, None, None, None
 
 
@@ -292,7 +290,7 @@ def vertex_tangents(vertices, topology, v_tex, t_tex_idx, v_nrm):
     corners, normalised, made perpendicular to v_nrm [V, 3] and normalised again.  Differentiable in vertices and v_nrm (v_tex
     [Vt, 2] float32 and t_tex_idx [F, 3] int32 are constants), a gather in both directions: no float atomics, bitwise equal from run to
     run.  A vertex that no face names gets (1, 0, 0) and sends no gradient (the reference yields NaN there)."""
-    _args("vertex_tangents", vertices, topology)
+    check_topology("vertex_tangents", vertices, topology)
     dev = vertices.device
     if not (isinstance(v_nrm, torch.Tensor) and v_nrm.is_cuda and v_nrm.dtype == torch.float32 and v_nrm.shape == vertices.shape and
             v_nrm.device == dev):
@@ -328,7 +326,7 @@ def dilate_texture(texture, mask, rounds):
     mask_a = mask.to(torch.uint8).contiguous()
     tex_a = torch.where(mask.unsqueeze(2), texture, torch.zeros_like(texture)).contiguous()
     tex_b, mask_b = torch.empty_like(tex_a), torch.empty_like(mask_a)
-    _call(texture.device, "gip_texture_dilate", _p(tex_a), _p(mask_a), _p(tex_b), _p(mask_b), H, W, C, rounds)
+    call_model(texture.device, "gip_texture_dilate", ptr(tex_a), ptr(mask_a), ptr(tex_b), ptr(mask_b), H, W, C, rounds)
     return (tex_b, mask_b.bool()) if rounds & 1 else (tex_a, mask_a.bool())
 
 

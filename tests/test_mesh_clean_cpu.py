@@ -136,3 +136,35 @@ def test_argument_errors_come_before_the_library():
             mesh._grid_arg("cluster_decimate", grid)
     assert mesh._grid_arg("cluster_decimate", 1) == 1 and mesh._grid_arg("cluster_decimate", 2048) == 2048
     assert dict(_lib.call_counts) == before
+
+
+def test_settle_labels_and_null_pointers():
+    """settle_labels over a fake propagation that needs k + 1 rounds (k that lower a label and the one that confirms) and whose flag stays
+    raised until a call has run them: it returns after ceil((k + 1) / batch) calls and hands every call a zeroed flag.  A flag that never
+    drops raises once the rounds pass limit + 1 + batch, the bound connected_components and unwrap_charts had.  _lib.ptr is null for
+    None and for an empty tensor."""
+    from gaussianip_amd import _lib
+    from gaussianip_amd.utils.mesh import settle_labels
+    limit = 10
+    for batch in (1, 4, 8):
+        for k in (0, 1, 3, 4, 7, 8, 9, 21):
+            flag, seen = torch.zeros(1, dtype=torch.int32), []
+
+            def step():
+                seen.append(int(flag.item()))
+                flag.fill_(1 if len(seen) * batch < k + 1 else 0)
+                return flag
+            assert settle_labels(step, 100, batch, "fake") is None
+            assert len(seen) == -(-(k + 1) // batch) and not any(seen)
+        calls = []
+
+        def stuck():
+            calls.append(None)
+            return torch.ones(1, dtype=torch.int32)
+        rounds = (limit + 1 + batch) // batch * batch + batch                            # the first whole batch past limit + 1 + batch
+        with pytest.raises(RuntimeError, match=r"^fake labels did not settle in %d rounds$" % rounds):
+            settle_labels(stuck, limit, batch, "fake labels")
+        assert len(calls) * batch == rounds and rounds > limit + 1 + batch >= rounds - batch
+    assert _lib.ptr(None).value is None and _lib.ptr(torch.empty(0)).value is None and _lib.ptr(torch.empty((0, 3))).value is None
+    t = torch.zeros(2)
+    assert _lib.ptr(t).value == t.data_ptr()
