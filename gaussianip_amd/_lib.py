@@ -319,6 +319,18 @@ def model_lib():
         lib.gip_uv_vertex_tangents_backward.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp]
         lib.gip_texture_dilate.restype = ctypes.c_int
         lib.gip_texture_dilate.argtypes = [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]
+        lib.gip_tet_workspace_size.restype = ctypes.c_int
+        lib.gip_tet_workspace_size.argtypes = [_i64, ctypes.POINTER(_sz)]
+        lib.gip_tet_mark.restype = ctypes.c_int
+        lib.gip_tet_mark.argtypes = [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp]
+        lib.gip_tet_emit.restype = ctypes.c_int
+        lib.gip_tet_emit.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp]
+        lib.gip_tet_backward.restype = ctypes.c_int
+        lib.gip_tet_backward.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp]
+        lib.gip_tet_sdf_diff.restype = ctypes.c_int
+        lib.gip_tet_sdf_diff.argtypes = [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _sz, _vp]
+        lib.gip_tet_sdf_diff_backward.restype = ctypes.c_int
+        lib.gip_tet_sdf_diff_backward.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp]
         _model = _Counted(lib)
     return _model
 
@@ -494,3 +506,5 @@ MESH_GEOM_SYMBOLS = ["gip_mesh_geometry_workspace_size", "gip_mesh_vertex_normal
                      "gip_mesh_normal_consistency_backward"]
 MESH_UV_SYMBOLS = ["gip_uv_face_classes", "gip_uv_chart_rounds", "gip_uv_chart_boxes", "gip_uv_place", "gip_uv_vertex_tangents",
                    "gip_uv_vertex_tangents_backward", "gip_texture_dilate"]
+MESH_TET_SYMBOLS = ["gip_tet_workspace_size", "gip_tet_mark", "gip_tet_emit", "gip_tet_backward", "gip_tet_sdf_diff",
+                    "gip_tet_sdf_diff_backward"]

@@ -326,6 +326,31 @@ class GaussianModel:
         return {"density": out["density"], "gradient": out["gradient"] * scale, "color": self._blend(out["color_sum"], out["density"])}
 
     @torch.no_grad()
+    def to_tetrahedra_sdf_grid(self, resolution=64, density_thresh=1.0, tets_path=None, **field_kwargs):
+        """A utils.isosurface.TetrahedraSDFGrid that starts from this model's surface density == density_thresh: the bridge from the
+        representation the project trains to a mesh whose vertices AND connectivity can be optimised further.  isosurface_bbox is the
+        box of the normalised cloud, center -/+ 1 / scale; sdf = clamp(density_thresh - density, -1, 1) with the density of
+        sample_fields(**field_kwargs) at the grid's vertices (the clamp is the reference's TetrahedraSDFGrid.create_from of an
+        implicit volume); inside is negative, as in the reference.  resolution and tets_path choose the tetrahedral grid
+        (utils.isosurface.MarchingTetrahedraHelper); the deformation starts at zero.  field_kwargs are sample_fields' num_blocks and
+        relax_ratio, and field_resolution for its resolution (the name `resolution` is the tetrahedral grid's here)."""
+        from ..utils.isosurface import TetrahedraSDFGrid, scale_tensor
+        if "field_resolution" in field_kwargs:
+            field_kwargs["resolution"] = field_kwargs.pop("field_resolution")
+        if set(field_kwargs) - {"resolution", "num_blocks", "relax_ratio"}:
+            raise TypeError("to_tetrahedra_sdf_grid: unknown arguments %s" % sorted(set(field_kwargs) - {"resolution", "num_blocks", "relax_ratio"}))
+        dev = self._xyz.device
+        grid = TetrahedraSDFGrid(isosurface_resolution=resolution, tets_path=tets_path).to(dev)
+        if self._field_sources() is not None:                # sets center / scale; without sources the box stays the unit one
+            half = 1.0 / self.scale
+            grid.isosurface_bbox.copy_(torch.stack((self.center - half, self.center + half)))
+        helper = grid.isosurface_helper
+        points = scale_tensor(helper.grid_vertices, helper.points_range, grid.isosurface_bbox).contiguous()
+        density = self.sample_fields(points, **field_kwargs)["density"]
+        grid.sdf.data = (float(density_thresh) - density).clamp(-1, 1).reshape(-1, 1)
+        return grid
+
+    @torch.no_grad()
     def extract_mesh_with_attributes(self, path=None, density_thresh=1.0, resolution=128, num_blocks=16, relax_ratio=1.5, colors=None, *,
                                      clean=False, min_faces=8, min_diameter=0.05, decimate_target=0):
         """(vertices [V, 3] float32, faces [F, 3] int32, normals [V, 3] float32, colors [V, 3] float32 in [0, 1]): extract_mesh's

@@ -414,6 +414,31 @@ int gip_uv_vertex_tangents_backward(const int32_t* faces, const int32_t* corner_
                                     int64_t F, int64_t Vt, float* g_sum, float* g_edge, float* g_pos, float* g_nrm, void* stream);
 int gip_texture_dilate(float* tex_a, uint8_t* mask_a, float* tex_b, uint8_t* mask_b, int32_t H, int32_t W, int32_t C, int32_t rounds,
                        void* stream);
+/* Differentiable marching tetrahedra over a tetrahedral grid and the tet_sdf_diff regulariser (csrc/mesh_tets.hip, whose header states
+ * the definitions; gaussianip_amd/utils/isosurface.py TetGrid, marching_tetrahedra, tet_sdf_diff).  sdf [Nv] and pos [Nv, 3] float32;
+ * the grid's tables, built once: edges [Ne, 2] (a < b, lexicographic), tets [Ft, 4], tet_edge_ids [Ft, 6], vert_edge_start [Nv + 1] and
+ * vert_edge_list [2 Ne] (entries 2 e + end, ascending per vertex), all int32; everything on the device.
+ *   gip_tet_mark  flags [Ne + 2 Ft] int32: per edge whether it crosses, per tetrahedron whether it emits one triangle, and whether two.
+ *   gip_tet_emit  with `scan`, the caller's inclusive int32 scan of all of `flags`, and the three totals read from it (V vertices, F1
+ *       one-triangle and F2 two-triangle tetrahedra): v_pos [V, 3], faces [F1 + 2 F2, 3] int32 and edge_vid [Ne] int32 (-1: no crossing).
+ *   gip_tet_backward  g_sdf [Nv] and, unless g_pos is NULL, g_pos [Nv, 3] from g_v [V, 3]: a gather per grid vertex, no atomics.
+ *   gip_tet_sdf_diff  *loss (device) and *count (device, the number of edges whose ends differ in sign; loss 0 when it is 0);
+ *       workspace of gip_tet_workspace_size(Ne) bytes.  gip_tet_sdf_diff_backward reads count and the upstream gradient g_loss from the
+ *       device and writes g_sdf [Nv].
+ * Status 1: a NULL required pointer, Nv above 2^31 - 1, 2 Ne, 6 Ft or Ne + 2 Ft above 2^31 - 1, totals that do not fit the grid, a short
+ * workspace; a call that fails so launches nothing.  Nothing to do (no edge, no grid vertex) is a success that launches nothing.
+ * Status 3: a launch error. */
+int gip_tet_workspace_size(int64_t Ne, size_t* bytes);
+int gip_tet_mark(const float* sdf, const int32_t* edges, const int32_t* tets, int64_t Nv, int64_t Ne, int64_t Ft, int32_t* flags, void* stream);
+int gip_tet_emit(const float* pos, const float* sdf, const int32_t* edges, const int32_t* tets, const int32_t* tet_edge_ids,
+                 const int32_t* flags, const int32_t* scan, int64_t Nv, int64_t Ne, int64_t Ft, int64_t V, int64_t F1, int64_t F2, float* v_pos,
+                 int32_t* faces, int32_t* edge_vid, void* stream);
+int gip_tet_backward(const float* pos, const float* sdf, const int32_t* edges, const int32_t* vert_edge_start, const int32_t* vert_edge_list,
+                     const int32_t* edge_vid, const float* g_v, int64_t Nv, int64_t Ne, int64_t V, float* g_pos, float* g_sdf, void* stream);
+int gip_tet_sdf_diff(const float* sdf, const int32_t* edges, int64_t Nv, int64_t Ne, float* loss, int32_t* count, void* workspace,
+                     size_t workspace_bytes, void* stream);
+int gip_tet_sdf_diff_backward(const float* sdf, const int32_t* edges, const int32_t* vert_edge_start, const int32_t* vert_edge_list,
+                              const int32_t* count, const float* g_loss, int64_t Nv, int64_t Ne, float* g_sdf, void* stream);
 #ifdef __cplusplus
 }
 #endif

@@ -813,8 +813,80 @@ def uv_tangents():
     print("uv tangent fixtures written: %d bytes" % os.path.getsize(os.path.join(OUT, "uv_tangents.npz")))
 
 
+def isosurface():
+    """threestudio/models/isosurface.py (MarchingTetrahedraHelper: all_edges, normalize_grid_deformation, _forward) and
+    threestudio/utils/ops.py tet_sdf_diff on the three seeded cases of tests/isosurface_inputs.py, on the reference's 32-grid, on the
+    CPU, once in float32 and once in float64.  Both files are loaded by path with the permissive stubs above (threestudio.models.mesh
+    is one of them: _forward is called directly and no Mesh is built).  Stored: all_edges (once: it is the grid's), and per case `c`
+    the inputs c_sdf and c_def (which tests/isosurface_inputs.py must reproduce bit for bit) and c_w, the faces c_faces (identical in
+    both precisions), the float64 values c_v_pos, c_g_sdf and c_g_def (with a deformation) or c_g_pos (without: the gradient to the
+    grid's positions) of sum w . v_pos, c_tsd and c_g_tsd (tet_sdf_diff and its gradient), and per quantity q the reference's own
+    float32 error c_err_q = max |float32 - float64|.  Outputs only.  (tet_sdf_diff makes its targets with .float(); torch computes a
+    loss with a float32 target in float32 whatever the logits are, so for the float64 run Tensor.float is .double().)"""
+    _install_threestudio_stubs()
+    for n in ("igl", "threestudio.models.mesh"):
+        sys.modules.setdefault(n, _Stub(n))
+    sys.path.insert(0, os.path.dirname(OUT))
+    import isosurface_inputs as inputs
+    iso = _load_by_path("threestudio.models.isosurface", "threestudio/models/isosurface.py", "threestudio.models")
+    ops_mod = _load_by_path("threestudio.utils.ops_by_path", "threestudio/utils/ops.py", "threestudio.utils")
+    helper = iso.MarchingTetrahedraHelper(inputs.RESOLUTION, inputs.TETS)
+    edges = helper.all_edges
+    _, indices = inputs.grid()
+
+    def run(sdf, deformation, dtype):
+        out = {}
+        s = torch.from_numpy(sdf).to(dtype).requires_grad_(True)
+        pos = helper.grid_vertices.to(dtype).requires_grad_(True)
+        if deformation is not None:
+            leaf = torch.from_numpy(deformation).to(dtype).requires_grad_(True)
+            grid_vertices = pos + helper.normalize_grid_deformation(leaf)
+        else:
+            leaf, grid_vertices = pos, pos
+        v_pos, faces = helper._forward(grid_vertices, s, helper.indices)
+        w = torch.from_numpy(inputs.weights(name, v_pos.shape[0])).to(dtype)
+        g_sdf, g_leaf = torch.autograd.grad((w * v_pos).sum(), (s, leaf))
+        out["v_pos"], out["faces"], out["g_sdf"] = v_pos.detach(), faces, g_sdf
+        out["g_def" if deformation is not None else "g_pos"] = g_leaf
+        s = torch.from_numpy(sdf).to(dtype).requires_grad_(True)
+        to_float = torch.Tensor.float
+        if dtype == torch.float64:             # tet_sdf_diff builds its targets with .float(), and a float32 target makes the whole
+            torch.Tensor.float = lambda t, *a, **k: t.double()      # loss float32: in the float64 run .float() means the run's dtype
+        try:
+            val = ops_mod.tet_sdf_diff(s, edges)
+        finally:
+            torch.Tensor.float = to_float
+        out["tsd"] = val.detach()
+        out["g_tsd"], = torch.autograd.grad(val, s)
+        return out
+
+    data, lines = {"all_edges": edges.numpy().astype(np.int32)}, []
+    for name in inputs.CASES:
+        sdf, deformation = inputs.case(name)
+        hist = inputs.case_histogram(sdf, indices)
+        r32, r64 = run(sdf, deformation, torch.float32), run(sdf, deformation, torch.float64)
+        assert torch.equal(r32["faces"], r64["faces"]) and r32["v_pos"].shape == r64["v_pos"].shape
+        data[name + "_sdf"] = sdf
+        if deformation is not None:
+            data[name + "_def"] = deformation
+        data[name + "_w"] = inputs.weights(name, r64["v_pos"].shape[0])
+        data[name + "_faces"] = r64["faces"].numpy().astype(np.int32)
+        lines.append("case %s: V %d, F %d, tetrahedra per case %s" % (name, r64["v_pos"].shape[0], r64["faces"].shape[0], hist.tolist()))
+        for q in inputs.QUANTITIES[name]:
+            assert r64[q].dtype == torch.float64 and bool(torch.isfinite(r64[q]).all()) and bool(torch.isfinite(r32[q]).all()), (name, q)
+            data["%s_%s" % (name, q)] = r64[q].numpy()
+            err = float((r32[q].double() - r64[q]).abs().max())
+            data["%s_err_%s" % (name, q)] = np.float64(err)
+            lines.append("case %-6s %-5s float32 error %.3e on a maximum of %.3e" % (name, q, err, float(r64[q].abs().max())))
+    np.savez_compressed(os.path.join(OUT, "isosurface.npz"), **data)
+    print("\n".join(lines))
+    print("isosurface fixtures written: %d bytes, %d edges" % (os.path.getsize(os.path.join(OUT, "isosurface.npz")), edges.shape[0]))
+
+
 if __name__ == "__main__":
-    if len(sys.argv) > 1 and sys.argv[1] == "field":
+    if len(sys.argv) > 1 and sys.argv[1] == "isosurface":
+        isosurface()
+    elif len(sys.argv) > 1 and sys.argv[1] == "field":
         field()
     elif len(sys.argv) > 1 and sys.argv[1] == "ahds":
         ahds()
