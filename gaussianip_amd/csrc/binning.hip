@@ -20,6 +20,7 @@
 // the order in which the atomics resolved: the tile / index buffers are deterministic and equal to
 // the reference's (tile | depth) stable radix sort (ties on depth resolved by Gaussian index).
 #include "gip_internal.h"
+#include "tile_sort_assign.h"
 
 // ------------------------------------------------------------------------------------------------
 // scan: ceil(V*T / 1024) + ceil(V*nblk / 1024) INDEPENDENT workgroups of 1024 threads, one launch, no inter-workgroup communication
@@ -429,14 +430,6 @@ __device__ __forceinline__ void wave_store(unsigned long long* a, uint32_t n, ui
 #pragma unroll
   for (int r = 0; r < R; r++) { const uint32_t i = base + r * 64 + lane; if (i < n) a[i] = v[r]; }
 }
-// one tile of n <= 64*R keys, one wave, registers only
-template <int R>
-__device__ __forceinline__ void wave_sort_tile(unsigned long long* a, uint32_t n, int lane) {
-  unsigned long long v[R];
-  wave_load<R>(a, n, 0, lane, v);
-  wave_sort<R>(v, lane);
-  wave_store<R>(a, n, 0, lane, v);
-}
 
 // LDS image of a key chunk: one pad slot per 16 keys, so that a thread writing its own 8 / 16 consecutive keys (stride
 // 8.5 / 17 slots across lanes) and a wave writing 64 consecutive keys are both (nearly) bank-conflict free
@@ -545,19 +538,26 @@ __device__ void lds_merge(unsigned long long* s, uint32_t n, const unsigned long
 
 // Per-tile sort, ONE launch of one 1024-thread workgroup per CU with a 16384-key (128 KB) LDS chunk.  The scan kernel
 // wrote tile_order longest class first and the class boundaries into header->class_end; every workgroup runs three
-// phases; A and M draw their work from atomic cursors in the header, so a workgroup held up in A simply draws less in M
-// (as separate launches the few long lists of a training view cost 25 serial microseconds):
+// phases.  Who sorts which tile in the first round is static (tile_sort_assign.h: from class_end, the grid size and the
+// workgroup's index alone), so that a training view's few hundred long lists cost no cursor round trip and no barrier, and
+// the short lists go to the workgroups that hold the least of the long ones; only what one round does not cover is drawn
+// from the header's atomic cursors (as separate launches the few long lists of a training view cost 25 serial microseconds):
 //   A  lists >= 2048 entries, one tile per workgroup: up to 16384 entries are read once, sorted entirely on chip
 //      (lds_sort) and written once; longer lists sort their 16384-key chunks that way and run only the merge strides
 //      >= 16384 in place in global memory.  (1M-Gaussian orbit views put ~6000 entries, up to 22k, in every occupied
-//      tile: phase A IS the sort there.)
-//   M  lists of 512..2047 entries, FOUR tiles per workgroup at a time: each 256-thread quarter sorts its tile in its own
+//      tile: phase A IS the sort there, and everything behind the first grid of tiles is drawn: a workgroup held up by a
+//      long list simply draws less.)
+//   M  lists of 512..2047 entries, up to FOUR tiles per workgroup at a time: each 256-thread quarter sorts its tile in its own
 //      2048-key slice of the chunk (one 512-key register block per wave, then the stages 1024 and 2048).  All quarters
 //      run the same fixed stage sequence so that the workgroup barriers line up; comparators beyond a list's length are
-//      skipped, a stage a short list does not need leaves it unchanged.
-//   B  lists of 1..511 entries, one tile per WAVE, entirely in registers (wave_sort_tile: 64 / 128 / 256 / 512-key
-//      networks by length), no LDS and no barrier; static round-robin over the grid's waves (a 1024^2 view has at most
-//      4096 tiles: about one per wave).
+//      skipped, a stage a short list does not need leaves it unchanged, a quarter without a tile runs the barriers only.
+//      Dealt over the workgroups without an A tile, as few quarters each as covers the class (fewer waves share the CU's
+//      vector units in wave_sort<8>).
+//   B  lists of 1..511 entries, one tile per WAVE, entirely in registers (wave_sort: 64 / 128 / 256 / 512-key networks by
+//      length), no LDS and no barrier (a 1024^2 view has at most 4096 tiles: about one per wave).  The wave requests its
+//      first tile's keys before phase M.  A wave whose quarter holds no M tile sorts its B tiles BEFORE it joins phase M's
+//      barriers, while the other quarters' waves are in their register networks; the others find the keys there when they
+//      come out of phase M.
 #define LONG_CHUNK 16384
 #define LONG_THREADS 1024
 __device__ __forceinline__ void ce_global(unsigned long long* a, uint32_t lo, uint32_t hi, uint32_t n) {
@@ -618,7 +618,9 @@ __device__ __forceinline__ void write_seg_tiles(const GipKernelParams& kp, const
 // one 512-key register block per wave, then the two merge levels 512 -> 1024 -> 2048, then the coalesced copy out.
 // Fixed sequence for every quarter, so the workgroup barriers inside merge_level line up.
 __device__ void quarter_sort(unsigned long long* s, uint32_t n, unsigned long long* a) {
-  const int lane = threadIdx.x & 63, w = (threadIdx.x >> 6) & 3;
+  // which of its quarter's four waves takes which 512-key block turns by two from one quarter to the next: most lists have two
+  // blocks, and the waves 4q, 4q + 1 of all quarters share two of the CU's four vector units (a workgroup's waves go round them)
+  const int lane = threadIdx.x & 63, w = ((threadIdx.x >> 6) + ((threadIdx.x >> 8) << 1)) & 3;
   const uint32_t ltid = threadIdx.x & 255, base = w * 512;
   const bool multi = n > 512;
   if (base < n) {
@@ -645,71 +647,100 @@ gip_tile_sort_kernel(GipKernelParams kp, GipRasterHeader* __restrict__ header, c
                      uint32_t* __restrict__ seg_tile, unsigned long long* __restrict__ keys) {
   extern __shared__ __attribute__((aligned(16))) unsigned long long s_long[];
   __shared__ uint32_t s_pos;
-  const uint32_t end_a = header->class_end[1], end_m = header->class_end[0], end_b = header->class_end[3];
-  // ---- phase A: workgroup per tile ----
-  if (end_a > 0) {
-    for (;;) {
-      __syncthreads();
-      if (threadIdx.x == 0) s_pos = atomicAdd(&header->sort_cursor, 1u);
-      __syncthreads();
-      const uint32_t pos = s_pos;
-      if (pos >= end_a) break;
-      const uint32_t t = tile_order[pos];
-      const uint32_t start = tile_start[t];
-      const uint32_t n = gip_list_len(kp, start, tile_start[t + 1]);
-      if (n == 0) continue;
-      unsigned long long* a = keys + gip_list_base(kp, t, start);
-      write_seg_tiles<LONG_THREADS>(kp, seg_start, seg_tile, t, n);
-      if (n <= 1) continue;
-      if (n <= LONG_CHUNK) lds_sort<LONG_THREADS>(s_long, n, a, a);
-      else sort_beyond_lds(a, n, s_long);
-    }
-  }
-  // ---- phase M: quarter (256 threads) per tile, four tiles per draw ----
-  if (end_m > end_a) {
-    const uint32_t q = threadIdx.x >> 8;
-    for (;;) {
-      __syncthreads();
-      if (threadIdx.x == 0) s_pos = atomicAdd(&header->sort_cursor_m, 4u);
-      __syncthreads();
-      const uint32_t pos = end_a + s_pos + q;
-      if (end_a + s_pos >= end_m) break;
-      uint32_t n = 0;
-      unsigned long long* a = keys;
-      if (pos < end_m) {
-        const uint32_t t = tile_order[pos];
-        const uint32_t start = tile_start[t];
-        n = gip_list_len(kp, start, tile_start[t + 1]);
-        if (n > 0) {
-          a = keys + gip_list_base(kp, t, start);
-          const uint32_t s0 = seg_start[t], ns = (n + GIP_SEGMENT - 1) / GIP_SEGMENT;
-          for (uint32_t b = threadIdx.x & 255; b < ns; b += 256)
-            if (s0 + b < kp.seg_capacity) seg_tile[s0 + b] = t;
-        }
-      }
-      quarter_sort(s_long + q * PADK_SLOTS(2048), n > 1 ? n : 0, a);
-    }
-  }
-  // ---- phase B: wave per tile, static round-robin over all waves of the grid (no barrier from here on) ----
+  const GipSortAssign as = gip_sort_assign(gridDim.x, header->class_end[1], header->class_end[0], header->class_end[3]);
+  const uint32_t end_a = as.end_a, end_m = as.end_m, end_b = as.end_b;
   const int lane = threadIdx.x & 63;
-  const uint32_t waves_per_wg = LONG_THREADS / 64;
-  // consecutive positions (similar lengths: the order is by size class) go to different CUs, not to the waves of one
-  for (uint32_t pos = end_m + (threadIdx.x >> 6) * gridDim.x + blockIdx.x; pos < end_b; pos += gridDim.x * waves_per_wg) {
+  const uint32_t wave = threadIdx.x >> 6, q = threadIdx.x >> 8;
+  // ---- phase A: workgroup per tile; position blockIdx.x first, the rounds behind one grid of tiles from the cursor ----
+  for (uint32_t pos = gip_sort_a_pos(as, blockIdx.x); pos < end_a;) {
     const uint32_t t = tile_order[pos];
     const uint32_t start = tile_start[t];
     const uint32_t n = gip_list_len(kp, start, tile_start[t + 1]);
-    if (n == 0) continue;
-    {
-      const uint32_t s0 = seg_start[t], ns = (n + GIP_SEGMENT - 1) / GIP_SEGMENT;
-      for (uint32_t b = lane; b < ns; b += 64)
-        if (s0 + b < kp.seg_capacity) seg_tile[s0 + b] = t;
+    if (n > 0) {
+      unsigned long long* a = keys + gip_list_base(kp, t, start);
+      write_seg_tiles<LONG_THREADS>(kp, seg_start, seg_tile, t, n);
+      if (n > LONG_CHUNK) sort_beyond_lds(a, n, s_long);
+      else if (n > 1) lds_sort<LONG_THREADS>(s_long, n, a, a);
     }
-    unsigned long long* a = keys + gip_list_base(kp, t, start);
-    if (n <= 1) continue;
-    if (n <= 64) wave_sort_tile<1>(a, n, lane);
-    else if (n <= 128) wave_sort_tile<2>(a, n, lane);
-    else if (n <= 256) wave_sort_tile<4>(a, n, lane);
-    else wave_sort_tile<8>(a, n, lane);
+    if (end_a <= as.a_first) break;                   // one round covered the class: no draw, no barrier
+    __syncthreads();
+    if (threadIdx.x == 0) s_pos = atomicAdd(&header->sort_cursor, 1u);
+    __syncthreads();
+    pos = as.a_first + s_pos;
+  }
+  // ---- the wave's first B tile and the quarter's static M tile: both descriptor chains (tile_order -> tile_start / seg_start)
+  // go out together, then the B tile's keys are requested into the registers its network will use.  They arrive while the
+  // workgroup is in phase M.  (Behind phase A, not in front of it: 16 more registers across lds_sort's merge_level<16> would not
+  // fit 128, and a workgroup with an A tile holds no static M tile and B tiles only when every other wave of the grid has one.)
+  const uint32_t b_stride = gip_sort_b_stride(as);
+  uint32_t bpos = gip_sort_b_pos(as, blockIdx.x, wave);
+  const uint32_t mq = gip_sort_m_quarters(as, blockIdx.x);
+  uint32_t bt = bpos < end_b ? tile_order[bpos] : 0u;
+  const uint32_t mt = q < mq ? tile_order[gip_sort_m_pos(as, blockIdx.x, q)] : 0u;
+  uint32_t bstart = 0, bn = 0, bs0 = 0, mstart = 0, mn = 0, ms0 = 0;
+  if (bpos < end_b) { bstart = tile_start[bt]; bn = gip_list_len(kp, bstart, tile_start[bt + 1]); bs0 = seg_start[bt]; }
+  if (q < mq) { mstart = tile_start[mt]; mn = gip_list_len(kp, mstart, tile_start[mt + 1]); ms0 = seg_start[mt]; }
+  unsigned long long bv[8];
+  wave_load<8>(keys + gip_list_base(kp, bt, bstart), bn, 0, lane, bv);
+  // The waves of a quarter without a static M tile would only wait at quarter_sort's first barrier for the other quarters'
+  // register networks: they sort their B tiles first, on vector units that phase M leaves idle (B fills a workgroup's waves from
+  // the last one down, tile_sort_assign.h).  The other waves sort theirs behind phase M.  One copy of each phase's code.
+  const bool b_first = q >= mq;
+#pragma nounroll
+  for (int pass = 0; pass < 2; pass++) {
+    // ---- phase M: quarter (256 threads) per tile; the static share in one pass without a barrier in front of it (no workgroup
+    // comes here from phase A with a static share, so nobody still reads the chunk), what it does not cover four per draw ----
+    if (pass == 1 && (mq > 0 || as.m_drawn < end_m)) {
+      for (bool dealt = mq > 0;; dealt = false) {
+        uint32_t t = mt, start = mstart, n = mn, s0 = ms0;
+        if (!dealt) {
+          if (as.m_drawn >= end_m) break;
+          __syncthreads();
+          if (threadIdx.x == 0) s_pos = atomicAdd(&header->sort_cursor_m, 4u);
+          __syncthreads();
+          const uint32_t pos = as.m_drawn + s_pos + q;
+          if (as.m_drawn + s_pos >= end_m) break;
+          t = 0; start = 0; n = 0; s0 = 0;
+          if (pos < end_m) {
+            t = tile_order[pos];
+            start = tile_start[t];
+            n = gip_list_len(kp, start, tile_start[t + 1]);
+            s0 = seg_start[t];
+          }
+        }
+        if (n > 0) {
+          const uint32_t ns = (n + GIP_SEGMENT - 1) / GIP_SEGMENT;
+          for (uint32_t b = threadIdx.x & 255; b < ns; b += 256)
+            if (s0 + b < kp.seg_capacity) seg_tile[s0 + b] = t;
+        }
+        quarter_sort(s_long + q * PADK_SLOTS(2048), n > 1 ? n : 0, keys + gip_list_base(kp, t, start));
+      }
+    }
+    // ---- phase B: wave per tile, no barrier; the first tile's keys are in bv, a wave with more than one tile loads the next
+    // one where it stored the last ----
+    if ((pass == 0) == b_first) {
+      while (bpos < end_b) {
+        if (bn > 0) {
+          const uint32_t ns = (bn + GIP_SEGMENT - 1) / GIP_SEGMENT;
+          for (uint32_t b = lane; b < ns; b += 64)
+            if (bs0 + b < kp.seg_capacity) seg_tile[bs0 + b] = bt;
+        }
+        if (bn > 1) {
+          unsigned long long* a = keys + gip_list_base(kp, bt, bstart);
+          if (bn <= 64) { unsigned long long v[1] = {bv[0]}; wave_sort<1>(v, lane); wave_store<1>(a, bn, 0, lane, v); }
+          else if (bn <= 128) { unsigned long long v[2] = {bv[0], bv[1]}; wave_sort<2>(v, lane); wave_store<2>(a, bn, 0, lane, v); }
+          else if (bn <= 256) { unsigned long long v[4] = {bv[0], bv[1], bv[2], bv[3]}; wave_sort<4>(v, lane); wave_store<4>(a, bn, 0, lane, v); }
+          else { wave_sort<8>(bv, lane); wave_store<8>(a, bn, 0, lane, bv); }
+        }
+        bpos += b_stride;
+        if (bpos >= end_b) break;
+        bt = tile_order[bpos];
+        bstart = tile_start[bt];
+        bn = gip_list_len(kp, bstart, tile_start[bt + 1]);
+        bs0 = seg_start[bt];
+        wave_load<8>(keys + gip_list_base(kp, bt, bstart), bn, 0, lane, bv);
+      }
+    }
   }
 }
 

@@ -611,6 +611,8 @@ def state_views(plan):
         tile_start=tile_start,
         keys=keys,
         n_contrib=view(L.n_contrib, V * H * W, torch.int32, (V, H, W)),
+        seg_start=view(L.seg_start, V * T + 1, torch.int32, (V * T + 1,)),
+        seg_tile=view(L.seg_tile, (L.checkpoints - L.seg_tile) // 4, torch.int32, ((L.checkpoints - L.seg_tile) // 4,)),
         tiles_x=L.tiles_x, tiles_y=L.tiles_y)
 
 
