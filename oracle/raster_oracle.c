@@ -674,7 +674,8 @@ static void cov3D_backward(const float* scale, float scale_modifier, const float
     for (int k = 0; k < 3; k++)
       dLm[ii * 3 + k] = 2.0f * (dS[ii * 3 + 0] * R[0 * 3 + k] * s[k] + dS[ii * 3 + 1] * R[1 * 3 + k] * s[k] + dS[ii * 3 + 2] * R[2 * 3 + k] * s[k]);
   /* NOTE (reference quirk, reproduced): the fork's dL_dscale is the gradient w.r.t. mod*scale, it is
-   * not multiplied by scale_modifier.  Identical at scale_modifier = 1 (the only differentiated case). */
+   * not multiplied by scale_modifier.  Identical at scale_modifier = 1; at 0.5 / 1.5 / 2.5 tests/test_oracle_vs_dense.py
+   * pins dL_dscale * scale_modifier to autograd with respect to the raw scales. */
   if (ds_out)
     for (int k = 0; k < 3; k++)
       ds_out[k] = R[0 * 3 + k] * dLm[0 * 3 + k] + R[1 * 3 + k] * dLm[1 * 3 + k] + R[2 * 3 + k] * dLm[2 * 3 + k];

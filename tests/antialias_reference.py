@@ -21,10 +21,11 @@ DILATION = 0.3
 
 
 def compensation(*, means3D, viewmatrix, H, W, tanfovx, tanfovy, scales=None, rotations=None, cov3D_precomp=None,
-                 scale_modifier=1.0):
+                 scale_modifier=1.0, fork_clamp=False):
     """comp [P] (float64) for one view; differentiable in means3D and in scales / rotations or cov3D_precomp.
     viewmatrix: [4,4] in the cameras.py layout (row-vector convention).  Values of Gaussians behind the near plane are
-    finite but meaningless (the rasterizer culls them)."""
+    finite but meaningless (the rasterizer culls them).  `fork_clamp`: as in dense_reference.dense_render (comp's derivative
+    runs through the same clamped Jacobian as the conic's)."""
     dt = torch.float64
     P = means3D.shape[0]
     ph = torch.cat([means3D, torch.ones(P, 1, dtype=dt)], dim=1)
@@ -43,6 +44,9 @@ def compensation(*, means3D, viewmatrix, H, W, tanfovx, tanfovy, scales=None, ro
     tzs = torch.where(tz > 0.2, tz, torch.ones_like(tz))
     tx = torch.clamp(pv[:, 0] / tzs, -limx, limx) * tzs
     ty = torch.clamp(pv[:, 1] / tzs, -limy, limy) * tzs
+    if fork_clamp:
+        tx = torch.where((pv[:, 0] / tzs).abs() > limx, tx.detach(), pv[:, 0])
+        ty = torch.where((pv[:, 1] / tzs).abs() > limy, ty.detach(), pv[:, 1])
     zero = torch.zeros_like(tzs)
     J = torch.stack([fx / tzs, zero, -(fx * tx) / (tzs * tzs), zero, fy / tzs, -(fy * ty) / (tzs * tzs)], dim=-1).reshape(-1, 2, 3)
     Mx = J @ viewmatrix[:3, :3].transpose(0, 1)
@@ -57,7 +61,7 @@ def _t64(a):
     return None if a is None else torch.as_tensor(np.asarray(a), dtype=torch.float64)
 
 
-def scene_compensation(sc, cam, H, W, cov=None, requires_grad=False):
+def scene_compensation(sc, cam, H, W, cov=None, requires_grad=False, fork_clamp=False):
     """comp of a numpy scene (tests/scenes.py layout) under a numpy camera (scenes.camera): returns (comp [P] float64 tensor,
     leaves dict).  With requires_grad the leaves (means3D and scales / rotations, or cov3D_precomp) are autograd leaves."""
     leaves = {"means3D": _t64(sc["means3D"])}
@@ -68,7 +72,8 @@ def scene_compensation(sc, cam, H, W, cov=None, requires_grad=False):
     if requires_grad:
         for v in leaves.values():
             v.requires_grad_(True)
-    comp = compensation(viewmatrix=_t64(cam["viewmatrix"]), H=H, W=W, tanfovx=cam["tanfovx"], tanfovy=cam["tanfovy"], **leaves)
+    comp = compensation(viewmatrix=_t64(cam["viewmatrix"]), H=H, W=W, tanfovx=cam["tanfovx"], tanfovy=cam["tanfovy"],
+                        fork_clamp=fork_clamp, **leaves)
     return comp, leaves
 
 
@@ -77,11 +82,11 @@ def effective_opacities(sc, comp):
     return (np.asarray(sc["opacities"], np.float64) * comp.detach().numpy()[:, None]).astype(np.float32)
 
 
-def composite_grads(go, sc, cam, H, W, cov=None):
+def composite_grads(go, sc, cam, H, W, cov=None, fork_clamp=False):
     """Every gradient of the antialiased model from an oracle backward `go` run on effective opacities:
     dL/dopacity = comp * dL/dopacity_eff, and dL/dopacity_eff * opacity chained through comp into means3D and
     scales / rotations (or cov3D_precomp).  Returns a dict shaped like `go` (float64)."""
-    comp, leaves = scene_compensation(sc, cam, H, W, cov=cov, requires_grad=True)
+    comp, leaves = scene_compensation(sc, cam, H, W, cov=cov, requires_grad=True, fork_clamp=fork_clamp)
     g_eff = np.asarray(go["opacities"], np.float64).reshape(-1)
     w = torch.from_numpy(g_eff * np.asarray(sc["opacities"], np.float64).reshape(-1))
     names = list(leaves)

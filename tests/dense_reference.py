@@ -49,9 +49,13 @@ def _quat_to_rot(q):
 
 def dense_render(*, means3D, opacities, viewmatrix, projmatrix, campos, bg, H, W, tanfovx, tanfovy,
                  shs=None, colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None, sh_degree=0,
-                 scale_modifier=1.0, means2D=None):
+                 scale_modifier=1.0, means2D=None, fork_clamp=False):
     """All tensors float64.  viewmatrix / projmatrix are the [4,4] tensors as cameras.py stores them
-    (row-vector convention: p_view = [p, 1] @ viewmatrix).  Returns dict(color, depth, alpha, radii, n_contrib)."""
+    (row-vector convention: p_view = [p, 1] @ viewmatrix).  Returns dict(color, depth, alpha, radii, n_contrib).
+
+    `fork_clamp`: differentiate the 1.3 x tanfov clamp of the Jacobian as the fork's backward does.  On the clamped side
+    (|x / z| > limit) the fork zeroes dL/dx (its x_grad_mul) but keeps the clamped x = limit * z a CONSTANT in dL/dz, where
+    the true derivative has a limit * dL/dx term.  Same forward values; default: plain autograd."""
     dt = torch.float64
     P = means3D.shape[0]
     ones = torch.ones(P, 1, dtype=dt)
@@ -80,6 +84,9 @@ def dense_render(*, means3D, opacities, viewmatrix, projmatrix, campos, bg, H, W
     tzs = torch.where(valid, tz, torch.ones_like(tz))
     tx = torch.clamp(pv[:, 0] / tzs, -limx, limx) * tzs
     ty = torch.clamp(pv[:, 1] / tzs, -limy, limy) * tzs
+    if fork_clamp:
+        tx = torch.where((pv[:, 0] / tzs).abs() > limx, tx.detach(), pv[:, 0])
+        ty = torch.where((pv[:, 1] / tzs).abs() > limy, ty.detach(), pv[:, 1])
     zero = torch.zeros_like(tzs)
     J = torch.stack([fx / tzs, zero, -(fx * tx) / (tzs * tzs), zero, fy / tzs, -(fy * ty) / (tzs * tzs)], dim=-1).reshape(-1, 2, 3)
     Rv = viewmatrix[:3, :3].transpose(0, 1)
@@ -191,6 +198,21 @@ def look_at_camera(elev_deg, azim_deg, dist, fovy_deg, H, W, znear=0.01, zfar=10
     full = view @ proj
     campos = torch.inverse(view)[3, :3]
     return view, full, campos, tanx, tany
+
+
+def clamp_cull_masks(means3D, viewmatrix, tanfovx, tanfovy):
+    """Which Gaussians take the projection's two special branches under one camera, from the inputs rounded to float32 (what
+    the oracle and the kernels receive), evaluated in float64.  Returns bool numpy arrays (clamped, behind):
+    behind: view-space z <= 0.2 (near cull); clamped: not behind and |x / z| > 1.3 tanfovx or |y / z| > 1.3 tanfovy."""
+    import numpy as np
+    m = np.asarray(means3D, dtype=np.float32).astype(np.float64)
+    v = np.asarray(viewmatrix, dtype=np.float32).astype(np.float64).reshape(4, 4)
+    pv = np.concatenate([m, np.ones((m.shape[0], 1))], 1) @ v
+    z = pv[:, 2]
+    behind = z <= 0.2
+    zs = np.where(behind, 1.0, z)
+    clamped = ~behind & ((np.abs(pv[:, 0] / zs) > 1.3 * tanfovx) | (np.abs(pv[:, 1] / zs) > 1.3 * tanfovy))
+    return clamped, behind
 
 
 def random_scene(P, seed, sh_M=1, radius=0.5, scale_lo=0.01, scale_hi=0.08, opa_lo=0.05, opa_hi=0.95):

@@ -119,9 +119,10 @@ def test_compensation_gradcheck():
         [m, cov], eps=1e-9)
 
 
-def _composite_vs_dense(oracle, P, H, W, seed, sh_degree=0, use_cov=False, use_colors=False, bgval=(0.2, 0.5, 0.9)):
+def _composite_vs_dense(oracle, P, H, W, seed, sh_degree=0, use_cov=False, use_colors=False, bgval=(0.2, 0.5, 0.9),
+                        cam=(10.0, 40.0, 1.6, 60.0), scene_kw=None, fork_clamp=False):
     M = (sh_degree + 1) ** 2
-    sc64, view, proj, campos, tanx, tany = _scene(P, seed, H, W, sh_M=M, scale_lo=0.004, scale_hi=0.05)
+    sc64, view, proj, campos, tanx, tany = _scene(P, seed, H, W, cam=cam, sh_M=M, **(scene_kw or dict(scale_lo=0.004, scale_hi=0.05)))
     sc = {k: v.numpy().astype(np.float32) for k, v in sc64.items()}
     scd = {k: torch.from_numpy(v).double() for k, v in sc.items()}          # the float32 scene, exactly, in float64
     bg = torch.tensor(bgval, dtype=torch.float64)
@@ -155,12 +156,14 @@ def _composite_vs_dense(oracle, P, H, W, seed, sh_degree=0, use_cov=False, use_c
         leaves["shs"] = scd["shs"].clone().requires_grad_(True)
         okw["shs"] = sc["shs"]
     # dense float64 antialiased model
-    comp = compensation(means3D=leaves["means3D"], viewmatrix=camd["viewmatrix"], H=H, W=W, tanfovx=tanx, tanfovy=tany, **ckw)
+    comp = compensation(means3D=leaves["means3D"], viewmatrix=camd["viewmatrix"], H=H, W=W, tanfovx=tanx, tanfovy=tany,
+                        fork_clamp=fork_clamp, **ckw)
     m2d = torch.zeros(P, 3, dtype=torch.float64, requires_grad=True)
     out = dense_render(means3D=leaves["means3D"], opacities=leaves["opacities"] * comp[:, None], viewmatrix=camd["viewmatrix"],
                        projmatrix=camd["projmatrix"], campos=camd["campos"], bg=bg, H=H, W=W, tanfovx=tanx, tanfovy=tany,
                        sh_degree=sh_degree, means2D=m2d, shs=leaves.get("shs"), colors_precomp=leaves.get("colors_precomp"),
-                       scales=leaves.get("scales"), rotations=leaves.get("rotations"), cov3D_precomp=leaves.get("cov3D_precomp"))
+                       scales=leaves.get("scales"), rotations=leaves.get("rotations"), cov3D_precomp=leaves.get("cov3D_precomp"),
+                       fork_clamp=fork_clamp)
     g = torch.Generator().manual_seed(99)
     gC = torch.randn(3, H, W, generator=g, dtype=torch.float64)
     gD = torch.randn(1, H, W, generator=g, dtype=torch.float64)
@@ -175,7 +178,7 @@ def _composite_vs_dense(oracle, P, H, W, seed, sh_degree=0, use_cov=False, use_c
     np.testing.assert_allclose(depth, out["depth"].detach().numpy(), atol=2e-5)
     np.testing.assert_allclose(alpha, out["alpha"].detach().numpy(), atol=2e-5)
     go = ro.backward(gC.numpy(), gD.numpy(), gA.numpy())
-    ref = composite_grads(go, sc, cam, H, W, cov=None if cov is None else cov.numpy())
+    ref = composite_grads(go, sc, cam, H, W, cov=None if cov is None else cov.numpy(), fork_clamp=fork_clamp)
 
     def close(name, ours, dense, tol=2e-3):
         dense = dense.detach().numpy().reshape(np.shape(ours))
@@ -192,6 +195,20 @@ def _composite_vs_dense(oracle, P, H, W, seed, sh_degree=0, use_cov=False, use_c
 def test_composite_oracle_reference_equals_dense_antialiased_model(oracle, deg):
     comp = _composite_vs_dense(oracle, P=120, H=48, W=56, seed=40 + deg, sh_degree=deg)
     assert float(comp.min()) < 0.9          # the mode changes this scene
+
+
+def test_composite_oracle_reference_on_clamped_gaussians(oracle):
+    """Scene A of test_oracle_vs_dense.py (48 visible Gaussians on the clamped side of the Jacobian, 24 behind the near plane):
+    the compensation's derivative runs through the clamped Jacobian too, so the composite reference and the dense model take
+    `fork_clamp` alike.  The reference of test_gpu_raster_branches.py's antialiased case."""
+    from dense_reference import clamp_cull_masks
+    from test_oracle_vs_dense import SCENE_A as A
+    comp = _composite_vs_dense(oracle, P=A["P"], H=A["H"], W=A["W"], seed=A["seed"], sh_degree=A["sh_degree"], cam=A["cam"],
+                               scene_kw=A["scene_kw"], fork_clamp=True)
+    sc, view, _, _, tanx, tany = _scene(A["P"], A["seed"], A["H"], A["W"], cam=A["cam"], **A["scene_kw"])
+    clamped, behind = clamp_cull_masks(sc["means3D"].numpy(), view.numpy(), tanx, tany)
+    # the compensation must act on the clamped Gaussians, or their branch of its derivative carries nothing
+    assert int((clamped & (comp.numpy() < 0.999)).sum()) >= 24 and int(behind.sum()) >= 12
 
 
 def test_composite_oracle_reference_equals_dense_precomputed_inputs(oracle):

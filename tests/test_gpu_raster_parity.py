@@ -52,13 +52,15 @@ def _check_forward(oracle, kind, P, H, W, seed, sh_degree, cam_args, bg=(0.0, 0.
     return _check_forward_scene(oracle, sc, cam, H, W, sh_degree, bg, nc_mismatch_frac)[0]
 
 
-def _check_forward_scene(oracle, sc, cam, H, W, sh_degree, bg=(0.0, 0.0, 0.0), nc_mismatch_frac=2e-4, min_keep=0.5, stats=None):
+def _check_forward_scene(oracle, sc, cam, H, W, sh_degree, bg=(0.0, 0.0, 0.0), nc_mismatch_frac=2e-4, min_keep=0.5, stats=None,
+                         scale_modifier=1.0, outputs=None):
     """Forward of one view through the C-ABI against the oracle: integer buffers bit-exact, images within IMG_TOL.
     Returns (num_rendered, oracle object with its forward state) so a backward comparison can follow.
-    `stats`: a dict that receives the library's header words and the number of (proven knife-edge) pixels out of tolerance."""
+    `stats`: a dict that receives the library's header words and the number of (proven knife-edge) pixels out of tolerance.
+    `outputs`: a dict that receives the images, the radii and the plan of the call."""
     from gaussianip_amd import rasterizer as R
-    ro, (o_color, o_radii, o_depth, o_alpha) = _oracle_forward(oracle, sc, cam, H, W, bg, sh_degree)
-    st = _settings(cam, H, W, bg, sh_degree)
+    ro, (o_color, o_radii, o_depth, o_alpha) = _oracle_forward(oracle, sc, cam, H, W, bg, sh_degree, scale_modifier)
+    st = _settings(cam, H, W, bg, sh_degree, scale_modifier)
     (color, radii, depth, alpha), plan = R.forward_with_state(
         _dev(sc["means3D"]), _dev(sc["opacities"]), [st], shs=_dev(sc["shs"]), scales=_dev(sc["scales"]),
         rotations=_dev(sc["rotations"]))
@@ -84,6 +86,8 @@ def _check_forward_scene(oracle, sc, cam, H, W, sh_degree, bg=(0.0, 0.0, 0.0), n
     # ---- images ----
     n_out = _assert_images(ro, color[0], depth[0], alpha[0], o_color, o_depth, o_alpha, sv["n_contrib"][0], nc_expected,
                            nc_mismatch_frac)
+    if outputs is not None:
+        outputs.update(color=color, radii=radii, depth=depth, alpha=alpha, plan=plan)
     if stats is not None:
         ts = sv["tile_start"].cpu().numpy().astype(np.int64)
         stats.update(num_rendered=int(hdr[1]), max_tile_count=int(hdr[3]), num_segments=int(hdr[5]), pixels_out_of_tolerance=n_out,
@@ -235,7 +239,11 @@ def test_forward_parity_close_camera_big_tiles(oracle):
 
 
 def _check_backward(oracle, kind, P, H, W, seed, sh_degree, use_precomp=False, bg=(0.3, 0.1, 0.2), tol=2e-3, scene=None, cam=None,
-                    tol_e2e=5e-3, geom_tol=None):
+                    tol_e2e=5e-3, geom_tol=None, scale_modifier=1.0, upstream=("color", "depth", "alpha"), cov=None, outputs=None):
+    """`scale_modifier`: of the settings and of the oracle (both return the scale gradient with respect to modifier * scale).
+    `upstream`: the outputs that get an upstream gradient; the others are left out of the loss, so their gradient reaches the
+    kernels as a NULL pointer, and go to the oracle as None.  `cov`: the [P,6] covariances of a `use_precomp` call (default: the
+    oracle's own).  `outputs`: a dict that receives the images, radii and the gradients of the precomputed inputs."""
     from gaussianip_amd import GaussianRasterizer
     sc = scenes.make_scene(kind, P, seed=seed, sh_degree=sh_degree) if scene is None else scene
     cam = scenes.camera(8.0, 60.0, 1.7, 60.0, H, W) if cam is None else cam
@@ -243,9 +251,11 @@ def _check_backward(oracle, kind, P, H, W, seed, sh_degree, use_precomp=False, b
     gC = rng.normal(size=(3, H, W)).astype(np.float32)
     gD = rng.normal(size=(1, H, W)).astype(np.float32)
     gA = rng.normal(size=(1, H, W)).astype(np.float32)
-    colors = cov = None
+    colors = None
+    gC, gD, gA = (g if k in upstream else None for k, g in zip(("color", "depth", "alpha"), (gC, gD, gA)))
     if use_precomp:
         colors = rng.uniform(0, 1, (P, 3)).astype(np.float32)
+    if use_precomp and cov is None:
         ro0, _ = _oracle_forward(oracle, sc, cam, H, W, bg, sh_degree)
         cov = ro0.geom()["cov3D"]
         bad = ~(np.abs(cov).sum(1) > 0)   # culled Gaussians have no cov3D in the oracle state: rebuild analytically
@@ -256,10 +266,10 @@ def _check_backward(oracle, kind, P, H, W, seed, sh_degree, use_precomp=False, b
             S = (L @ L.transpose(1, 2)).numpy()
             full = np.stack([S[:, 0, 0], S[:, 0, 1], S[:, 0, 2], S[:, 1, 1], S[:, 1, 2], S[:, 2, 2]], 1).astype(np.float32)
             cov[bad] = full[bad]
-    ro, _ = _oracle_forward(oracle, sc, cam, H, W, bg, sh_degree, colors=colors, cov=cov)
+    ro, o_out = _oracle_forward(oracle, sc, cam, H, W, bg, sh_degree, scale_modifier, colors=colors, cov=cov)
     go_e2e = ro.backward(gC, gD, gA)
 
-    st = _settings(cam, H, W, bg, sh_degree)
+    st = _settings(cam, H, W, bg, sh_degree, scale_modifier)
     t = {k: _dev(v).requires_grad_(True) for k, v in sc.items()}
     means2D = torch.zeros(P, 3, device="cuda", requires_grad=True)
     kw = dict(means3D=t["means3D"], means2D=means2D, opacities=t["opacities"])
@@ -271,15 +281,20 @@ def _check_backward(oracle, kind, P, H, W, seed, sh_degree, use_precomp=False, b
     else:
         kw.update(shs=t["shs"], scales=t["scales"], rotations=t["rotations"])
     color, radii, depth, alpha = GaussianRasterizer(st)(**kw)
-    loss = (color * _dev(gC)).sum() + (depth * _dev(gD)).sum() + (alpha * _dev(gA)).sum()
+    loss = sum((o * _dev(g)).sum() for o, g in ((color, gC), (depth, gD), (alpha, gA)) if g is not None)
     loss.backward()
     torch.cuda.synchronize()
+    if outputs is not None:
+        outputs.update(color=color.detach(), radii=radii, depth=depth.detach(), alpha=alpha.detach(), oracle=ro, oracle_radii=o_out[1],
+                       colors_precomp=None if tc is None else tc.grad, cov3D_precomp=None if tv is None else tv.grad)
 
     # The fork's backward derives every T_j from T_final := 1 - alpha_out: at a nearly opaque pixel (alpha 0.9999) a
     # 1-ulp difference of the two forwards' alpha images (fp32 summation order) is a 1e-3 relative difference of T_final.
     # So the backward is checked in isolation at `tol` (the oracle replays with THIS forward's alpha image, exactly the
     # input the fork's backward gets) and end to end at the looser bar that conditioning allows.
     go_iso = ro.backward(gC, gD, gA, alpha_out=alpha.detach().cpu().numpy().reshape(1, H, W))
+    if outputs is not None:
+        outputs["oracle_grads"] = go_iso
 
     def close(name, ours, ref, floor=0.0, bar=tol):
         # `floor`: magnitude below which a gradient is analytically zero (e.g. the rotation of an isotropic Gaussian)
