@@ -331,6 +331,13 @@ def model_lib():
         lib.gip_tet_sdf_diff.argtypes = [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _sz, _vp]
         lib.gip_tet_sdf_diff_backward.restype = ctypes.c_int
         lib.gip_tet_sdf_diff_backward.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp]
+        _levels = [_vp] * 5 + [_i64, _i32, _i32, _i64]        # the level table's five host arrays, then N, L, F, P
+        lib.gip_hashgrid_forward.restype = ctypes.c_int
+        lib.gip_hashgrid_forward.argtypes = [_vp, _vp] + _levels + [_vp, _vp]
+        lib.gip_hashgrid_backward_input.restype = ctypes.c_int
+        lib.gip_hashgrid_backward_input.argtypes = [_vp, _vp, _vp] + _levels + [_vp, _vp]
+        lib.gip_hashgrid_backward_table.restype = ctypes.c_int
+        lib.gip_hashgrid_backward_table.argtypes = [_vp, _vp] + _levels + [_vp, _vp]
         _model = _Counted(lib)
     return _model
 
@@ -508,3 +515,4 @@ MESH_UV_SYMBOLS = ["gip_uv_face_classes", "gip_uv_chart_rounds", "gip_uv_chart_b
                    "gip_uv_vertex_tangents_backward", "gip_texture_dilate"]
 MESH_TET_SYMBOLS = ["gip_tet_workspace_size", "gip_tet_mark", "gip_tet_emit", "gip_tet_backward", "gip_tet_sdf_diff",
                     "gip_tet_sdf_diff_backward"]
+HASHGRID_SYMBOLS = ["gip_hashgrid_forward", "gip_hashgrid_backward_input", "gip_hashgrid_backward_table"]

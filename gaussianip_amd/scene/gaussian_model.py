@@ -326,21 +326,30 @@ class GaussianModel:
         return {"density": out["density"], "gradient": out["gradient"] * scale, "color": self._blend(out["color_sum"], out["density"])}
 
     @torch.no_grad()
-    def to_tetrahedra_sdf_grid(self, resolution=64, density_thresh=1.0, tets_path=None, **field_kwargs):
+    def to_tetrahedra_sdf_grid(self, resolution=64, density_thresh=1.0, tets_path=None, feature_steps=0, feature_lr=0.01,
+                               pos_encoding_config=None, mlp_network_config=None, **field_kwargs):
         """A utils.isosurface.TetrahedraSDFGrid that starts from this model's surface density == density_thresh: the bridge from the
         representation the project trains to a mesh whose vertices AND connectivity can be optimised further.  isosurface_bbox is the
         box of the normalised cloud, center -/+ 1 / scale; sdf = clamp(density_thresh - density, -1, 1) with the density of
         sample_fields(**field_kwargs) at the grid's vertices (the clamp is the reference's TetrahedraSDFGrid.create_from of an
         implicit volume); inside is negative, as in the reference.  resolution and tets_path choose the tetrahedral grid
         (utils.isosurface.MarchingTetrahedraHelper); the deformation starts at zero.  field_kwargs are sample_fields' num_blocks and
-        relax_ratio, and field_resolution for its resolution (the name `resolution` is the tetrahedral grid's here)."""
+        relax_ratio, and field_resolution for its resolution (the name `resolution` is the tetrahedral grid's here).
+        feature_steps > 0 gives the grid a feature network (n_feature_dims=3; pos_encoding_config and mlp_network_config as
+        TetrahedraSDFGrid's, the reference's by default) and fits it with that many Adam steps at feature_lr to sample_fields'
+        blended colour at the vertices of the extracted surface: the loss is the MSE of sigmoid(features).  The default 0 returns
+        the geometry alone, as before."""
         from ..utils.isosurface import TetrahedraSDFGrid, scale_tensor
         if "field_resolution" in field_kwargs:
             field_kwargs["resolution"] = field_kwargs.pop("field_resolution")
         if set(field_kwargs) - {"resolution", "num_blocks", "relax_ratio"}:
             raise TypeError("to_tetrahedra_sdf_grid: unknown arguments %s" % sorted(set(field_kwargs) - {"resolution", "num_blocks", "relax_ratio"}))
         dev = self._xyz.device
-        grid = TetrahedraSDFGrid(isosurface_resolution=resolution, tets_path=tets_path).to(dev)
+        feature_steps = int(feature_steps)
+        if feature_steps < 0:
+            raise ValueError("to_tetrahedra_sdf_grid: feature_steps must not be negative")
+        grid = TetrahedraSDFGrid(isosurface_resolution=resolution, tets_path=tets_path, n_feature_dims=3 if feature_steps else 0,
+                                 pos_encoding_config=pos_encoding_config, mlp_network_config=mlp_network_config).to(dev)
         if self._field_sources() is not None:                # sets center / scale; without sources the box stays the unit one
             half = 1.0 / self.scale
             grid.isosurface_bbox.copy_(torch.stack((self.center - half, self.center + half)))
@@ -348,6 +357,18 @@ class GaussianModel:
         points = scale_tensor(helper.grid_vertices, helper.points_range, grid.isosurface_bbox).contiguous()
         density = self.sample_fields(points, **field_kwargs)["density"]
         grid.sdf.data = (float(density_thresh) - density).clamp(-1, 1).reshape(-1, 1)
+        if feature_steps:
+            vertices = grid.isosurface().v_pos.detach().contiguous()
+            grid.mesh = None
+            if vertices.shape[0]:
+                target = self.sample_fields(vertices, **field_kwargs)["color"]
+                with torch.enable_grad():
+                    optimizer = torch.optim.Adam(list(grid.encoding.parameters()) + list(grid.feature_network.parameters()), lr=feature_lr)
+                    for _ in range(feature_steps):
+                        optimizer.zero_grad()
+                        loss = ((torch.sigmoid(grid(vertices)["features"]) - target) ** 2).mean()
+                        loss.backward()
+                        optimizer.step()
         return grid
 
     @torch.no_grad()

@@ -297,12 +297,20 @@ class TetrahedraSDFGrid(nn.Module):
     """The geometry of the reference's TetrahedraSDFGrid: a signed distance `sdf` [Nv, 1] and a `deformation` [Nv, 3] per vertex of a
     tetrahedral grid as the trainable parameters (buffers with fix_geometry=True; deformation is None with
     isosurface_deformable_grid=False), the buffer isosurface_bbox [2, 3], initialize_shape() for "sphere" and "ellipsoid", and
-    isosurface() -> Mesh in the bbox's coordinates, kept under fix_geometry.  Inside is negative.  The feature network (hash grid and MLP)
-    is out of scope, as is shape_init="mesh:..." (it needs trimesh and pysdf); isosurface_remove_outliers=True raises
-    NotImplementedError, since the project removes small components with utils.mesh.clean_mesh."""
+    isosurface() -> Mesh in the bbox's coordinates, kept under fix_geometry.  Inside is negative.  The feature network is opt-in:
+    with n_feature_dims > 0 the grid also holds `encoding` and `feature_network` (utils/encoding.py get_encoding / get_mlp; the
+    configurations default to the reference's hash grid, 16 levels of 2 features in 2^19 rows, and its 64-neuron VanillaMLP), and
+    forward(points) returns {"features": [..., n_feature_dims]} at points in the bbox's coordinates.  The default n_feature_dims=0 is
+    the geometry alone, and forward then returns {}.  shape_init="mesh:..." is out of scope (it needs trimesh and pysdf);
+    isosurface_remove_outliers=True raises NotImplementedError, since the project removes small components with utils.mesh.clean_mesh."""
+
+    POS_ENCODING_CONFIG = {"otype": "HashGrid", "n_levels": 16, "n_features_per_level": 2, "log2_hashmap_size": 19, "base_resolution": 16,
+                           "per_level_scale": 1.447269237440378}
+    MLP_NETWORK_CONFIG = {"otype": "VanillaMLP", "activation": "ReLU", "output_activation": "none", "n_neurons": 64, "n_hidden_layers": 1}
 
     def __init__(self, isosurface_resolution=128, isosurface_deformable_grid=True, isosurface_remove_outliers=False, shape_init=None,
-                 shape_init_params=None, fix_geometry=False, radius=1.0, tets_path=None):
+                 shape_init_params=None, fix_geometry=False, radius=1.0, tets_path=None, n_feature_dims=0, pos_encoding_config=None,
+                 mlp_network_config=None):
         super().__init__()
         if isosurface_remove_outliers:
             raise NotImplementedError("TetrahedraSDFGrid: isosurface_remove_outliers is not offered inside isosurface(); pass the mesh "
@@ -324,7 +332,27 @@ class TetrahedraSDFGrid(nn.Module):
                 self.register_buffer("deformation", deformation)
             else:
                 self.deformation = None
+        self.n_feature_dims = int(n_feature_dims)
+        if self.n_feature_dims < 0:
+            raise ValueError("n_feature_dims must not be negative")
+        if self.n_feature_dims > 0:
+            from .encoding import get_encoding, get_mlp
+            self.encoding = get_encoding(3, dict(self.POS_ENCODING_CONFIG if pos_encoding_config is None else pos_encoding_config))
+            self.feature_network = get_mlp(self.encoding.n_output_dims, self.n_feature_dims,
+                                           dict(self.MLP_NETWORK_CONFIG if mlp_network_config is None else mlp_network_config))
         self.mesh = None
+
+    def forward(self, points, output_normal=False):
+        """{"features": [..., n_feature_dims]} at points [..., 3] in the bbox's coordinates: the points scaled to [0, 1] by
+        isosurface_bbox (the reference's contract_to_unisphere without the unbounded mode), encoded, and through the MLP.  {} for a
+        grid without a feature network."""
+        if self.n_feature_dims == 0:
+            return {}
+        if output_normal:
+            raise NotImplementedError("TetrahedraSDFGrid: a normal output is not supported, as in the reference")
+        unit = scale_tensor(points, self.isosurface_bbox, (0, 1))
+        enc = self.encoding(unit.reshape(-1, 3))
+        return {"features": self.feature_network(enc).view(*points.shape[:-1], self.n_feature_dims)}
 
     def initialize_shape(self):
         """sdf = the distance of shape_init at the grid's vertices in the bbox's coordinates: "sphere" with a radius (a float),

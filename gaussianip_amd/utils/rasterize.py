@@ -22,6 +22,9 @@ render_mesh stays bilinear: the baked atlas gives every face its own cell, and a
 
 The regularisers that a loss on render_mesh(position_gradients=True) needs beside it (vertex normals, Laplacian, normal consistency) are
 in utils/mesh_geometry.py (csrc/mesh_geom.hip).
+
+render_field_mesh draws a geometry that carries a feature network (utils/isosurface.py TetrahedraSDFGrid with n_feature_dims=3, whose
+colour is a hash-grid encoding and an MLP: utils/encoding.py) the way the reference's nvdiff-rasterizer does.
 """
 import ctypes
 
@@ -30,7 +33,8 @@ import torch
 from .. import _lib
 from .._lib import call_model, ptr
 
-__all__ = ["MeshRasterizerContext", "DiffMeshRasterizerContext", "MipMeshRasterizerContext", "MipStack", "edge_topology", "render_mesh"]
+__all__ = ["MeshRasterizerContext", "DiffMeshRasterizerContext", "MipMeshRasterizerContext", "MipStack", "edge_topology", "render_mesh",
+           "render_field_mesh"]
 
 
 _MAX_SIDE = 16384             # of an image or a texture: the library's MR_MAX_SIZE
@@ -699,3 +703,52 @@ def render_mesh(camera, vertices, faces, uv, texture, bg_color=None, cull_backfa
     out = {"image": shaded[..., :3].permute(0, 3, 1, 2), "alpha": shaded[..., 3:].permute(0, 3, 1, 2),
            "depth": rast[..., 2:3].permute(0, 3, 1, 2), "rast": rast}
     return out if many else {k: v[0] for k, v in out.items()}
+
+
+def render_field_mesh(ctx, geometry, mvp_mtx, camera_positions, height, width, bg_color=None):
+    """{"opacity": [B, H, W, 1], "comp_normal": [B, H, W, 3], "comp_rgb": [B, H, W, 3], "mesh": Mesh}: the forward of the reference's
+    NVDiffRasterizer (threestudio/models/renderers/nvdiff_rasterizer.py) for a geometry with a feature network
+    (utils.isosurface.TetrahedraSDFGrid with n_feature_dims=3), its no-material (colour = sigmoid(features)) and a solid background.
+    geometry.isosurface() is extracted, transformed by mvp_mtx [B, 4, 4] (column-vector convention) and rasterized at (height, width);
+    the coverage mask and the normals (in [0, 1]) are antialiased; the surface position of every covered pixel is interpolated from
+    the vertices, geometry(positions) is evaluated there, and the colour, laid over bg_color [3] (black by default), is antialiased.
+    ctx is a DiffMeshRasterizerContext: gradients reach the feature network through the colour, and the signed distance and the
+    deformation through the positions the features are looked up at and through the antialiased silhouette.  camera_positions [B, 3]
+    is the reference's argument; without a view-dependent material nothing reads it.  One host synchronisation (the covered pixels
+    are gathered with a mask), as in the reference."""
+    if not isinstance(ctx, DiffMeshRasterizerContext):
+        raise ValueError("render_field_mesh needs a DiffMeshRasterizerContext (antialias and gradients to positions)")
+    if not (_is_gpu_float(mvp_mtx) and mvp_mtx.dim() == 3 and tuple(mvp_mtx.shape[1:]) == (4, 4)):
+        raise ValueError("mvp_mtx must be a [B, 4, 4] float32 GPU tensor")
+    B = int(mvp_mtx.shape[0])
+    if camera_positions is not None and tuple(camera_positions.shape) != (B, 3):
+        raise ValueError("camera_positions must be [B, 3]")
+    H, W = _resolution((height, width))
+    dev = mvp_mtx.device
+    if bg_color is None:
+        bg = torch.zeros(3, dtype=torch.float32, device=dev)
+    else:
+        bg = torch.as_tensor(bg_color, dtype=torch.float32).to(dev).reshape(-1)
+        if bg.numel() != 3:
+            raise ValueError("bg_color must have 3 values")
+    mesh = geometry.isosurface()
+    if mesh.t_pos_idx.shape[0] == 0:
+        raise ValueError("render_field_mesh: the geometry's surface is empty")
+    v_pos_clip = ctx.vertex_transform(mesh.v_pos, mvp_mtx).contiguous()
+    rast, _ = ctx.rasterize(v_pos_clip, mesh.t_pos_idx, (H, W))
+    mask = rast[..., 3:] > 0
+    mask_f = mask.float()
+    out = {"opacity": ctx.antialias(mask_f, rast, v_pos_clip, mesh.t_pos_idx), "mesh": mesh}
+    gb_normal, _ = ctx.interpolate_one(mesh.v_nrm, rast, mesh.t_pos_idx)
+    gb_normal = torch.nn.functional.normalize(gb_normal, dim=-1)
+    gb_normal_aa = torch.lerp(torch.zeros_like(gb_normal), (gb_normal + 1.0) / 2.0, mask_f)
+    out["comp_normal"] = ctx.antialias(gb_normal_aa.contiguous(), rast, v_pos_clip, mesh.t_pos_idx)
+    selector = mask[..., 0]
+    gb_pos, _ = ctx.interpolate_one(mesh.v_pos, rast, mesh.t_pos_idx)
+    positions = gb_pos[selector]
+    rgb_fg = torch.sigmoid(geometry(positions)["features"][..., :3]).float()
+    gb_rgb_fg = torch.zeros((B, H, W, 3), dtype=rgb_fg.dtype, device=dev)
+    gb_rgb_fg[selector] = rgb_fg
+    gb_rgb = torch.lerp(bg.expand(B, H, W, 3), gb_rgb_fg, mask_f)
+    out["comp_rgb"] = ctx.antialias(gb_rgb.contiguous(), rast, v_pos_clip, mesh.t_pos_idx)
+    return out

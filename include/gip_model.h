@@ -439,6 +439,28 @@ int gip_tet_sdf_diff(const float* sdf, const int32_t* edges, int64_t Nv, int64_t
                      size_t workspace_bytes, void* stream);
 int gip_tet_sdf_diff_backward(const float* sdf, const int32_t* edges, const int32_t* vert_edge_start, const int32_t* vert_edge_list,
                               const int32_t* count, const float* g_loss, int64_t Nv, int64_t Ne, float* g_sdf, void* stream);
+/* A multiresolution hash-grid encoding of 3-D points, forward and both backward passes (csrc/hashgrid.hip, whose header states the
+ * definition; gaussianip_amd/utils/encoding.py HashGridLayout, hash_grid_encode).  x [N, 3], table [P, F], enc and g_enc [N, L F]
+ * (level-major), g_x [N, 3], g_table [P, F]: float32 on the device; table, enc and g_enc aligned to min(4 F, 16) bytes.  The level table
+ * is five HOST arrays of L entries: level_scale (float32), level_res, level_size (rows of the level's slice, 1 .. 2^24), level_offset
+ * (int64, the running sum of the sizes, which must total P) and level_hashed (0: dense rows, else hashed rows).
+ *   gip_hashgrid_forward         enc; no atomics, bitwise reproducible.
+ *   gip_hashgrid_backward_input  g_x, a gather over the same walk; no atomics, bitwise reproducible.
+ *   gip_hashgrid_backward_table  ADDS into g_table, which the caller zeroed, with float atomic adds: the one output that is not bitwise
+ *       reproducible from run to run.
+ * Status 1: a NULL required pointer, L outside 1 .. 32, F not 1, 2, 4 or 8, N < 0, 4 N L F above 2^32 - 1, a level whose scale is not
+ * finite, whose res is below 1 or whose size is outside 1 .. 2^24, offsets that are not the running sum, sizes that do not total P, a
+ * misaligned table, enc or g_enc; a call that fails so launches nothing.  N == 0 is a success that launches nothing (the level table is
+ * still checked).  Status 3: a launch error. */
+int gip_hashgrid_forward(const float* x, const float* table, const float* level_scale, const int32_t* level_res, const int32_t* level_size,
+                         const int64_t* level_offset, const int32_t* level_hashed, int64_t N, int32_t L, int32_t F, int64_t P, float* enc,
+                         void* stream);
+int gip_hashgrid_backward_input(const float* x, const float* table, const float* g_enc, const float* level_scale, const int32_t* level_res,
+                                const int32_t* level_size, const int64_t* level_offset, const int32_t* level_hashed, int64_t N, int32_t L,
+                                int32_t F, int64_t P, float* g_x, void* stream);
+int gip_hashgrid_backward_table(const float* x, const float* g_enc, const float* level_scale, const int32_t* level_res,
+                                const int32_t* level_size, const int64_t* level_offset, const int32_t* level_hashed, int64_t N, int32_t L,
+                                int32_t F, int64_t P, float* g_table, void* stream);
 #ifdef __cplusplus
 }
 #endif
