@@ -1,4 +1,11 @@
-"""ctypes binding of libgip_raster.so / libgip_knn.so (the C-ABI declared in include/gip_raster.h, include/gip_knn.h).
+"""ctypes binding of the four HIP libraries: libgip_raster.so (include/gip_raster.h), libgip_knn.so (include/gip_knn.h),
+libgip_model.so (include/gip_model.h: scene, loss, mesh, field, tet and hash-grid kernels) and libgip_nn.so (include/gip_nn.h: the
+denoiser / VAE kernels and the guidance glue).
+
+Host code launches through `call_model`, `call_nn` and `call_knn` (pointers from `ptr`, the device's current stream appended, a
+RuntimeError naming the entry point on a non-zero status) and asks stream-less questions through `query_model`; the rasterizer has
+its own plan-based path in rasterizer.py.  Entry points that return a size or a count, not a status, are called directly on
+`model_lib()` / `nn_lib()` / `knn_lib()`.
 
 The product path has NO CPU fallback: if the HIP library is missing, loading raises ImportError with build
 instructions (`python -c "import __graft_entry__ as g; g.build()"`).
@@ -347,13 +354,45 @@ def ptr(t):
     return ctypes.c_void_p(t.data_ptr() if t is not None and t.numel() else None)
 
 
+def _call(lib, name, args, dev=None, accept=()):
+    """The one place the C-ABI protocol is spelled: entry point `name` of `lib` with args and, when dev is given, dev's current
+    stream as its last argument; RuntimeError naming the entry point unless it returns 0 or a status in `accept`.  Returns the status."""
+    if dev is not None:
+        import torch
+        args += (ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream),)
+    rc = getattr(lib, name)(*args)
+    if rc != 0 and rc not in accept:
+        raise RuntimeError("%s failed with status %d" % (name, rc))
+    return rc
+
+
 def call_model(dev, name, *args):
     """libgip_model.so's entry point `name` with args and, as its last argument, dev's current stream; RuntimeError unless it returns 0."""
     import torch
     with torch.cuda.device(dev):
-        rc = getattr(model_lib(), name)(*args, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    if rc != 0:
-        raise RuntimeError("%s failed with status %d" % (name, rc))
+        _call(model_lib(), name, args, dev)
+
+
+def call_knn(dev, name, *args):
+    """libgip_knn.so's entry point `name`, same contract as call_model (dev selected, its current stream last)."""
+    import torch
+    with torch.cuda.device(dev):
+        _call(knn_lib(), name, args, dev)
+
+
+def query_model(name, *args):
+    """An entry point of libgip_model.so that takes no stream and launches nothing (the *_workspace_size queries,
+    gip_mesh_mip_levels): RuntimeError unless it returns 0."""
+    _call(model_lib(), name, args)
+
+
+def call_nn(dev, name, *args, accept=()):
+    """libgip_nn.so's entry point `name` with args and, as its last argument, dev's current stream; RuntimeError unless it returns 0
+    or a status in `accept` (one the caller handles itself); returns the status.
+    Unlike call_model it does NOT select dev (no torch.cuda.device guard): the denoiser makes several hundred of these calls per
+    eager step, also on side streams and under graph capture, its callers never switched devices around them, and what the guard
+    would cost on that path has not been measured.  The caller runs with the tensors' device current."""
+    return _call(nn_lib(), name, args, dev, accept)
 
 
 _nn = None

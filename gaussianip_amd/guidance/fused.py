@@ -14,6 +14,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import _lib
+from .._lib import call_nn, ptr
 
 _ws = {}
 
@@ -29,52 +30,50 @@ def _workspace(dev, nbytes):
     return w
 
 
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr())
+def _addend_args(addend):
+    """(pointer, row stride) of a GroupNorm addend ([N, C], [1, C] or [C]) for the C-ABI: null and 0 for None; stride 0 when one
+    vector serves every sample."""
+    if addend is None:
+        return ptr(None), 0
+    return ptr(addend), (addend.stride(0) if addend.dim() == 2 and addend.shape[0] > 1 else 0)
+
+
+def _gn_forward(x, weight, bias, groups, eps, act, addend, chan_stats):
+    """(y, mean, rstd) of GroupNorm (+ SiLU) on NHWC fp16 x (+ addend) through the C-ABI (no autograd)."""
+    N, C, H, W = x.shape
+    ad_ptr, ad_stride = _addend_args(addend)
+    y = torch.empty_like(x, memory_format=torch.channels_last)
+    mean = torch.empty((N, groups), dtype=torch.float32, device=x.device)
+    rstd = torch.empty_like(mean)
+    if chan_stats is not None:
+        # the producer of x (MFMA convolution / linear epilogue) already summed x per 128-row block and channel
+        call_nn(x.device, "gip_gn_silu_forward_stats", ptr(x), ptr(weight), ptr(bias), ptr(y), ptr(mean), ptr(rstd), N, H * W, C, groups,
+                float(eps), int(act), ad_ptr, ad_stride, ptr(chan_stats), chan_stats.shape[0] // N)
+    else:
+        ws = _workspace(x.device, _lib.nn_lib().gip_gn_workspace_bytes(N, groups))
+        call_nn(x.device, "gip_gn_silu_forward", ptr(x), ptr(weight), ptr(bias), ptr(y), ptr(mean), ptr(rstd), N, H * W, C, groups,
+                float(eps), int(act), ad_ptr, ad_stride, ptr(ws), ws.numel())
+    return y, mean, rstd
 
 
 class _FusedGN(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, groups, eps, act, addend, chan_stats=None):
-        N, C, H, W = x.shape
-        ad_ptr, ad_stride = ctypes.c_void_p(None), 0
-        if addend is not None:
-            ad_ptr, ad_stride = _p(addend), (addend.stride(0) if addend.dim() == 2 and addend.shape[0] > 1 else 0)
-        lib = _lib.nn_lib()
-        y = torch.empty_like(x, memory_format=torch.channels_last)
-        mean = torch.empty((N, groups), dtype=torch.float32, device=x.device)
-        rstd = torch.empty_like(mean)
-        stream = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-        if chan_stats is not None:
-            # the producer of x (MFMA convolution / linear epilogue) already summed x per 128-row block and channel
-            rc = lib.gip_gn_silu_forward_stats(_p(x), _p(weight), _p(bias), _p(y), _p(mean), _p(rstd), N, H * W, C, groups,
-                                               float(eps), int(act), ad_ptr, ad_stride, _p(chan_stats), chan_stats.shape[0] // N, stream)
-        else:
-            nb = lib.gip_gn_workspace_bytes(N, groups)
-            ws = _workspace(x.device, nb)
-            rc = lib.gip_gn_silu_forward(_p(x), _p(weight), _p(bias), _p(y), _p(mean), _p(rstd), N, H * W, C, groups,
-                                         float(eps), int(act), ad_ptr, ad_stride, _p(ws), ws.numel(), stream)
-        if rc != 0:
-            raise RuntimeError("gip_gn_silu_forward failed with status %d" % rc)
+        y, mean, rstd = _gn_forward(x, weight, bias, groups, eps, act, addend, chan_stats)
         ctx.save_for_backward(x, weight, bias, mean, rstd, addend)
-        ctx.groups, ctx.act, ctx.ad_stride = groups, act, ad_stride
+        ctx.groups, ctx.act = groups, act
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, weight, bias, mean, rstd, addend = ctx.saved_tensors
-        ad_ptr = ctypes.c_void_p(None) if addend is None else _p(addend)
+        ad_ptr, ad_stride = _addend_args(addend)
         N, C, H, W = x.shape
-        lib = _lib.nn_lib()
         dy = dy.contiguous(memory_format=torch.channels_last)
         dx = torch.empty_like(x, memory_format=torch.channels_last)
-        nb = lib.gip_gn_workspace_bytes(N, ctx.groups)
-        ws = _workspace(x.device, nb)
-        rc = lib.gip_gn_silu_backward(_p(x), _p(dy), _p(weight), _p(bias), _p(mean), _p(rstd), _p(dx), N, H * W, C,
-                                      ctx.groups, int(ctx.act), ad_ptr, ctx.ad_stride, _p(ws), ws.numel(),
-                                      ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream))
-        if rc != 0:
-            raise RuntimeError("gip_gn_silu_backward failed with status %d" % rc)
+        ws = _workspace(x.device, _lib.nn_lib().gip_gn_workspace_bytes(N, ctx.groups))
+        call_nn(x.device, "gip_gn_silu_backward", ptr(x), ptr(dy), ptr(weight), ptr(bias), ptr(mean), ptr(rstd), ptr(dx), N, H * W, C,
+                ctx.groups, int(ctx.act), ad_ptr, ad_stride, ptr(ws), ws.numel())
         return dx, None, None, None, None, None, None, None
 
 
@@ -229,10 +228,7 @@ class _AddBiasResidual(torch.autograd.Function):
     def forward(ctx, a, b, bias):
         N, C, H, W = a.shape
         out = torch.empty_like(a, memory_format=torch.channels_last)
-        rc = _lib.nn_lib().gip_add_bias_residual(_p(a), _p(b), ctypes.c_void_p(None) if bias is None else _p(bias), _p(out),
-                                                 N * H * W, C, ctypes.c_void_p(torch.cuda.current_stream(a.device).cuda_stream))
-        if rc != 0:
-            raise RuntimeError("gip_add_bias_residual failed with status %d" % rc)
+        call_nn(a.device, "gip_add_bias_residual", ptr(a), ptr(b), ptr(bias), ptr(out), N * H * W, C)
         return out
 
     @staticmethod
@@ -261,12 +257,7 @@ def cat_skip(h, skip, residual=None):
         out = torch.empty((N, Ca + Cb, H, W), dtype=h.dtype, device=h.device, memory_format=torch.channels_last)
         want = (H * W) % 128 == 0 and (Ca + Cb) // 32 <= 256 and os.environ.get("GIP_GN_STATS", "1") != "0"
         st = torch.empty((N * H * W // 128, Ca + Cb, 2), dtype=torch.float32, device=h.device) if want else None
-        null = ctypes.c_void_p(None)
-        rc = _lib.nn_lib().gip_cat2_stats_f16(_p(h), _p(skip), null if residual is None else _p(residual), _p(out),
-                                              null if st is None else _p(st), N * H * W, Ca, Cb,
-                                              ctypes.c_void_p(torch.cuda.current_stream(h.device).cuda_stream))
-        if rc != 0:
-            raise RuntimeError("gip_cat2_stats_f16 failed with status %d" % rc)
+        call_nn(h.device, "gip_cat2_stats_f16", ptr(h), ptr(skip), ptr(residual), ptr(out), ptr(st), N * H * W, Ca, Cb)
         return attach_stats(out, st)
     return torch.cat([h, skip if residual is None else skip + residual], dim=1)
 
@@ -276,10 +267,7 @@ def geglu(x):
     D = x.shape[-1] // 2
     if not _DISABLED and x.is_cuda and x.dtype == torch.float16 and x.is_contiguous() and D % 8 == 0 and not (x.requires_grad and torch.is_grad_enabled()):
         out = torch.empty(x.shape[:-1] + (D,), dtype=x.dtype, device=x.device)
-        rc = _lib.nn_lib().gip_geglu(_p(x), _p(out), x.numel() // (2 * D), D,
-                                     ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream))
-        if rc != 0:
-            raise RuntimeError("gip_geglu failed with status %d" % rc)
+        call_nn(x.device, "gip_geglu", ptr(x), ptr(out), x.numel() // (2 * D), D)
         return out
     a, g = x.chunk(2, dim=-1)
     return a * F.gelu(g)
@@ -296,10 +284,7 @@ class LayerNorm(nn.LayerNorm):
                 C % 8 == 0 and C <= 2048 and x.numel() > 0 and
                 not (torch.is_grad_enabled() and (x.requires_grad or self.weight.requires_grad))):
             out = torch.empty_like(x)
-            rc = _lib.nn_lib().gip_layernorm_f16(_p(x), _p(self.weight), _p(self.bias), _p(out), x.numel() // C, C,
-                                                 float(self.eps), ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream))
-            if rc != 0:
-                raise RuntimeError("gip_layernorm_f16 failed with status %d" % rc)
+            call_nn(x.device, "gip_layernorm_f16", ptr(x), ptr(self.weight), ptr(self.bias), ptr(out), x.numel() // C, C, float(self.eps))
             return out
         fallback("LayerNorm", x)
         return super().forward(x)
@@ -408,26 +393,16 @@ def _conv_call(x, w, cout, bias=None, residual=None, stats=None):
     """`stats`: a list that receives the output's chan_stats tensor (see producer_stats) when the shape qualifies."""
     N, C, H, W = x.shape
     out = torch.empty((N, cout, H, W), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
-    null = ctypes.c_void_p(None)
     rows = _stats_rows(N, H, W, C, cout) if stats is not None else 0
+    ws = _workspace(x.device, _SPLITK_WS_BYTES) if _conv_tiles(N, H, W, cout) < 256 else None
     if rows:
         st = torch.empty((N * H * W // rows, cout, 2), dtype=torch.float32, device=x.device)
-        ws = _workspace(x.device, _SPLITK_WS_BYTES) if _conv_tiles(N, H, W, cout) < 256 else None
-        rc = _lib.nn_lib().gip_conv3x3_stats_ws_nhwc_f16(_p(x), _p(w), null if bias is None else _p(bias),
-                                                         null if residual is None else _p(residual), _p(out), N, H, W, C, cout,
-                                                         _p(st), rows, null if ws is None else _p(ws), 0 if ws is None else ws.numel(),
-                                                         ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream))
-        if rc != 0:
-            raise RuntimeError("gip_conv3x3_stats_ws_nhwc_f16 failed with status %d" % rc)
+        call_nn(x.device, "gip_conv3x3_stats_ws_nhwc_f16", ptr(x), ptr(w), ptr(bias), ptr(residual), ptr(out), N, H, W, C, cout,
+                ptr(st), rows, ptr(ws), 0 if ws is None else ws.numel())
         stats.append(st)
         return out
-    ws = _workspace(x.device, _SPLITK_WS_BYTES) if _conv_tiles(N, H, W, cout) < 256 else None
-    rc = _lib.nn_lib().gip_conv3x3_nhwc_f16(_p(x), _p(w), null if bias is None else _p(bias),
-                                            null if residual is None else _p(residual), _p(out), N, H, W, C, cout,
-                                            null if ws is None else _p(ws), 0 if ws is None else ws.numel(),
-                                            ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream))
-    if rc != 0:
-        raise RuntimeError("gip_conv3x3_nhwc_f16 failed with status %d" % rc)
+    call_nn(x.device, "gip_conv3x3_nhwc_f16", ptr(x), ptr(w), ptr(bias), ptr(residual), ptr(out), N, H, W, C, cout,
+            ptr(ws), 0 if ws is None else ws.numel())
     return out
 
 
@@ -515,50 +490,36 @@ def _winograd_conv(x, w, bias, residual, stats=None, gn_in=None):
     N, C, H, W = x.shape
     cout = w.shape[0]
     T = N * (H // 2) * (W // 2)
-    lib = _lib.nn_lib()
-    stream = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-    V = torch.empty((16, T, C), dtype=x.dtype, device=x.device)
+    dev = x.device
+    V = torch.empty((16, T, C), dtype=x.dtype, device=dev)
     if gn_in is None:
-        rc = lib.gip_winograd_input_f16(_p(x), _p(V), N, H, W, C, stream)
+        call_nn(dev, "gip_winograd_input_f16", ptr(x), ptr(V), N, H, W, C)
     else:
         gn, addend, chan_stats = gn_in
-        ad_ptr, ad_stride = ctypes.c_void_p(None), 0
-        if addend is not None:
-            ad_ptr, ad_stride = _p(addend), (addend.stride(0) if addend.dim() == 2 and addend.shape[0] > 1 else 0)
-        mean = torch.empty((N, gn.num_groups), dtype=torch.float32, device=x.device)
+        ad_ptr, ad_stride = _addend_args(addend)
+        mean = torch.empty((N, gn.num_groups), dtype=torch.float32, device=dev)
         rstd = torch.empty_like(mean)
-        rc = lib.gip_gn_stats_from_partials(_p(mean), _p(rstd), N, H * W, C, gn.num_groups, float(gn.eps), ad_ptr, ad_stride, _p(chan_stats),
-                                            chan_stats.shape[0] // N, stream)
-        if rc != 0:
-            raise RuntimeError("gip_gn_stats_from_partials failed with status %d" % rc)
-        rc = lib.gip_winograd_input_gn_f16(_p(x), _p(V), N, H, W, C, _p(gn.weight), _p(gn.bias), _p(mean), _p(rstd), gn.num_groups, int(gn.act),
-                                           ad_ptr, ad_stride, stream)
-    if rc != 0:
-        raise RuntimeError("gip_winograd_input_f16 failed with status %d" % rc)
+        call_nn(dev, "gip_gn_stats_from_partials", ptr(mean), ptr(rstd), N, H * W, C, gn.num_groups, float(gn.eps), ad_ptr, ad_stride,
+                ptr(chan_stats), chan_stats.shape[0] // N)
+        call_nn(dev, "gip_winograd_input_gn_f16", ptr(x), ptr(V), N, H, W, C, ptr(gn.weight), ptr(gn.bias), ptr(mean), ptr(rstd),
+                gn.num_groups, int(gn.act), ad_ptr, ad_stride)
     U = _wt_cache.get("wino", w, _winograd_weight)
     if _winograd_gemm_own(C, cout) and C % 64 == 0 and cout % 4 == 0 and T * max(C, cout) * 2 < (1 << 31):
         # the sixteen products in ONE launch of this repo's MFMA GEMM (blockIdx.y = product): gip_linear_batched_f16
-        M = torch.empty((16, T, cout), dtype=x.dtype, device=x.device)
-        rc = lib.gip_linear_batched_f16(_p(V), _p(U), _p(M), 16, T, C, cout, T * C, cout * C, T * cout, stream)
-        if rc != 0:
-            raise RuntimeError("gip_linear_batched_f16 failed with status %d" % rc)
+        M = torch.empty((16, T, cout), dtype=x.dtype, device=dev)
+        call_nn(dev, "gip_linear_batched_f16", ptr(V), ptr(U), ptr(M), 16, T, C, cout, T * C, cout * C, T * cout)
     else:
         fallback("winograd batched GEMM", V, library=True)
         M = torch.bmm(V, U.transpose(1, 2))          # sixteen GEMMs: one batched library call
-    out = torch.empty((N, cout, H, W), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
-    null = ctypes.c_void_p(None)
+    out = torch.empty((N, cout, H, W), dtype=x.dtype, device=dev, memory_format=torch.channels_last)
     if W in (16, 32) and (H * W) % 128 == 0:
         st = None
         if stats is not None and cout // 32 <= 256 and os.environ.get("GIP_GN_STATS", "1") != "0":
-            st = torch.empty((N * H * W // 128, cout, 2), dtype=torch.float32, device=x.device)
+            st = torch.empty((N * H * W // 128, cout, 2), dtype=torch.float32, device=dev)
             stats.append(st)
-        rc = lib.gip_winograd_output_stats_f16(_p(M), null if bias is None else _p(bias), null if residual is None else _p(residual),
-                                               _p(out), null if st is None else _p(st), N, H, W, cout, stream)
+        call_nn(dev, "gip_winograd_output_stats_f16", ptr(M), ptr(bias), ptr(residual), ptr(out), ptr(st), N, H, W, cout)
     else:
-        rc = lib.gip_winograd_output_f16(_p(M), null if bias is None else _p(bias), null if residual is None else _p(residual), _p(out),
-                                         N, H, W, cout, stream)
-    if rc != 0:
-        raise RuntimeError("gip_winograd_output_f16 failed with status %d" % rc)
+        call_nn(dev, "gip_winograd_output_f16", ptr(M), ptr(bias), ptr(residual), ptr(out), N, H, W, cout)
     return out
 
 
@@ -653,7 +614,6 @@ def attention(q, k, v, heads, k2=None, v2=None, weight2=1.0):
     ld_q = _kv_rows(q)                     # q may be a column range of a fused q | k | v projection (row stride 3 C)
     if ld_q is None:
         q, ld_q = q.contiguous(), C
-    null = ctypes.c_void_p(None)
     two = k2 is not None
 
     def pair(a, b):
@@ -666,12 +626,11 @@ def attention(q, k, v, heads, k2=None, v2=None, weight2=1.0):
     ld2 = C
     if two:
         k2, v2, ld2 = pair(k2, v2)
-    rc = _lib.nn_lib().gip_attention_fwd_strided2_f16(_p(q), _p(k), _p(v), _p(o), B, heads, Nq, k.shape[1], D, float(D) ** -0.5,
-                                                     _p(k2) if two else null, _p(v2) if two else null,
-                                                     k2.shape[1] if two else 0, float(weight2), ld_q, ld, ld2,
-                                                     ctypes.c_void_p(torch.cuda.current_stream(q.device).cuda_stream))
-    if rc != 0:
-        raise RuntimeError("gip_attention_fwd_strided2_f16 failed with status %d" % rc)
+    # the second pair goes by address, not through ptr(): null means "no second set" to the entry point, which rejects a set of
+    # zero keys — ptr() would turn an empty k2 / v2 into exactly that null
+    call_nn(q.device, "gip_attention_fwd_strided2_f16", ptr(q), ptr(k), ptr(v), ptr(o), B, heads, Nq, k.shape[1], D, float(D) ** -0.5,
+            ctypes.c_void_p(k2.data_ptr() if two else None), ctypes.c_void_p(v2.data_ptr() if two else None),
+            k2.shape[1] if two else 0, float(weight2), ld_q, ld, ld2)
     return o
 
 
@@ -687,10 +646,7 @@ class _WideHeadAttention(torch.autograd.Function):
         scale = float(q.shape[-1]) ** -0.5
         fallback("VAE mid attention (dense GEMMs around the own softmax kernels)", q, library=True)
         p = torch.bmm(q, k.transpose(1, 2))                       # raw scores [B, N, N]; becomes P in place
-        rc = _lib.nn_lib().gip_softmax_rows_f16(_p(p), p.shape[0] * p.shape[1], p.shape[2], scale,
-                                                ctypes.c_void_p(torch.cuda.current_stream(q.device).cuda_stream))
-        if rc != 0:
-            raise RuntimeError("gip_softmax_rows_f16 failed with status %d" % rc)
+        call_nn(q.device, "gip_softmax_rows_f16", ptr(p), p.shape[0] * p.shape[1], p.shape[2], scale)
         ctx.save_for_backward(q, k, v, p)
         ctx.scale = scale
         return torch.bmm(p, v)
@@ -704,10 +660,7 @@ class _WideHeadAttention(torch.autograd.Function):
         # the 1 / sqrt(D) factor is NOT folded into the half-rounded score gradient (P (dP - sum dP P) is ~1e-4 dP already: times
         # 0.044 it would sink into fp16's subnormals — measured: dL/dimage 2.6e-3 -> 5.6e-3 from fp32 at loss scale 1); it rides as
         # the float32 alpha of the two products that consume it
-        rc = _lib.nn_lib().gip_softmax_rows_backward_f16(_p(p), _p(dp), p.shape[0] * p.shape[1], p.shape[2], 1.0,
-                                                         ctypes.c_void_p(torch.cuda.current_stream(q.device).cuda_stream))
-        if rc != 0:
-            raise RuntimeError("gip_softmax_rows_backward_f16 failed with status %d" % rc)
+        call_nn(q.device, "gip_softmax_rows_backward_f16", ptr(p), ptr(dp), p.shape[0] * p.shape[1], p.shape[2], 1.0)
         dq = torch.baddbmm(q, dp, k, beta=0.0, alpha=ctx.scale)
         dk = torch.baddbmm(k, dp.transpose(1, 2), q, beta=0.0, alpha=ctx.scale)
         return dq, dk, dv
@@ -771,10 +724,8 @@ def linear_ln(x, norm, w, bias=None, geglu_act=False):
         return None
     wg, s_vec, t_vec = _ln_fold_weights(norm, w, bias)
     out = torch.empty(x.shape[:-1] + (n_out,), dtype=x.dtype, device=x.device)
-    rc = _lib.nn_lib().gip_linear_ln_f16(_p(x), _p(wg), _p(s_vec), _p(t_vec), _p(out), M, K, n_out, int(geglu_act), _p(rows), rows.shape[1],
-                                         float(norm.eps), ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream))
-    if rc != 0:
-        raise RuntimeError("gip_linear_ln_f16 failed with status %d" % rc)
+    call_nn(x.device, "gip_linear_ln_f16", ptr(x), ptr(wg), ptr(s_vec), ptr(t_vec), ptr(out), M, K, n_out, int(geglu_act), ptr(rows),
+            rows.shape[1], float(norm.eps))
     return out
 
 
@@ -838,31 +789,18 @@ def linear(x, w, bias=None, residual=None, geglu_act=False, stats=None, rows=Non
     if linear_supported(x, w) and n_out % (64 if geglu_act else 4) == 0 and (residual is None or residual.is_contiguous()):
         M = x.numel() // x.shape[-1]
         out = torch.empty(x.shape[:-1] + (n_out,), dtype=x.dtype, device=x.device)
-        null = ctypes.c_void_p(None)
         if rows is not None and not geglu_act and stats is None and n_out % 8 == 0:
             # `rows`: a list that receives the per-row (sum, sum of squares) partials of the output [M, parts, 2]
-            lib = _lib.nn_lib()
-            rt = torch.empty((M, lib.gip_linear_row_parts(M, n_out), 2), dtype=torch.float32, device=x.device)
-            rc = lib.gip_linear_rows_f16(_p(x), _p(w), null if bias is None else _p(bias), null if residual is None else _p(residual), _p(out),
-                                         M, x.shape[-1], n_out, _p(rt), ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream))
-            if rc != 0:
-                raise RuntimeError("gip_linear_rows_f16 failed with status %d" % rc)
+            rt = torch.empty((M, _lib.nn_lib().gip_linear_row_parts(M, n_out), 2), dtype=torch.float32, device=x.device)
+            call_nn(x.device, "gip_linear_rows_f16", ptr(x), ptr(w), ptr(bias), ptr(residual), ptr(out), M, x.shape[-1], n_out, ptr(rt))
             rows.append(rt)
             return out
         if stats is not None and not geglu_act and M % 128 == 0 and n_out % 8 == 0 and os.environ.get("GIP_GN_STATS", "1") != "0":
             st = torch.empty((M // 128, n_out, 2), dtype=torch.float32, device=x.device)
-            rc = _lib.nn_lib().gip_linear_stats_f16(_p(x), _p(w), null if bias is None else _p(bias),
-                                                    null if residual is None else _p(residual), _p(out), M, x.shape[-1], n_out, _p(st),
-                                                    ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream))
-            if rc != 0:
-                raise RuntimeError("gip_linear_stats_f16 failed with status %d" % rc)
+            call_nn(x.device, "gip_linear_stats_f16", ptr(x), ptr(w), ptr(bias), ptr(residual), ptr(out), M, x.shape[-1], n_out, ptr(st))
             stats.append(st)
             return out
-        rc = _lib.nn_lib().gip_linear_f16(_p(x), _p(w), null if bias is None else _p(bias), null if residual is None else _p(residual),
-                                          _p(out), M, x.shape[-1], n_out, int(geglu_act),
-                                          ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream))
-        if rc != 0:
-            raise RuntimeError("gip_linear_f16 failed with status %d" % rc)
+        call_nn(x.device, "gip_linear_f16", ptr(x), ptr(w), ptr(bias), ptr(residual), ptr(out), M, x.shape[-1], n_out, int(geglu_act))
         return out
     fallback("linear", x)
     y = F.linear(x, w, bias)
@@ -876,25 +814,7 @@ def linear(x, w, bias=None, residual=None, geglu_act=False, stats=None, rows=Non
 # ---------------------------------------------------------------------------------------------------------------------
 def _gn_fwd_raw(x, gn, addend, chan_stats):
     """(y, mean, rstd) of GroupNormAct `gn` on NHWC fp16 x through the C-ABI (no autograd)."""
-    N, C, H, W = x.shape
-    lib = _lib.nn_lib()
-    ad_ptr, ad_stride = ctypes.c_void_p(None), 0
-    if addend is not None:
-        ad_ptr, ad_stride = _p(addend), (addend.stride(0) if addend.dim() == 2 and addend.shape[0] > 1 else 0)
-    y = torch.empty_like(x, memory_format=torch.channels_last)
-    mean = torch.empty((N, gn.num_groups), dtype=torch.float32, device=x.device)
-    rstd = torch.empty_like(mean)
-    stream = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-    if chan_stats is not None:
-        rc = lib.gip_gn_silu_forward_stats(_p(x), _p(gn.weight), _p(gn.bias), _p(y), _p(mean), _p(rstd), N, H * W, C, gn.num_groups,
-                                           float(gn.eps), int(gn.act), ad_ptr, ad_stride, _p(chan_stats), chan_stats.shape[0] // N, stream)
-    else:
-        ws = _workspace(x.device, lib.gip_gn_workspace_bytes(N, gn.num_groups))
-        rc = lib.gip_gn_silu_forward(_p(x), _p(gn.weight), _p(gn.bias), _p(y), _p(mean), _p(rstd), N, H * W, C, gn.num_groups,
-                                     float(gn.eps), int(gn.act), ad_ptr, ad_stride, _p(ws), ws.numel(), stream)
-    if rc != 0:
-        raise RuntimeError("GroupNorm forward failed with status %d" % rc)
-    return y, mean, rstd
+    return _gn_forward(x, gn.weight, gn.bias, gn.num_groups, gn.eps, gn.act, addend, chan_stats)
 
 
 def _conv_gn_in(x, gn, addend, chan_stats, w, bias, residual, stats):
@@ -909,29 +829,18 @@ def _conv_gn_in(x, gn, addend, chan_stats, w, bias, residual, stats):
             _conv_tiles(N, H, W, cout) < 256 or os.environ.get("GIP_CONV_GNIN", "1") == "0" or
             x.numel() * 2 >= (1 << 31) or N * H * W * cout * 2 >= (1 << 31)):
         return None
-    lib = _lib.nn_lib()
-    stream = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-    null = ctypes.c_void_p(None)
-    ad_ptr, ad_stride = null, 0
-    if addend is not None:
-        ad_ptr, ad_stride = _p(addend), (addend.stride(0) if addend.dim() == 2 and addend.shape[0] > 1 else 0)
+    ad_ptr, ad_stride = _addend_args(addend)
     mean = torch.empty((N, gn.num_groups), dtype=torch.float32, device=x.device)
     rstd = torch.empty_like(mean)
-    rc = lib.gip_gn_stats_from_partials(_p(mean), _p(rstd), N, H * W, C, gn.num_groups, float(gn.eps), ad_ptr, ad_stride, _p(chan_stats),
-                                        chan_stats.shape[0] // N, stream)
-    if rc != 0:
-        raise RuntimeError("gip_gn_stats_from_partials failed with status %d" % rc)
+    call_nn(x.device, "gip_gn_stats_from_partials", ptr(mean), ptr(rstd), N, H * W, C, gn.num_groups, float(gn.eps), ad_ptr, ad_stride,
+            ptr(chan_stats), chan_stats.shape[0] // N)
     out = torch.empty((N, cout, H, W), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
     st = None
     if stats is not None and stats_wanted(N, H, W, cout):
         st = torch.empty((N * H * W // 128, cout, 2), dtype=torch.float32, device=x.device)
-    rc = lib.gip_conv3x3_gnin_nhwc_f16(_p(x), _p(w), null if bias is None else _p(bias), null if residual is None else _p(residual), _p(out),
-                                       N, H, W, C, cout, _p(gn.weight), _p(gn.bias), _p(mean), _p(rstd), gn.num_groups, int(gn.act),
-                                       ad_ptr, ad_stride, null if st is None else _p(st), stream)
-    if rc == 1:
+    if call_nn(x.device, "gip_conv3x3_gnin_nhwc_f16", ptr(x), ptr(w), ptr(bias), ptr(residual), ptr(out), N, H, W, C, cout, ptr(gn.weight),
+               ptr(gn.bias), ptr(mean), ptr(rstd), gn.num_groups, int(gn.act), ad_ptr, ad_stride, ptr(st), accept=(1,)) == 1:
         return None                      # a shape the halo kernel does not take after all
-    if rc != 0:
-        raise RuntimeError("gip_conv3x3_gnin_nhwc_f16 failed with status %d" % rc)
     if st is not None:
         stats.append(st)
     return out, mean, rstd
@@ -952,40 +861,26 @@ def _dgrad_with_gn_sums(dy, w, x_gn, gn, mean, rstd, addend):
         return _conv_call(dy, wt, C), None
     out = torch.empty((N, C, H, W), dtype=dy.dtype, device=dy.device, memory_format=torch.channels_last)
     sums = torch.empty((N * H * W // 128, C, 2), dtype=torch.float32, device=dy.device)
-    ad_ptr, ad_stride = ctypes.c_void_p(None), 0
-    if addend is not None:
-        ad_ptr, ad_stride = _p(addend), (addend.stride(0) if addend.dim() == 2 and addend.shape[0] > 1 else 0)
-    rc = _lib.nn_lib().gip_conv3x3_gnbwd_nhwc_f16(_p(dy), _p(wt), _p(out), N, H, W, dy.shape[1], C, _p(x_gn), _p(gn.weight), _p(gn.bias),
-                                                  _p(mean), _p(rstd), gn.num_groups, int(gn.act), ad_ptr, ad_stride, _p(sums),
-                                                  ctypes.c_void_p(torch.cuda.current_stream(dy.device).cuda_stream))
-    if rc != 0:
-        raise RuntimeError("gip_conv3x3_gnbwd_nhwc_f16 failed with status %d" % rc)
+    ad_ptr, ad_stride = _addend_args(addend)
+    call_nn(dy.device, "gip_conv3x3_gnbwd_nhwc_f16", ptr(dy), ptr(wt), ptr(out), N, H, W, dy.shape[1], C, ptr(x_gn), ptr(gn.weight),
+            ptr(gn.bias), ptr(mean), ptr(rstd), gn.num_groups, int(gn.act), ad_ptr, ad_stride, ptr(sums))
     return out, sums
 
 
 def _gn_bwd_raw(x, dy, gn, mean, rstd, addend, accum=None, chan_sums=None):
     """dL/dx of the same GroupNorm (+ `accum`, the other gradient reaching x, in the same pass)."""
     N, C, H, W = x.shape
-    lib = _lib.nn_lib()
-    ad_ptr, ad_stride = ctypes.c_void_p(None), 0
-    if addend is not None:
-        ad_ptr, ad_stride = _p(addend), (addend.stride(0) if addend.dim() == 2 and addend.shape[0] > 1 else 0)
+    ad_ptr, ad_stride = _addend_args(addend)
     dx = torch.empty_like(x, memory_format=torch.channels_last)
-    ws = _workspace(x.device, lib.gip_gn_workspace_bytes(N, gn.num_groups))
-    stream = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+    ws = _workspace(x.device, _lib.nn_lib().gip_gn_workspace_bytes(N, gn.num_groups))
+    head = (ptr(x), ptr(dy), ptr(gn.weight), ptr(gn.bias), ptr(mean), ptr(rstd), ptr(dx), N, H * W, C, gn.num_groups, int(gn.act),
+            ad_ptr, ad_stride)
     if chan_sums is not None:
-        rc = lib.gip_gn_silu_backward_sums(_p(x), _p(dy), _p(gn.weight), _p(gn.bias), _p(mean), _p(rstd), _p(dx), N, H * W, C,
-                                           gn.num_groups, int(gn.act), ad_ptr, ad_stride,
-                                           ctypes.c_void_p(None) if accum is None else _p(accum), _p(chan_sums), (H * W) // 128,
-                                           _p(ws), ws.numel(), stream)
+        call_nn(x.device, "gip_gn_silu_backward_sums", *head, ptr(accum), ptr(chan_sums), (H * W) // 128, ptr(ws), ws.numel())
     elif accum is None:
-        rc = lib.gip_gn_silu_backward(_p(x), _p(dy), _p(gn.weight), _p(gn.bias), _p(mean), _p(rstd), _p(dx), N, H * W, C,
-                                      gn.num_groups, int(gn.act), ad_ptr, ad_stride, _p(ws), ws.numel(), stream)
+        call_nn(x.device, "gip_gn_silu_backward", *head, ptr(ws), ws.numel())
     else:
-        rc = lib.gip_gn_silu_backward_accum(_p(x), _p(dy), _p(gn.weight), _p(gn.bias), _p(mean), _p(rstd), _p(dx), N, H * W, C,
-                                            gn.num_groups, int(gn.act), ad_ptr, ad_stride, _p(accum), _p(ws), ws.numel(), stream)
-    if rc != 0:
-        raise RuntimeError("GroupNorm backward failed with status %d" % rc)
+        call_nn(x.device, "gip_gn_silu_backward_accum", *head, ptr(accum), ptr(ws), ws.numel())
     return dx
 
 
@@ -1084,22 +979,15 @@ def _conv_s2_call(x, w, bias, pad, stats=None):
     N, C, H, W = x.shape
     cout = w.shape[0]
     out = torch.empty((N, cout, H // 2, W // 2), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
-    null = ctypes.c_void_p(None)
     if (stats is not None and _conv_tiles(N, H // 2, W // 2, cout) >= 256 and ((H // 2) * (W // 2)) % 128 == 0 and cout % 8 == 0 and
             cout // 32 <= 256 and os.environ.get("GIP_GN_STATS", "1") != "0" and os.environ.get("GIP_CONV_S2_STATS", "1") != "0"):
         st = torch.empty((N * (H // 2) * (W // 2) // 128, cout, 2), dtype=torch.float32, device=x.device)
-        rc = _lib.nn_lib().gip_conv3x3s2_stats_nhwc_f16(_p(x), _p(w), null if bias is None else _p(bias), _p(out), N, H, W, C, cout, pad, pad,
-                                                        _p(st), ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream))
-        if rc != 0:
-            raise RuntimeError("gip_conv3x3s2_stats_nhwc_f16 failed with status %d" % rc)
+        call_nn(x.device, "gip_conv3x3s2_stats_nhwc_f16", ptr(x), ptr(w), ptr(bias), ptr(out), N, H, W, C, cout, pad, pad, ptr(st))
         stats.append(st)
         return out
     ws = _workspace(x.device, _SPLITK_WS_BYTES) if _conv_tiles(N, H // 2, W // 2, cout) < 256 else None
-    rc = _lib.nn_lib().gip_conv3x3s2_nhwc_f16(_p(x), _p(w), null if bias is None else _p(bias), _p(out), N, H, W, C, cout, pad, pad,
-                                              null if ws is None else _p(ws), 0 if ws is None else ws.numel(),
-                                              ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream))
-    if rc != 0:
-        raise RuntimeError("gip_conv3x3s2_nhwc_f16 failed with status %d" % rc)
+    call_nn(x.device, "gip_conv3x3s2_nhwc_f16", ptr(x), ptr(w), ptr(bias), ptr(out), N, H, W, C, cout, pad, pad,
+            ptr(ws), 0 if ws is None else ws.numel())
     return out
 
 
@@ -1138,11 +1026,8 @@ def upsample2x_conv3x3(x, w, bias):
             x.shape[0] * 4 * x.shape[2] * x.shape[3] * max(x.shape[1], w.shape[0]) * 2 < (1 << 31)):
         N, C, H, W = x.shape
         out = torch.empty((N, w.shape[0], 2 * H, 2 * W), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
-        rc = _lib.nn_lib().gip_upsample2x_conv3x3_nhwc_f16(_p(x), _p(_wt_cache.get("up4", w, _upsample_conv_weight)),
-                                                           ctypes.c_void_p(None) if bias is None else _p(bias), _p(out), N, H, W, C,
-                                                           w.shape[0], ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream))
-        if rc != 0:
-            raise RuntimeError("gip_upsample2x_conv3x3_nhwc_f16 failed with status %d" % rc)
+        call_nn(x.device, "gip_upsample2x_conv3x3_nhwc_f16", ptr(x), ptr(_wt_cache.get("up4", w, _upsample_conv_weight)), ptr(bias), ptr(out),
+                N, H, W, C, w.shape[0])
         return out
     return conv3x3(F.interpolate(x, scale_factor=2.0, mode="nearest"), w, bias)
 
@@ -1183,10 +1068,8 @@ class _DownsampleAsym(torch.autograd.Function):
             # four parity classes of dx, each a small convolution over dy's grid (4 / 2 / 2 / 1 taps): minimal FLOPs
             dy = dy.contiguous(memory_format=torch.channels_last)
             dx = torch.empty((N, C, H, W), dtype=dy.dtype, device=dy.device, memory_format=torch.channels_last)
-            rc = _lib.nn_lib().gip_conv3x3s2_dgrad_nhwc_f16(_p(dy), _p(_wt_cache.get("s2t", w, _s2_dgrad_weight)), _p(dx), N, H // 2, W // 2,
-                                                            w.shape[0], C, ctypes.c_void_p(torch.cuda.current_stream(dy.device).cuda_stream))
-            if rc != 0:
-                raise RuntimeError("gip_conv3x3s2_dgrad_nhwc_f16 failed with status %d" % rc)
+            call_nn(dy.device, "gip_conv3x3s2_dgrad_nhwc_f16", ptr(dy), ptr(_wt_cache.get("s2t", w, _s2_dgrad_weight)), ptr(dx), N, H // 2, W // 2,
+                    w.shape[0], C)
             return dx, None, None, None
         if w.shape[0] > 128:          # measured: the library's backward-data kernels are as fast at 256 / 512 channels
             fallback("downsample_asym data gradient", dy, library=True)
@@ -1232,17 +1115,12 @@ class _ConvFewInputChannels(torch.autograd.Function):
         if ctx.c3:
             N, _, H, W = x.shape
             out = torch.empty((N, 128, H, W), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
-            null = ctypes.c_void_p(None)
-            stream = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
             if stats_out is not None and os.environ.get("GIP_GN_STATS", "1") != "0" and os.environ.get("GIP_CONV_S2_STATS", "1") != "0":
                 st = torch.empty((N * H * W // 128, 128, 2), dtype=torch.float32, device=x.device)
-                rc = _lib.nn_lib().gip_conv3x3_c3_fwd_stats_nhwc_f16(_p(x), _p(w), null if bias is None else _p(bias), _p(out), N, H, W, 128,
-                                                                     _p(st), stream)
+                call_nn(x.device, "gip_conv3x3_c3_fwd_stats_nhwc_f16", ptr(x), ptr(w), ptr(bias), ptr(out), N, H, W, 128, ptr(st))
                 stats_out.append(st)
             else:
-                rc = _lib.nn_lib().gip_conv3x3_c3_fwd_nhwc_f16(_p(x), _p(w), null if bias is None else _p(bias), _p(out), N, H, W, 128, stream)
-            if rc != 0:
-                raise RuntimeError("gip_conv3x3_c3_fwd_nhwc_f16 failed with status %d" % rc)
+                call_nn(x.device, "gip_conv3x3_c3_fwd_nhwc_f16", ptr(x), ptr(w), ptr(bias), ptr(out), N, H, W, 128)
             return out
         fallback("conv_in (few input channels)", x)
         return F.conv2d(x, w, bias, padding=1)
@@ -1256,10 +1134,7 @@ class _ConvFewInputChannels(torch.autograd.Function):
             wt = _wt_cache.get("c3t", w, lambda t: t.detach().flip(2, 3).permute(1, 2, 3, 0).contiguous())
             N, _, H, W = dy.shape
             dx = torch.empty((N, 3, H, W), dtype=dy.dtype, device=dy.device, memory_format=torch.channels_last)
-            rc = _lib.nn_lib().gip_conv3x3_c3_dgrad_nhwc_f16(_p(dy), _p(wt), _p(dx), N, H, W, 128,
-                                                             ctypes.c_void_p(torch.cuda.current_stream(dy.device).cuda_stream))
-            if rc != 0:
-                raise RuntimeError("gip_conv3x3_c3_dgrad_nhwc_f16 failed with status %d" % rc)
+            call_nn(dy.device, "gip_conv3x3_c3_dgrad_nhwc_f16", ptr(dy), ptr(wt), ptr(dx), N, H, W, 128)
             return dx, None, None, None
 
         def make(t):
@@ -1287,11 +1162,8 @@ def conv3x3_fewch(x, w, bias, stride=1, act=False):
             x.shape[2] % stride == 0 and x.shape[3] % stride == 0 and Wo % 16 == 0 and Ho % _FEWCH_SHAPES[(cin, cout, stride)] == 0 and
             not (torch.is_grad_enabled() and (x.requires_grad or w.requires_grad))):
         out = torch.empty((x.shape[0], cout, Ho, Wo), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
-        rc = _lib.nn_lib().gip_conv3x3_fewch_nhwc_f16(_p(x), _p(w), ctypes.c_void_p(None) if bias is None else _p(bias), _p(out),
-                                                      x.shape[0], x.shape[2], x.shape[3], cin, cout, stride, int(bool(act)),
-                                                      ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream))
-        if rc != 0:
-            raise RuntimeError("gip_conv3x3_fewch_nhwc_f16 failed with status %d" % rc)
+        call_nn(x.device, "gip_conv3x3_fewch_nhwc_f16", ptr(x), ptr(w), ptr(bias), ptr(out), x.shape[0], x.shape[2], x.shape[3], cin, cout,
+                stride, int(bool(act)))
         return out
     fallback("conv3x3_fewch", x)
     y = F.conv2d(x, w, bias, stride=stride, padding=1)
@@ -1364,10 +1236,7 @@ def _narrow_out_call(x, w, bias):
         p[:cout] = t.detach()
         return p.contiguous(memory_format=torch.channels_last)
     out = torch.empty((N, cout, H, W), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
-    rc = _lib.nn_lib().gip_conv3x3_fewch_nhwc_f16(_p(x), _p(_wt_cache.get("pad16", w, pad16)), ctypes.c_void_p(None) if bias is None else _p(bias),
-                                                  _p(out), N, H, W, cin, cout, 1, 0, ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream))
-    if rc != 0:
-        raise RuntimeError("gip_conv3x3_fewch_nhwc_f16 failed with status %d" % rc)
+    call_nn(x.device, "gip_conv3x3_fewch_nhwc_f16", ptr(x), ptr(_wt_cache.get("pad16", w, pad16)), ptr(bias), ptr(out), N, H, W, cin, cout, 1, 0)
     return out
 
 

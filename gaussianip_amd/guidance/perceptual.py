@@ -133,33 +133,28 @@ class _DistanceToTargets(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, module, x, *targets):
-        from .. import _lib
-        lib = _lib.nn_lib()
+        from .._lib import call_nn, nn_lib, ptr
         needs_grad = x.requires_grad
         with torch.set_grad_enabled(needs_grad):
             x16 = _nhwc(x.detach().to(torch.float16)).requires_grad_(needs_grad)
             feats = [_nhwc(f) for f in module.net(x16)]
         N = x.shape[0]
-        stream = fused.ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
         lins = module.lin_vectors()
         targets = [_nhwc(t) for t in targets]
         total = torch.zeros(N, device=x.device, dtype=torch.float32)
         for f, t, lin in zip(feats, targets, lins):
             assert t.shape == f.shape and t.dtype == torch.float16, "target features do not match the rendered images"
             HW, C = f.shape[2] * f.shape[3], f.shape[1]
-            blocks = lib.gip_lpips_layer_blocks(N, HW)
+            blocks = nn_lib().gip_lpips_layer_blocks(N, HW)
             partial = torch.empty(N, blocks, device=x.device, dtype=torch.float32)
-            rc = lib.gip_lpips_layer_forward(fused._p(f), fused._p(t), fused._p(lin), fused._p(partial), N, HW, C, blocks, stream)
-            if rc != 0:
-                raise RuntimeError("gip_lpips_layer_forward failed with status %d" % rc)
+            call_nn(x.device, "gip_lpips_layer_forward", ptr(f), ptr(t), ptr(lin), ptr(partial), N, HW, C, blocks)
             total += partial.sum(dim=1) / HW
         ctx.inner = (x16, feats, targets, lins) if needs_grad else None
         return total.view(N, 1, 1, 1)
 
     @staticmethod
     def backward(ctx, gout):
-        from .. import _lib
-        lib = _lib.nn_lib()
+        from .._lib import call_nn, ptr
         x16, feats, targets, lins = ctx.inner
         ctx.inner = None
         N = x16.shape[0]
@@ -168,15 +163,12 @@ class _DistanceToTargets(torch.autograd.Function):
         # the kernel saturates the rest)
         bound = torch.stack([4.0 * lin.max() / (f.shape[2] * f.shape[3]) for f, lin in zip(feats, lins)]).max() * g.abs().max()
         scale = torch.exp2(torch.floor(torch.log2(256.0 / bound.clamp_min(1e-30)))).clamp(1.0, 2.0 ** 60)
-        stream = fused.ctypes.c_void_p(torch.cuda.current_stream(x16.device).cuda_stream)
         grads = []
         for f, t, lin in zip(feats, targets, lins):
             HW, C = f.shape[2] * f.shape[3], f.shape[1]
             coef = (g * (scale / HW)).contiguous()
             gf = torch.empty_like(f)
-            rc = lib.gip_lpips_layer_backward(fused._p(f), fused._p(t), fused._p(lin), fused._p(coef), fused._p(gf), N, HW, C, stream)
-            if rc != 0:
-                raise RuntimeError("gip_lpips_layer_backward failed with status %d" % rc)
+            call_nn(x16.device, "gip_lpips_layer_backward", ptr(f), ptr(t), ptr(lin), ptr(coef), ptr(gf), N, HW, C)
             grads.append(gf)
         gx, = torch.autograd.grad(feats, x16, grads)
         return (None, gx.float() / scale) + (None,) * len(targets)

@@ -2,8 +2,6 @@
 
 Reference: simple_knn._C.distCUDA2 (gaussiansplatting/submodules/simple-knn/ext.cpp:16, spatial.cu:16-25,
 simple_knn.cu:185-221); called once at initialisation (scene/gaussian_model.py:123)."""
-import ctypes
-
 import torch
 
 from . import _lib
@@ -22,14 +20,8 @@ def distCUDA2(points: torch.Tensor, mode: str = "auto") -> torch.Tensor:
     out = torch.zeros((P,), dtype=torch.float32, device=pts.device)
     if P == 0:
         return out
-    lib = _lib.knn_lib()
     m = MODES[mode]
-    with torch.cuda.device(pts.device):
-        ws_bytes = lib.gip_knn_workspace_bytes_mode(P, m)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=pts.device)
-        rc = lib.gip_knn_mean_dist2_mode(P, ctypes.c_void_p(pts.data_ptr()), ctypes.c_void_p(out.data_ptr()),
-                                         ctypes.c_void_p(ws.data_ptr()), ws_bytes, m,
-                                         ctypes.c_void_p(torch.cuda.current_stream(pts.device).cuda_stream))
-    if rc != 0:
-        raise RuntimeError("gip_knn_mean_dist2_mode failed with status %d" % rc)
+    ws_bytes = _lib.knn_lib().gip_knn_workspace_bytes_mode(P, m)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=pts.device)
+    _lib.call_knn(pts.device, "gip_knn_mean_dist2_mode", P, _lib.ptr(pts), _lib.ptr(out), _lib.ptr(ws), ws_bytes, m)
     return out

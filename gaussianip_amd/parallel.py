@@ -48,7 +48,6 @@ def exchange_sum(params: Sequence[torch.Tensor], viewspace_grad_norm: Optional[t
     if _bucket_fast_path(grads + ([viewspace_grad_norm] if viewspace_grad_norm is not None else []), viewspace_grads):
         import ctypes
         from . import _lib
-        lib = _lib.model_lib()
         dsts = grads + ([viewspace_grad_norm] if viewspace_grad_norm is not None else [])
         n_scaled = len(grads)
         counts = [d.numel() for d in dsts]
@@ -58,21 +57,16 @@ def exchange_sum(params: Sequence[torch.Tensor], viewspace_grad_norm: Optional[t
         flat = torch.empty(sum(counts) + P, device=dev, dtype=torch.float32)
         seg = (ctypes.c_void_p * max(len(dsts), 1))(*[d.data_ptr() for d in dsts])
         cnt = (ctypes.c_int64 * max(len(dsts), 1))(*counts)
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        g2d = ctypes.c_void_p(viewspace_grads.data_ptr()) if viewspace_grads is not None else ctypes.c_void_p(None)
-        rc = lib.gip_pack_bucket(seg, cnt, len(dsts), g2d, V, P, ctypes.c_void_p(flat.data_ptr()), stream)
-        if rc != 0:
-            raise RuntimeError("gip_pack_bucket failed with status %d" % rc)
+        # the raw gradients go by address, not through _lib.ptr: null means "no norms" to the entry point, which rejects V = 0 —
+        # ptr would turn an empty [0, P, 3] into exactly that null and leave the bucket's tail unwritten
+        g2d = ctypes.c_void_p(viewspace_grads.data_ptr() if viewspace_grads is not None else None)
+        _lib.call_model(dev, "gip_pack_bucket", seg, cnt, len(dsts), g2d, V, P, _lib.ptr(flat))
         dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=group)
         # gradients (scaled when averaged) and a ready-made norm tensor (never scaled) go back in place
         if average and n_scaled < len(dsts):
-            rc = lib.gip_unpack_bucket(seg, cnt, n_scaled, ctypes.c_void_p(dsts[-1].data_ptr()), counts[-1],
-                                       ctypes.c_void_p(flat.data_ptr()), 1.0 / world, stream)
+            _lib.call_model(dev, "gip_unpack_bucket", seg, cnt, n_scaled, _lib.ptr(dsts[-1]), counts[-1], _lib.ptr(flat), 1.0 / world)
         else:
-            rc = lib.gip_unpack_bucket(seg, cnt, len(dsts), ctypes.c_void_p(None), 0, ctypes.c_void_p(flat.data_ptr()),
-                                       1.0 / world if average else 1.0, stream)
-        if rc != 0:
-            raise RuntimeError("gip_unpack_bucket failed with status %d" % rc)
+            _lib.call_model(dev, "gip_unpack_bucket", seg, cnt, len(dsts), _lib.ptr(None), 0, _lib.ptr(flat), 1.0 / world if average else 1.0)
         if viewspace_grads is not None:
             return flat[sum(counts):]
         return viewspace_grad_norm
@@ -153,15 +147,10 @@ def exchange_forward_stats(radii_per_view: torch.Tensor, depth: torch.Tensor, gr
     unpacking).  .wait() before use."""
     if radii_per_view.is_cuda and radii_per_view.dtype == torch.int32 and radii_per_view.is_contiguous() and \
             depth.dtype == torch.float32 and depth.is_contiguous():
-        import ctypes
         from . import _lib
         V, P = int(radii_per_view.shape[0]), int(radii_per_view.shape[1])
         bucket = torch.empty(P + 1, device=radii_per_view.device, dtype=torch.int32)
-        rc = _lib.model_lib().gip_max_bucket(ctypes.c_void_p(radii_per_view.data_ptr()), V, P, ctypes.c_void_p(depth.data_ptr()),
-                                             depth.numel(), ctypes.c_void_p(bucket.data_ptr()),
-                                             ctypes.c_void_p(torch.cuda.current_stream(bucket.device).cuda_stream))
-        if rc != 0:
-            raise RuntimeError("gip_max_bucket failed with status %d" % rc)
+        _lib.call_model(bucket.device, "gip_max_bucket", _lib.ptr(radii_per_view), V, P, _lib.ptr(depth), depth.numel(), _lib.ptr(bucket))
         work = dist.all_reduce(bucket, op=dist.ReduceOp.MAX, group=group, async_op=True) if _on(group) else None
         return _ForwardStats(bucket[:P], bucket[P:].view(torch.float32).reshape(()), work)
     rmax, dmax = radii_per_view.amax(dim=0), depth.detach().amax()

@@ -8,7 +8,6 @@ the view axis and the canvas is two HIP launches (include/gip_pose.h: OpenCV's e
 then the per-pixel draw), so a step issues no host synchronisation for
 its pose maps.  CPU tensors take a numpy path through the same spec (oracle-free: it is the host mirror used by tests).
 """
-import ctypes
 import math
 
 import numpy as np
@@ -122,14 +121,9 @@ class Skeleton:
         if self.device.type == "cuda":
             from . import _lib
             canvas = torch.empty((V, H, W, 3), dtype=torch.float32, device=self.device)
-            lib = _lib.model_lib()
-            ws = torch.empty(lib.gip_openpose_workspace_bytes(V, H), dtype=torch.uint8, device=self.device)     # per-row limb spans
-            rc = lib.gip_openpose_draw(
-                ctypes.c_void_p(pts_px.data_ptr()), ctypes.c_void_p(vis8.data_ptr()), ctypes.c_void_p(limbs.data_ptr()),
-                ctypes.c_void_p(canvas.data_ptr()), V, H, W, ctypes.c_void_p(ws.data_ptr()), ws.numel(),
-                ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
-            if rc != 0:
-                raise RuntimeError("gip_openpose_draw failed with status %d" % rc)
+            ws = torch.empty(_lib.model_lib().gip_openpose_workspace_bytes(V, H), dtype=torch.uint8, device=self.device)     # per-row limb spans
+            _lib.call_model(self.device, "gip_openpose_draw", _lib.ptr(pts_px), _lib.ptr(vis8), _lib.ptr(limbs), _lib.ptr(canvas), V, H, W,
+                            _lib.ptr(ws), ws.numel())
         else:
             raise ValueError("Skeleton.openpose_draw: the canvas is drawn by the HIP kernel; build the skeleton on a GPU")
         all_vis = mask.all(dim=1).to(torch.int64)

@@ -4,7 +4,6 @@ torch's fused Adam then launches three multi-tensor kernels per group — 18 lau
 (state[p] = {"step", "exp_avg", "exp_avg_sq"}, the step count a device scalar like torch's fused / capturable Adam), so
 the densify / prune surgery on the moments and `state_dict()` work unchanged; a GradScaler drives it like torch's fused
 Adam (`_step_supports_amp_scaling`: found_inf stays on the device, a skipped step moves nothing)."""
-import ctypes
 
 import torch
 
@@ -83,17 +82,12 @@ class GipAdam(torch.optim.Adam):
                                                 st["step"].data_ptr(), p.numel(), float(g["lr"]), 0))
         if not groups:
             return loss
-        lib = _lib.model_lib()
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        fi = ctypes.c_void_p(None)
+        fi32 = None
         if found_inf is not None:
             fi32 = found_inf.to(device=dev, dtype=torch.float32)       # (a converted temporary must outlive the launch)
             keep.append(fi32)
-            fi = ctypes.c_void_p(fi32.data_ptr())
         for i in range(0, len(groups), 8):
             chunk = groups[i:i + 8]
             arr = (_lib.GipAdamGroup * len(chunk))(*chunk)
-            rc = lib.gip_adam_step(arr, len(chunk), float(betas[0]), float(betas[1]), float(eps), fi, stream)
-            if rc != 0:
-                raise RuntimeError("gip_adam_step failed with status %d" % rc)
+            _lib.call_model(dev, "gip_adam_step", arr, len(chunk), float(betas[0]), float(betas[1]), float(eps), _lib.ptr(fi32))
         return loss

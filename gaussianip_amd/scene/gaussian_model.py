@@ -40,34 +40,23 @@ class _Activate(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, o, s, q):
-        import ctypes
-
-        from .. import _lib
+        from .._lib import call_model, ptr
         oo, so, qo = torch.empty_like(o), torch.empty_like(s), torch.empty_like(q)
-        p = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
-        rc = _lib.model_lib().gip_activate_gaussians(p(o), p(s), p(q), o.shape[0], p(oo), p(so), p(qo),
-                                                     ctypes.c_void_p(torch.cuda.current_stream(o.device).cuda_stream))
-        if rc != 0:
-            raise RuntimeError("gip_activate_gaussians failed with status %d" % rc)
+        call_model(o.device, "gip_activate_gaussians", ptr(o), ptr(s), ptr(q), o.shape[0], ptr(oo), ptr(so), ptr(qo))
         ctx.save_for_backward(oo, so, q)
         return oo, so, qo
 
     @staticmethod
     def backward(ctx, go, gs, gq):
-        import ctypes
-
-        from .. import _lib
+        from .._lib import call_model, ptr
         oo, so, q = ctx.saved_tensors
-        p = lambda t: ctypes.c_void_p(None if t is None else t.data_ptr())  # noqa: E731
         go, gs, gq = (None if g_ is None else g_.contiguous() for g_ in (go, gs, gq))
         need = ctx.needs_input_grad
         d_o = torch.empty_like(oo) if need[0] else None
         d_s = torch.empty_like(so) if need[1] else None
         d_q = torch.empty_like(q) if need[2] else None
-        rc = _lib.model_lib().gip_activate_gaussians_backward(p(oo), p(so), p(q), p(go), p(gs), p(gq), oo.shape[0], p(d_o), p(d_s), p(d_q),
-                                                              ctypes.c_void_p(torch.cuda.current_stream(oo.device).cuda_stream))
-        if rc != 0:
-            raise RuntimeError("gip_activate_gaussians_backward failed with status %d" % rc)
+        call_model(oo.device, "gip_activate_gaussians_backward", ptr(oo), ptr(so), ptr(q), ptr(go), ptr(gs), ptr(gq), oo.shape[0],
+                   ptr(d_o), ptr(d_s), ptr(d_q))
         return d_o, d_s, d_q
 
 
@@ -178,8 +167,7 @@ class GaussianModel:
     def _field_call(self, entry, src, colors, resolution, num_blocks, relax_ratio, before, after):
         """One call of the C entry `entry` of the field family (gip_density_field, gip_field_sample, gip_texture_bake) on the sources
         `src` of _field_sources(): the sources (with `colors` [N, 3] of the whole model cut to them, unless None) and the geometry,
-        then the entry's own arguments `before` and `after` the workspace, then the stream; tensors go by address.  RuntimeError
-        naming the entry on a non-zero status."""
+        then the entry's own arguments `before` and `after` the workspace; tensors go by address (_lib.ptr)."""
         import ctypes
 
         from .. import _lib
@@ -188,20 +176,13 @@ class GaussianModel:
         P = int(opacities.shape[0])
         grid = torch.linspace(-1, 1, resolution, dtype=torch.float32).to(dev)      # the host's values: the cut below depends on their bits
         margin = (2 / num_blocks) * relax_ratio       # rounded to float32 on the way in, like `vmin -= block_size * relax_ratio`
-        lib = _lib.model_lib()
         need = ctypes.c_size_t(0)
-        rc = lib.gip_field_workspace_size(P, resolution, num_blocks, ctypes.byref(need))
-        if rc != 0:
-            raise RuntimeError("gip_field_workspace_size failed with status %d" % rc)
+        _lib.query_model("gip_field_workspace_size", P, resolution, num_blocks, ctypes.byref(need))
         ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
         rgb = () if colors is None else (colors.float()[mask].contiguous(),)
         args = ((xyzs, opacities, stds, rots) + rgb + (P, self.center.contiguous(), self.scale, grid, resolution, num_blocks, margin) +
                 tuple(before) + (ws, need.value) + tuple(after))
-        with torch.cuda.device(dev):
-            rc = getattr(lib, entry)(*(ctypes.c_void_p(a.data_ptr()) if isinstance(a, torch.Tensor) else a for a in args),
-                                     ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        if rc != 0:
-            raise RuntimeError("%s failed with status %d" % (entry, rc))
+        _lib.call_model(dev, entry, *(_lib.ptr(a) if isinstance(a, torch.Tensor) else a for a in args))
 
     @staticmethod
     def _point_blocks(u, resolution, num_blocks):
@@ -870,9 +851,7 @@ class GaussianModel:
     def _gather_all(self, index, n_old, new_rows):
         """One launch (include/gip_model.h) rebuilds the six parameters and their Adam moments:
         row j <- old[index[j]] if index[j] < n_old else new_rows[name][index[j] - n_old] (moments of new rows: zeros)."""
-        import ctypes
         from .. import _lib
-        lib = _lib.model_lib()
         n_out = int(index.numel())
         descs, outs, keep_alive = [], {}, []
         for group in self.optimizer.param_groups:
@@ -897,12 +876,8 @@ class GaussianModel:
             arr[i].new_rows = nw.data_ptr() if (nw is not None and nw.numel()) else None
             arr[i].dst, arr[i].row_bytes = d.data_ptr(), rb
             keep_alive.append((o, nw, d))
-        rc = 0
         if descs:
-            rc = lib.gip_gather_rows(arr, len(descs), ctypes.c_void_p(index.data_ptr()), n_out, n_old,
-                                     ctypes.c_void_p(torch.cuda.current_stream(index.device).cuda_stream))
-        if rc != 0:
-            raise RuntimeError("gip_gather_rows failed with status %d" % rc)
+            _lib.call_model(index.device, "gip_gather_rows", arr, len(descs), _lib.ptr(index), n_out, n_old)
         rebuilt = {}
         for group in self.optimizer.param_groups:
             old = group["params"][0]

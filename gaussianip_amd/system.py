@@ -10,7 +10,6 @@ One behavioural difference, by design: the cameras of a step are rendered in ONE
 of sequentially; per-view results are identical (tests/test_gpu_pipeline.py).
 """
 import contextlib
-import ctypes
 import os
 from dataclasses import dataclass
 from typing import Dict, List, Optional
@@ -32,13 +31,9 @@ class _SparsityTerm(torch.autograd.Function):
     @staticmethod
     def forward(ctx, depth):
         from . import _lib
-        lib = _lib.model_lib()
         # a workspace per call (12 KB): it carries the maximum and the tie count to THIS call's backward, whatever runs in between
-        ws = torch.empty(lib.gip_sparsity_workspace_bytes() // 4, dtype=torch.float32, device=depth.device)
-        rc = lib.gip_sparsity_loss_forward(ctypes.c_void_p(depth.data_ptr()), depth.numel(), ctypes.c_void_p(ws.data_ptr()),
-                                           ctypes.c_void_p(torch.cuda.current_stream(depth.device).cuda_stream))
-        if rc != 0:
-            raise RuntimeError("gip_sparsity_loss_forward failed with status %d" % rc)
+        ws = torch.empty(_lib.model_lib().gip_sparsity_workspace_bytes() // 4, dtype=torch.float32, device=depth.device)
+        _lib.call_model(depth.device, "gip_sparsity_loss_forward", _lib.ptr(depth), depth.numel(), _lib.ptr(ws))
         ctx.save_for_backward(depth)
         ctx.ws = ws
         return ws[1]
@@ -49,11 +44,8 @@ class _SparsityTerm(torch.autograd.Function):
         depth, = ctx.saved_tensors
         g_depth = torch.empty_like(depth)
         g = g.to(torch.float32).reshape(1)
-        rc = _lib.model_lib().gip_sparsity_loss_backward(
-            ctypes.c_void_p(depth.data_ptr()), depth.numel(), ctypes.c_void_p(g.data_ptr()), 1.0, ctypes.c_void_p(ctx.ws.data_ptr()),
-            ctypes.c_void_p(g_depth.data_ptr()), ctypes.c_void_p(torch.cuda.current_stream(depth.device).cuda_stream))
-        if rc != 0:
-            raise RuntimeError("gip_sparsity_loss_backward failed with status %d" % rc)
+        _lib.call_model(depth.device, "gip_sparsity_loss_backward", _lib.ptr(depth), depth.numel(), _lib.ptr(g), 1.0, _lib.ptr(ctx.ws),
+                        _lib.ptr(g_depth))
         return g_depth
 
 
@@ -331,11 +323,9 @@ class StageOneStep:
         from . import _lib
         P = vis.shape[0]
         V = vg.shape[0] if vg.dim() == 3 else 1
-        p_ = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
-        rc = _lib.model_lib().gip_densify_stats(p_(vg), V, P, p_(vis), p_(self.radii), p_(g.max_radii2D), p_(g.xyz_gradient_accum), p_(g.denom),
-                                                ctypes.c_void_p(torch.cuda.current_stream(vis.device).cuda_stream))
-        if rc != 0:
-            raise RuntimeError("gip_densify_stats failed with status %d" % rc)
+        ptr = _lib.ptr
+        _lib.call_model(vis.device, "gip_densify_stats", ptr(vg), V, P, ptr(vis), ptr(self.radii), ptr(g.max_radii2D), ptr(g.xyz_gradient_accum),
+                        ptr(g.denom))
         return True
 
     # GaussianIP.on_before_optimizer_step (stage 1 branch)

@@ -203,9 +203,7 @@ class _TetSdfDiff(torch.autograd.Function):
         s = sdf.detach().reshape(-1).contiguous()
         Ne = grid.num_edges
         need = ctypes.c_size_t(0)
-        rc = _lib.model_lib().gip_tet_workspace_size(Ne, ctypes.byref(need))
-        if rc != 0:
-            raise RuntimeError("gip_tet_workspace_size failed with status %d" % rc)
+        _lib.query_model("gip_tet_workspace_size", Ne, ctypes.byref(need))
         with torch.cuda.device(dev):
             ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
             loss = torch.empty((), dtype=torch.float32, device=dev)

@@ -4,7 +4,6 @@
 include/gip_model.h: gip_ssim_*); everything else (CPU tensors, other dtypes, other window sizes) takes `ssim_torch`, a plain
 PyTorch statement of the same definition — under GIP_STRICT=1 a CUDA tensor that would leave the kernels raises instead.
 The photometric loss of those trainers is `0.8 * l1_loss(a, b) + 0.2 * (1 - ssim(a, b))`."""
-import ctypes
 import math
 import os
 
@@ -61,10 +60,6 @@ def _left_the_kernels(site, t):
         raise RuntimeError("GIP_STRICT: %s left the HIP kernels for a PyTorch FALLBACK (tensor %s, %s)" % (site, tuple(t.shape), t.dtype))
 
 
-def _vp(t):
-    return ctypes.c_void_p(t.data_ptr() if t is not None else None)
-
-
 class _FusedSSIM(torch.autograd.Function):
     """Per-image SSIM means [N] of [N, C, H, W] float32 CUDA images; optionally the map.  Saves the two images and the three
     derivative planes [3, N, C, H, W] the forward kernel wrote; the backward kernel reads the upstream gradient [N] on the device."""
@@ -72,18 +67,15 @@ class _FusedSSIM(torch.autograd.Function):
     @staticmethod
     def forward(ctx, img1, img2, want_map):
         from .. import _lib
-        lib = _lib.model_lib()
         N, C, H, W = img1.shape
         dev = img1.device
         need_grad = ctx.needs_input_grad[0]
-        ws = torch.empty(max(1, lib.gip_ssim_workspace_bytes(N, C, H, W) // 4), dtype=torch.float32, device=dev)
+        ws = torch.empty(max(1, _lib.model_lib().gip_ssim_workspace_bytes(N, C, H, W) // 4), dtype=torch.float32, device=dev)
         means = torch.empty(N, dtype=torch.float32, device=dev)
         deriv = torch.empty((3, N, C, H, W), dtype=torch.float32, device=dev) if need_grad else None
         smap = torch.empty_like(img1) if want_map else None
-        rc = lib.gip_ssim_forward(_vp(img1), _vp(img2), N, C, H, W, _vp(means), _vp(deriv), _vp(smap), _vp(ws),
-                                  ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        if rc != 0:
-            raise RuntimeError("gip_ssim_forward failed with status %d (shape %s)" % (rc, (N, C, H, W)))
+        _lib.call_model(dev, "gip_ssim_forward", _lib.ptr(img1), _lib.ptr(img2), N, C, H, W, _lib.ptr(means), _lib.ptr(deriv), _lib.ptr(smap),
+                        _lib.ptr(ws))
         if need_grad:
             ctx.save_for_backward(img1, img2, deriv)
         if want_map:
@@ -98,10 +90,8 @@ class _FusedSSIM(torch.autograd.Function):
         N, C, H, W = img1.shape
         g = g_means.to(torch.float32).contiguous()
         g_img1 = torch.empty_like(img1)
-        rc = _lib.model_lib().gip_ssim_backward(_vp(img1), _vp(img2), _vp(deriv), _vp(g), N, C, H, W, _vp(g_img1),
-                                                ctypes.c_void_p(torch.cuda.current_stream(img1.device).cuda_stream))
-        if rc != 0:
-            raise RuntimeError("gip_ssim_backward failed with status %d" % rc)
+        _lib.call_model(img1.device, "gip_ssim_backward", _lib.ptr(img1), _lib.ptr(img2), _lib.ptr(deriv), _lib.ptr(g), N, C, H, W,
+                        _lib.ptr(g_img1))
         return g_img1, None, None
 
 

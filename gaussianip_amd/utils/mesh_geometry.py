@@ -103,9 +103,7 @@ def check_topology(what, vertices, topology):
 
 def _workspace(V, dev):
     need = ctypes.c_size_t(0)
-    rc = _lib.model_lib().gip_mesh_geometry_workspace_size(V, ctypes.byref(need))
-    if rc != 0:
-        raise RuntimeError("gip_mesh_geometry_workspace_size failed with status %d" % rc)
+    _lib.query_model("gip_mesh_geometry_workspace_size", V, ctypes.byref(need))
     return torch.empty(need.value, dtype=torch.uint8, device=dev), need.value
 
 

@@ -487,9 +487,7 @@ def _mip_levels(Th, Tw, max_mip_level):
         if cap < 0:
             raise ValueError("max_mip_level must be None or >= 0")
     L, texels = ctypes.c_int32(0), ctypes.c_int64(0)
-    rc = _lib.model_lib().gip_mesh_mip_levels(Th, Tw, cap, ctypes.byref(L), ctypes.byref(texels))      # no launch: it takes no stream
-    if rc != 0:
-        raise RuntimeError("gip_mesh_mip_levels failed with status %d" % rc)
+    _lib.query_model("gip_mesh_mip_levels", Th, Tw, cap, ctypes.byref(L), ctypes.byref(texels))      # no launch: it takes no stream
     return cap, int(L.value), int(texels.value)
 
 

@@ -56,7 +56,7 @@ def test_layer_kernels_match_fp32_autograd(N, H, W, C):
     gradient on the same fp16 tensors, including pixels whose features are all zero (ReLU output)."""
     import ctypes
     from gaussianip_amd import _lib
-    from gaussianip_amd.guidance.fused import _p
+    _p = _lib.ptr
     lib = _lib.nn_lib()
     g = torch.Generator(device="cuda").manual_seed(N * 1000 + C)
     f = torch.relu(torch.randn(N, C, H, W, device="cuda", generator=g)).half().contiguous(memory_format=torch.channels_last)
