@@ -1,5 +1,5 @@
 """ctypes binding of the four HIP libraries: libgip_raster.so (include/gip_raster.h), libgip_knn.so (include/gip_knn.h),
-libgip_model.so (include/gip_model.h: scene, loss, mesh, field, tet and hash-grid kernels) and libgip_nn.so (include/gip_nn.h: the
+libgip_model.so (include/gip_model.h: scene, loss, mesh, field, tet, hash-grid and volume kernels) and libgip_nn.so (include/gip_nn.h: the
 denoiser / VAE kernels and the guidance glue).
 
 Host code launches through `call_model`, `call_nn` and `call_knn` (pointers from `ptr`, the device's current stream appended, a
@@ -345,6 +345,19 @@ def model_lib():
         lib.gip_hashgrid_backward_input.argtypes = [_vp, _vp, _vp] + _levels + [_vp, _vp]
         lib.gip_hashgrid_backward_table.restype = ctypes.c_int
         lib.gip_hashgrid_backward_table.argtypes = [_vp, _vp] + _levels + [_vp, _vp]
+        _box = [_f32] * 9 + [_f32, _f32, _f32, _i32]          # lo, hi and scale per axis, then dt, near, far, K_cap
+        lib.gip_volume_march_count.restype = ctypes.c_int
+        lib.gip_volume_march_count.argtypes = [_vp, _vp, _vp, _vp, _i64, _i32] + _box + [_vp, _vp]
+        lib.gip_volume_march_emit.restype = ctypes.c_int
+        lib.gip_volume_march_emit.argtypes = [_vp, _vp, _vp, _vp, _i64, _i32] + _box + [_vp, _i64, _vp, _vp, _vp, _vp]
+        lib.gip_volume_weights_forward.restype = ctypes.c_int
+        lib.gip_volume_weights_forward.argtypes = [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp]
+        lib.gip_volume_weights_backward.restype = ctypes.c_int
+        lib.gip_volume_weights_backward.argtypes = [_vp] * 7 + [_i64, _i64, _vp, _vp]
+        lib.gip_volume_accumulate_forward.restype = ctypes.c_int
+        lib.gip_volume_accumulate_forward.argtypes = [_vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp]
+        lib.gip_volume_accumulate_backward.restype = ctypes.c_int
+        lib.gip_volume_accumulate_backward.argtypes = [_vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp]
         _model = _Counted(lib)
     return _model
 
@@ -555,3 +568,5 @@ MESH_UV_SYMBOLS = ["gip_uv_face_classes", "gip_uv_chart_rounds", "gip_uv_chart_b
 MESH_TET_SYMBOLS = ["gip_tet_workspace_size", "gip_tet_mark", "gip_tet_emit", "gip_tet_backward", "gip_tet_sdf_diff",
                     "gip_tet_sdf_diff_backward"]
 HASHGRID_SYMBOLS = ["gip_hashgrid_forward", "gip_hashgrid_backward_input", "gip_hashgrid_backward_table"]
+VOLUME_SYMBOLS = ["gip_volume_march_count", "gip_volume_march_emit", "gip_volume_weights_forward", "gip_volume_weights_backward",
+                  "gip_volume_accumulate_forward", "gip_volume_accumulate_backward"]

@@ -626,6 +626,58 @@ class GaussianModel:
         out["mesh"] = mesh
         return out
 
+    @torch.no_grad()
+    def render_field_volume(self, camera, num_samples_per_ray=256, density_scale=1.0, grid_resolution=32, bg_color=None, **field_kwargs):
+        """The density-and-colour field that extract_mesh meshes, seen from `camera` by volume rendering (utils/volume.py):
+        {"comp_rgb" [3, H, W], "opacity" [1, H, W], "depth" [1, H, W]} in the layout of render(...).  One ray per pixel centre from
+        the camera's centre; the box is the normalised cloud's, center -/+ 1 / scale, as in to_tetrahedra_sdf_grid; its
+        grid_resolution^3 occupancy grid is extract_fields(**field_kwargs) max-pooled, > 0; steps of 1.732 * 2 / scale /
+        num_samples_per_ray; sigma = density_scale * density and the colour of sample_fields(**field_kwargs) at the samples'
+        midpoints.  depth is the weighted sum of the midpoints' distances (not divided by the opacity).  bg_color: three numbers,
+        black when absent; a pixel whose ray misses the box is exactly bg_color.  field_kwargs: resolution, num_blocks, relax_ratio."""
+        import math
+
+        from ..utils import volume
+        if set(field_kwargs) - {"resolution", "num_blocks", "relax_ratio"}:
+            raise TypeError("render_field_volume: unknown arguments %s" % sorted(set(field_kwargs) - {"resolution", "num_blocks", "relax_ratio"}))
+        num_samples_per_ray, G = int(num_samples_per_ray), int(grid_resolution)
+        if num_samples_per_ray < 1 or not 1 <= G <= volume.MAX_GRID:
+            raise ValueError("render_field_volume: num_samples_per_ray must be at least 1 and grid_resolution lie in 1 .. %d" % volume.MAX_GRID)
+        dev = self._xyz.device
+        H, W = int(camera.image_height), int(camera.image_width)
+        bg = torch.zeros(3, device=dev) if bg_color is None else torch.as_tensor(bg_color, dtype=torch.float32, device=dev).reshape(3)
+        out = {"comp_rgb": bg[:, None, None].expand(3, H, W).clone(), "opacity": torch.zeros((1, H, W), device=dev),
+               "depth": torch.zeros((1, H, W), device=dev)}
+        field = self.extract_fields(**field_kwargs)                   # sets center / scale
+        if self._field_sources() is None:
+            return out
+        occ = torch.nn.functional.adaptive_max_pool3d(field[None, None], G)[0, 0] > 0
+        half = 1.0 / self.scale
+        aabb = torch.cat((self.center - half, self.center + half))
+        # the camera looks along +z with x to the right and y down; its matrices are stored transposed
+        c2w = torch.linalg.inv(camera.world_view_transform.to(dev).float().t())
+        fx, fy = W / (2.0 * math.tan(camera.FoVx / 2.0)), H / (2.0 * math.tan(camera.FoVy / 2.0))
+        j, i = torch.meshgrid(torch.arange(H, dtype=torch.float32, device=dev) + 0.5, torch.arange(W, dtype=torch.float32, device=dev) + 0.5,
+                              indexing="ij")
+        directions = torch.stack(((i - W / 2.0) / fx, (j - H / 2.0) / fy, torch.ones_like(i)), dim=-1).reshape(-1, 3)
+        rays_d = torch.nn.functional.normalize(directions @ c2w[:3, :3].t(), dim=-1).contiguous()
+        rays_o = c2w[:3, 3].expand(rays_d.shape).contiguous()
+        step = 1.732 * 2 * half / num_samples_per_ray
+        ray_indices, t_starts, t_ends, _ = volume.march_rays(rays_o, rays_d, occ, aabb, step, max_samples_per_ray=num_samples_per_ray + 1)
+        if ray_indices.shape[0] == 0:
+            return out
+        index = ray_indices.long()
+        t_mid = ((t_starts + t_ends) / 2.0)[:, None]
+        sampled = self.sample_fields((rays_o[index] + rays_d[index] * t_mid).contiguous(), **field_kwargs)
+        sigmas = (float(density_scale) * sampled["density"]).contiguous()
+        weights, _, _ = volume.render_weight_from_density(t_starts, t_ends, sigmas, ray_indices, H * W)
+        opacity = volume.accumulate_along_rays(weights, None, ray_indices, H * W)
+        depth = volume.accumulate_along_rays(weights, t_mid, ray_indices, H * W)
+        rgb = volume.accumulate_along_rays(weights, sampled["color"].contiguous(), ray_indices, H * W)
+        comp = rgb + bg * (1.0 - opacity)
+        return {"comp_rgb": comp.t().reshape(3, H, W).contiguous(), "opacity": opacity.t().reshape(1, H, W).contiguous(),
+                "depth": depth.t().reshape(1, H, W).contiguous()}
+
     # ------------------------------------------------------------------ initialisation
     def create_from_pcd(self, pcd: BasicPointCloud, spatial_lr_scale: float, dist2=None):
         """`dist2` (mean squared 3-NN distance per point) defaults to the HIP distCUDA2 replacement."""

@@ -461,6 +461,39 @@ int gip_hashgrid_backward_input(const float* x, const float* table, const float*
 int gip_hashgrid_backward_table(const float* x, const float* g_enc, const float* level_scale, const int32_t* level_res,
                                 const int32_t* level_size, const int64_t* level_offset, const int32_t* level_hashed, int64_t N, int32_t L,
                                 int32_t F, int64_t P, float* g_table, void* stream);
+/* Volume rendering of a density field: marching rays through an occupancy grid and compositing along them (csrc/volume.hip, whose
+ * header states the definition; gaussianip_amd/utils/volume.py).  They stand in for the nerfacc calls of the reference's
+ * nerf-volume-renderer (threestudio/models/renderers/nerf_volume_renderer.py); nerfacc is CUDA-only.  All arrays are on the device:
+ * rays_o, rays_d [R, 3] float32, occ [G, G, G] uint8 ([ix, iy, iz]), jitter [R] float32 or NULL, counts [R] int32, offsets [R + 1]
+ * int32 (CSR: the samples of ray r are the rows offsets[r] .. offsets[r + 1] - 1), ray_indices [M] int32, every other array float32.
+ * The box lo, hi and scale = G / (hi - lo) per axis go by value.  No entry point uses an atomic: every output is bitwise reproducible.
+ *   gip_volume_march_count, gip_volume_march_emit   nerfacc.OccGridEstimator.sampling without its sigma_fn (nerf_volume_renderer.py:84
+ *       and :96): the number of samples of every ray; then, with offsets = the exclusive running sum of the counts and M their total,
+ *       ray_indices, t_starts and t_ends [M], a ray's samples adjacent and ordered by t.  A row is compared with M before it is written.
+ *   gip_volume_weights_forward / _backward          nerfacc.render_weight_from_density (nerf_volume_renderer.py:150): weights, trans and
+ *       alphas [M] of sigmas [M]; backward g_sigmas [M] of g_weights [M] and the forward's three outputs.  Rows are clamped to [0, M].
+ *   gip_volume_accumulate_forward / _backward       nerfacc.accumulate_along_rays (nerf_volume_renderer.py:158, :161, :164, :170):
+ *       out [R, C] = the weighted sum of values [M, C] along each ray, C = 1 .. 16; values NULL means ones and C = 1.  Backward writes
+ *       g_weights [M] and g_values [M, C] (either may be NULL) of g_out [R, C]; a ray index outside [0, R) gives zeros.
+ * Status 1, launching nothing: a NULL required pointer, R < 0 or R above (2^31 - 1) / 64, G outside 1 .. 256, K_cap < 1,
+ * R K_cap >= 2^31, dt not positive and finite, a NaN near or far, a box that is not finite with lo < hi and scale > 0, M outside
+ * 0 .. 2^31 - 1, C outside 1 .. 16, C != 1 without values, M C >= 2^31.  R == 0 (and, where nothing would be written, M == 0) is a
+ * success that launches nothing.  Status 3: a launch error. */
+int gip_volume_march_count(const float* rays_o, const float* rays_d, const uint8_t* occ, const float* jitter, int64_t R, int32_t G,
+                           float lo_x, float lo_y, float lo_z, float hi_x, float hi_y, float hi_z, float scale_x, float scale_y,
+                           float scale_z, float dt, float near, float far, int32_t K_cap, int32_t* counts, void* stream);
+int gip_volume_march_emit(const float* rays_o, const float* rays_d, const uint8_t* occ, const float* jitter, int64_t R, int32_t G,
+                          float lo_x, float lo_y, float lo_z, float hi_x, float hi_y, float hi_z, float scale_x, float scale_y,
+                          float scale_z, float dt, float near, float far, int32_t K_cap, const int32_t* offsets, int64_t M,
+                          int32_t* ray_indices, float* t_starts, float* t_ends, void* stream);
+int gip_volume_weights_forward(const float* t_starts, const float* t_ends, const float* sigmas, const int32_t* offsets, int64_t R, int64_t M,
+                               float* weights, float* trans, float* alphas, void* stream);
+int gip_volume_weights_backward(const float* t_starts, const float* t_ends, const float* g_weights, const float* weights, const float* trans,
+                                const float* alphas, const int32_t* offsets, int64_t R, int64_t M, float* g_sigmas, void* stream);
+int gip_volume_accumulate_forward(const float* weights, const float* values, const int32_t* offsets, int64_t R, int64_t M, int32_t C,
+                                  float* out, void* stream);
+int gip_volume_accumulate_backward(const float* weights, const float* values, const int32_t* ray_indices, const float* g_out, int64_t R,
+                                   int64_t M, int32_t C, float* g_weights, float* g_values, void* stream);
 #ifdef __cplusplus
 }
 #endif
