@@ -24,6 +24,7 @@ import pytest
 import torch
 
 import scenes
+from scenes import gaussians_at_pixels as _gaussians  # noqa: F401  (test_gpu_fwd_tail_trips.py imports it from here)
 from test_gpu_headline_parity import list_mode  # noqa: F401  (fixture)
 from test_gpu_raster_parity import _check_backward, _dev, _oracle_forward, _settings
 
@@ -44,28 +45,6 @@ SCENES = {
 
 def _camera(h, w):
     return scenes.camera(0.0, 0.0, 2.0, 50.0, h, w)
-
-
-def _place(cam, h, w, px, py, z):
-    """World positions that project to the pixel coordinates (px, py) at view depth z (the rasterizer's pixel (i, j) sits at
-    the coordinates (i, j))."""
-    xv = ((2.0 * px + 1.0) / w - 1.0) * cam["tanfovx"] * z
-    yv = ((2.0 * py + 1.0) / h - 1.0) * cam["tanfovy"] * z
-    ph = np.stack([xv, yv, z, np.ones_like(z)], 1) @ np.linalg.inv(cam["viewmatrix"].astype(np.float64))
-    return ph[:, :3]
-
-
-def _gaussians(rng, cam, h, w, px, py, z, sigma_pix, opacity, sh_degree):
-    """Anisotropic Gaussians (axes 0.6-1 of sigma_pix pixels on screen, any orientation) at the given pixel coordinates."""
-    n = px.shape[0]
-    focal = w / (2.0 * cam["tanfovx"])
-    q = rng.normal(size=(n, 4))
-    shs = np.zeros((n, (sh_degree + 1) ** 2, 3))
-    shs[:, 0] = (rng.uniform(0, 1, (n, 3)) - 0.5) / 0.28209479177387814
-    shs[:, 1:] = rng.normal(size=shs[:, 1:].shape) * 0.1
-    sc = dict(means3D=_place(cam, h, w, px, py, z), scales=(sigma_pix * z / focal)[:, None] * rng.uniform(0.6, 1.0, (n, 3)),
-              rotations=q / np.linalg.norm(q, axis=1, keepdims=True), opacities=opacity[:, None], shs=shs)
-    return {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in sc.items()}
 
 
 @functools.lru_cache(maxsize=None)

@@ -68,14 +68,15 @@ def _dump():
     _write_record(_report, "parity_deep_lists.json")
 
 
-def _oracle_view(oracle, name, azimuth=0.0):
-    """The oracle's forward of one view, its images and its knife-edge classes: computed once per (scene, camera)."""
-    key = (name, azimuth)
+def _oracle_view(oracle, name, azimuth=0.0, mod=dls):
+    """The oracle's forward of one view, its images and its knife-edge classes: computed once per (scene, camera).  `mod`: the
+    scenes module (deep_list_scenes, or one with its build / oracle_forward / list_statistics / BG / SH_DEGREE)."""
+    key = (mod.__name__, name, azimuth)
     if key not in _oracle_cache:
-        ro, images = dls.oracle_forward(oracle, name, azimuth)
+        ro, images = mod.oracle_forward(oracle, name, azimuth)
         subjects, n_pixels, sharing = ro.knife_edge_gaussians(KNIFE_EDGE, sharing=True)
         _oracle_cache[key] = dict(ro=ro, images=images, subjects=subjects, sharing=sharing | subjects, knife_edge_pixels=n_pixels,
-                                  lists=dls.list_statistics(ro))
+                                  lists=mod.list_statistics(ro))
     return _oracle_cache[key]
 
 
@@ -85,15 +86,15 @@ def _upstream(seed, V, H, W):
             rng.normal(size=(V, 1, H, W)).astype(np.float32))
 
 
-def _hip_backward(name, azimuths, up, color_only=False):
+def _hip_backward(name, azimuths, up, color_only=False, mod=dls):
     """Forward + backward of the launch set through the autograd function.  Returns (images, {name: gradient}) as numpy;
     means2D is [V, P, 3]."""
     from gaussianip_amd import GaussianRasterizer, rasterize_views
     V = len(azimuths)
     sts = []
     for az in azimuths:
-        sc, cam, H, W = dls.build(name, az)
-        sts.append(_settings(cam, H, W, dls.BG, dls.SH_DEGREE))
+        sc, cam, H, W = mod.build(name, az)
+        sts.append(_settings(cam, H, W, mod.BG, mod.SH_DEGREE))
     P = sc["means3D"].shape[0]
     t = {k: _dev(v).requires_grad_(True) for k, v in sc.items()}
     kw = dict(shs=t["shs"], scales=t["scales"], rotations=t["rotations"])
@@ -141,10 +142,12 @@ def _row_errors(ours, ref, top):
     return (np.abs(ours.astype(np.float64).reshape(ref.shape) - ref) / top).reshape(P, -1).max(1)
 
 
-def _compare(tag, name, ours, ref, subjects, cap, ref_end_to_end=None, assert_end_to_end=False, sharing=None, apart=None):
+def _compare(tag, name, ours, ref, subjects, cap, ref_end_to_end=None, assert_end_to_end=False, sharing=None, apart=None,
+             min_entries=MIN_ELEMENTWISE_ENTRIES, report=None):
     """MAX_TOL of the largest |gradient| on every row that is no knife-edge subject; at most `cap` subject rows beyond it;
     `sharing` given: REL_TOL element by element above FLOOR_FRAC of the maximum on the rows outside `sharing`;
-    `apart` given: the max-normalised error over the rows outside it is recorded as well."""
+    `apart` given: the max-normalised error over the rows outside it is recorded as well.  `min_entries`: what the per-element
+    bar has to cover at least; `report`: the record to write to (this module's by default)."""
     ref = ref.astype(np.float64)
     top = float(np.abs(ref).max()) + 1e-30
     rows = _row_errors(ours, ref, top)
@@ -170,13 +173,13 @@ def _compare(tag, name, ours, ref, subjects, cap, ref_end_to_end=None, assert_en
         e2e = float(_row_errors(ours, ref_end_to_end.astype(np.float64), top)[~subjects].max())
         rec["max_norm_end_to_end"] = e2e
         line += "   end-to-end %.2e%s" % (e2e, "" if assert_end_to_end else " (recorded only)")
-    _report.setdefault(tag, {})[name] = rec
+    (_report if report is None else report).setdefault(tag, {})[name] = rec
     print(line)
     assert e_max < MAX_TOL, "%s %s: max error / max |grad| = %.3e outside the knife-edge subject rows" % (tag, name, e_max)
     assert n_subject_miss <= cap, "%s %s: %d knife-edge subject rows miss the bar, more than the %d pixels that may flip" % (
         tag, name, n_subject_miss, cap)
     if sharing is not None:
-        assert n_rel >= MIN_ELEMENTWISE_ENTRIES, "%s %s: the per-element bar covers only %d entries" % (tag, name, n_rel)
+        assert n_rel >= min_entries, "%s %s: the per-element bar covers only %d entries" % (tag, name, n_rel)
         assert e_rel < REL_TOL, "%s %s: per-element relative error %.3e (entries above %.0e of the maximum)" % (tag, name, e_rel, FLOOR_FRAC)
     if assert_end_to_end:
         assert e2e < MAX_TOL, "%s %s: end-to-end max error / max |grad| = %.3e" % (tag, name, e2e)
