@@ -484,6 +484,8 @@ def nn_lib():
         lib.gip_attention_fwd_strided2_f16.restype = ctypes.c_int
         lib.gip_attention_fwd_strided2_f16.argtypes = [_vp, _vp, _vp, _vp] + [ctypes.c_int32] * 5 + [ctypes.c_float, _vp, _vp, ctypes.c_int32,
                                                        ctypes.c_float, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp]
+        lib.gip_attention_variant.restype = ctypes.c_int
+        lib.gip_attention_variant.argtypes = [ctypes.c_int32] * 6
         lib.gip_attention_fwd_f16.restype = ctypes.c_int
         lib.gip_attention_fwd_f16.argtypes = [_vp, _vp, _vp, _vp] + [ctypes.c_int32] * 5 + [ctypes.c_float, _vp, _vp, ctypes.c_int32, ctypes.c_float, _vp]
         lib.gip_attention_fwd_strided_f16.restype = ctypes.c_int

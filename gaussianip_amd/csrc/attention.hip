@@ -611,13 +611,14 @@ static void launch_attn_q2(hipStream_t s, const void* q, const void* k, const vo
                      (_Float16*)o, Nq, Nkv, H, c, ld_kv, ld_q, xcd);
 }
 
+// two: 0 = one key set, 1 / 2 = the short / long second-set kernel (attn_fwd_kernel's TWO; chosen by attn_variant below)
 template <int D>
-static void launch_attn(dim3 grid, hipStream_t s, const void* q, const void* k, const void* v, void* o, int Nq, int Nkv, int H,
+static void launch_attn(int two, dim3 grid, hipStream_t s, const void* q, const void* k, const void* v, void* o, int Nq, int Nkv, int H,
                         float c, const void* k2, const void* v2, int Nkv2, float w2, int ld_kv, int ld_kv2, int ld_q) {
-  if (k2 && Nkv2 <= AT_BKV)
+  if (two == 1)
     hipLaunchKernelGGL((attn_fwd_kernel<D, 1>), grid, dim3(256), 0, s, (const _Float16*)q, (const _Float16*)k, (const _Float16*)v,
                        (_Float16*)o, Nq, Nkv, H, c, (const _Float16*)k2, (const _Float16*)v2, Nkv2, w2, ld_kv, ld_kv2, ld_q);
-  else if (k2)
+  else if (two == 2)
     hipLaunchKernelGGL((attn_fwd_kernel<D, 2>), grid, dim3(256), 0, s, (const _Float16*)q, (const _Float16*)k, (const _Float16*)v,
                        (_Float16*)o, Nq, Nkv, H, c, (const _Float16*)k2, (const _Float16*)v2, Nkv2, w2, ld_kv, ld_kv2, ld_q);
   else
@@ -638,42 +639,71 @@ static void launch_attn_wide(hipStream_t s, const void* q, const void* k, const 
                      ld_kv, ld_q, xcd);
 }
 
+// ---- dispatch -------------------------------------------------------------------------------------------------------------------
+// Which kernel a call runs.  The head dim picks the instantiation of the first three; the last three exist for D = 40 only.
+enum AttnVariant {
+  ATTN_PLAIN = 0,        // attn_fwd_kernel<D, 0, 4>: one key set, 128 queries per workgroup
+  ATTN_SET2_SMALL = 1,   // attn_fwd_kernel<D, 1, 4>: second key set of at most AT_BKV keys, one accumulator
+  ATTN_SET2_LONG = 2,    // attn_fwd_kernel<D, 2, 4>: second key set of any length, two accumulators
+  ATTN_WIDE8 = 3,        // attn_fwd_kernel<40, 0, 8>: 8 waves (256 queries) per workgroup
+  ATTN_Q2_8 = 4,         // attn_fwd_q2_kernel<40, 8>: two query tiles per wave, 512 queries per workgroup
+  ATTN_Q2_4 = 5          // attn_fwd_q2_kernel<40, 4>: two query tiles per wave, 256 queries per workgroup
+};
+// Debug knobs (tests and tools set them through ctypes; the gip_dbg_conv_* pattern of conv3x3.hip):
+//   gip_dbg_attn_qt / gip_dbg_attn_nw   >= 0: used by the next calls in place of GIP_ATTN_QT / GIP_ATTN_NW; -1: the environment's value
+//   gip_dbg_attn_last_variant           the AttnVariant of the last call that was dispatched (-1: none yet; a rejected call leaves it)
+extern "C" { int gip_dbg_attn_qt = -1; int gip_dbg_attn_nw = -1; int gip_dbg_attn_last_variant = -1; }
+
+// GIP_ATTN_NW (default 4 waves): waves per workgroup of the long D = 40 self-attention (the 64 x 64 level: 4096 keys).  The plain loop
+// streams every (batch, head)'s keys / values from L2 once per 128 queries — 2 GB per launch at batch 12, and a build without
+// any MFMA or exp2 still takes 2/3 of the time (tools/experiments/attention_pipelined_qk.md, round 4) — 256 queries per workgroup
+// halve that stream: 0.44 -> 0.41 ms at batch 12, 0.155 -> 0.138 at batch 4 (one workgroup per CU, so only where >= 512
+// workgroups remain; D = 80 at 1024 keys measured slower).  GIP_ATTN_NW = 4: the plain loop everywhere (A/B), 8: wherever supported
+// GIP_ATTN_QT: two query tiles per wave, 8 waves (512 queries) per workgroup for the long D = 40 layers that leave >= 192 workgroups
+// (attn_fwd_q2_kernel): one wave's matrix and vector work overlap across its two tiles and the K / V stream per query is a
+// quarter of the plain loop's.  Same box, bit-identical outputs: 0.44 -> 0.39 ms at batch 12 on a slow box (0.365 on a fast
+// one), 0.150 -> 0.141 at batch 4, 1.11 -> 0.99 at 16384 keys (refine).  GIP_ATTN_QT = 1: off (A/B); 2: wherever supported
+// Both are read once per process.  The one place the kernel is chosen (the entry point and the tests' gip_attention_variant use it).
+static AttnVariant attn_variant(int B, int H, int Nq, int Nkv, int D, bool two, int Nkv2) {
+  static const int env_nw = [] { const char* e = getenv("GIP_ATTN_NW"); return e && *e ? atoi(e) : 0; }();
+  static const int env_qt = [] { const char* e = getenv("GIP_ATTN_QT"); return e && *e ? atoi(e) : 0; }();
+  const int nw = gip_dbg_attn_nw >= 0 ? gip_dbg_attn_nw : env_nw, qt2 = gip_dbg_attn_qt >= 0 ? gip_dbg_attn_qt : env_qt;
+  if (qt2 != 1 && !two && D == 40 && Nkv >= 1024 && Nq % 64 == 0 && (qt2 == 2 || ((Nq + 511) / 512) * B * H >= 192))
+    return nw == 4 ? ATTN_Q2_4 : ATTN_Q2_8;
+  if (!two && D == 40 && Nkv >= 1024 && Nq % 256 == 0 && nw != 4 && (nw == 8 || (Nq / 256) * B * H >= 512)) return ATTN_WIDE8;
+  return !two ? ATTN_PLAIN : (Nkv2 <= AT_BKV ? ATTN_SET2_SMALL : ATTN_SET2_LONG);
+}
+
+// the variant a call of these sizes would run under the current knobs (Nkv2 = 0: one key set); launches nothing
+extern "C" int gip_attention_variant(int32_t B, int32_t H, int32_t Nq, int32_t Nkv, int32_t D, int32_t Nkv2) {
+  return attn_variant(B, H, Nq, Nkv, D, Nkv2 > 0, Nkv2);
+}
+
 extern "C" int gip_attention_fwd_strided2_f16(const void* q, const void* k, const void* v, void* o, int32_t B, int32_t H,
                                               int32_t Nq, int32_t Nkv, int32_t D, float scale, const void* k2, const void* v2,
                                               int32_t Nkv2, float weight2, int32_t ld_q, int32_t ld_kv, int32_t ld_kv2, void* stream) {
   if (!q || !k || !v || !o || B < 1 || H < 1 || Nq < 32 || Nq % 32 || Nkv < 1 || ld_q < H * D || ld_q % 8) return 1;
   if ((k2 != nullptr) != (v2 != nullptr) || (k2 && Nkv2 < 1)) return 1;
   if (ld_kv < H * D || ld_kv % 8 || (k2 && (ld_kv2 < H * D || ld_kv2 % 8))) return 1;        // 16-byte row loads
+  if (D != 40 && D != 64 && D != 80 && D != 160) return 1;
   const float c = scale * 1.4426950408889634f;
   const dim3 grid((Nq + AT_BQ - 1) / AT_BQ, B * H);
   hipStream_t s = (hipStream_t)stream;
-  // GIP_ATTN_NW (6 / 8; default 4): waves per workgroup of the long self-attention layers (D = 40 / 80, >= 1024 keys); A/B switch
-  // long D = 40 self-attention (the 64 x 64 level: 4096 keys): 8 waves per workgroup share the K / V stages.  The plain loop
-  // streams every (batch, head)'s keys / values from L2 once per 128 queries — 2 GB per launch at batch 12, and a build without
-  // any MFMA or exp2 still takes 2/3 of the time (tools/experiments/attention_pipelined_qk.md, round 4) — 256 queries per workgroup
-  // halve that stream: 0.44 -> 0.41 ms at batch 12, 0.155 -> 0.138 at batch 4 (one workgroup per CU, so only where >= 512
-  // workgroups remain; D = 80 at 1024 keys measured slower).  GIP_ATTN_NW = 4: the plain loop everywhere (A/B), 8: wherever supported
-  static const int nw = [] { const char* e = getenv("GIP_ATTN_NW"); return e && *e ? atoi(e) : 0; }();
-  // Two query tiles per wave, 8 waves (512 queries) per workgroup for the long D = 40 layers that leave >= 192 workgroups
-  // (attn_fwd_q2_kernel): one wave's matrix and vector work overlap across its two tiles and the K / V stream per query is a
-  // quarter of the plain loop's.  Same box, bit-identical outputs: 0.44 -> 0.39 ms at batch 12 on a slow box (0.365 on a fast
-  // one), 0.150 -> 0.141 at batch 4, 1.11 -> 0.99 at 16384 keys (refine).  GIP_ATTN_QT = 1: off (A/B); 2: wherever supported
-  static const int qt2 = [] { const char* e = getenv("GIP_ATTN_QT"); return e && *e ? atoi(e) : 0; }();
-  if (qt2 != 1 && !k2 && D == 40 && Nkv >= 1024 && Nq % 64 == 0 && (qt2 == 2 || ((Nq + 511) / 512) * B * H >= 192)) {
-    if (nw == 4) launch_attn_q2<40, 4>(s, q, k, v, o, B * H, Nq, Nkv, H, c, ld_kv, ld_q);
-    else launch_attn_q2<40, 8>(s, q, k, v, o, B * H, Nq, Nkv, H, c, ld_kv, ld_q);
-    return hipGetLastError() == hipSuccess ? 0 : 3;
-  }
-  if (!k2 && D == 40 && Nkv >= 1024 && Nq % 256 == 0 && nw != 4 && (nw == 8 || (Nq / 256) * B * H >= 512)) {
-    launch_attn_wide<40, 8>(s, q, k, v, o, B * H, Nq, Nkv, H, c, ld_kv, ld_q);
-    return hipGetLastError() == hipSuccess ? 0 : 3;
-  }
-  switch (D) {
-    case 40: launch_attn<40>(grid, s, q, k, v, o, Nq, Nkv, H, c, k2, v2, Nkv2, weight2, ld_kv, ld_kv2, ld_q); break;
-    case 64: launch_attn<64>(grid, s, q, k, v, o, Nq, Nkv, H, c, k2, v2, Nkv2, weight2, ld_kv, ld_kv2, ld_q); break;
-    case 80: launch_attn<80>(grid, s, q, k, v, o, Nq, Nkv, H, c, k2, v2, Nkv2, weight2, ld_kv, ld_kv2, ld_q); break;
-    case 160: launch_attn<160>(grid, s, q, k, v, o, Nq, Nkv, H, c, k2, v2, Nkv2, weight2, ld_kv, ld_kv2, ld_q); break;
-    default: return 1;
+  const AttnVariant var = attn_variant(B, H, Nq, Nkv, D, k2 != nullptr, Nkv2);
+  gip_dbg_attn_last_variant = var;
+  switch (var) {
+    case ATTN_Q2_4: launch_attn_q2<40, 4>(s, q, k, v, o, B * H, Nq, Nkv, H, c, ld_kv, ld_q); break;
+    case ATTN_Q2_8: launch_attn_q2<40, 8>(s, q, k, v, o, B * H, Nq, Nkv, H, c, ld_kv, ld_q); break;
+    case ATTN_WIDE8: launch_attn_wide<40, 8>(s, q, k, v, o, B * H, Nq, Nkv, H, c, ld_kv, ld_q); break;
+    default: {
+      const int two = var == ATTN_SET2_SMALL ? 1 : (var == ATTN_SET2_LONG ? 2 : 0);
+      switch (D) {
+        case 40: launch_attn<40>(two, grid, s, q, k, v, o, Nq, Nkv, H, c, k2, v2, Nkv2, weight2, ld_kv, ld_kv2, ld_q); break;
+        case 64: launch_attn<64>(two, grid, s, q, k, v, o, Nq, Nkv, H, c, k2, v2, Nkv2, weight2, ld_kv, ld_kv2, ld_q); break;
+        case 80: launch_attn<80>(two, grid, s, q, k, v, o, Nq, Nkv, H, c, k2, v2, Nkv2, weight2, ld_kv, ld_kv2, ld_q); break;
+        default: launch_attn<160>(two, grid, s, q, k, v, o, Nq, Nkv, H, c, k2, v2, Nkv2, weight2, ld_kv, ld_kv2, ld_q); break;
+      }
+    }
   }
   return hipGetLastError() == hipSuccess ? 0 : 3;
 }

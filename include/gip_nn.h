@@ -295,6 +295,10 @@ int gip_attention_fwd_strided_f16(const void* q, const void* k, const void* v, v
 int gip_attention_fwd_strided2_f16(const void* q, const void* k, const void* v, void* o, int32_t B, int32_t H, int32_t Nq,
                                    int32_t Nkv, int32_t D, float scale, const void* k2, const void* v2, int32_t Nkv2,
                                    float weight2, int32_t ld_q, int32_t ld_kv, int32_t ld_kv2, void* stream);
+/* Which of the six kernel variants (enum AttnVariant in csrc/attention.hip: 0 plain, 1 / 2 short / long second key set, 3 eight
+ * waves, 4 / 5 two query tiles per wave with 8 / 4 waves) a call of these sizes runs; Nkv2 = 0: one key set.  Launches nothing.
+ * The entry points choose by the same function and leave their choice in the integer gip_dbg_attn_last_variant. */
+int gip_attention_variant(int32_t B, int32_t H, int32_t Nq, int32_t Nkv, int32_t D, int32_t Nkv2);
 
 /* Guidance glue (csrc/guidance_glue.hip): the element-wise algebra around the denoiser, one launch per stage instead of the
  * reference's op chains; same expressions, same order, same intermediate half roundings.

@@ -29,6 +29,11 @@ def test_attention_matches_fp32_reference(B, H, Nq, Nkv, D, spread):
     err = float((o.float() - ref).abs().max())
     assert err <= 3e-3 * max(1.0, float(ref.abs().max())), err
     assert torch.equal(fused.attention(q, k, v, H), o)
+    if (B, H, Nq, Nkv, D) == (12, 8, 4096, 4096, 40):
+        import ctypes
+        from gaussianip_amd import _lib
+        # the training shape runs the two-tiles-per-wave kernel, 8 waves (enum AttnVariant of csrc/attention.hip)
+        assert ctypes.c_int.in_dll(_lib.nn_lib()._lib, "gip_dbg_attn_last_variant").value == 4
 
 
 def test_attention_module_uses_the_hip_kernel(monkeypatch):
