@@ -1,5 +1,5 @@
 """ctypes binding of the four HIP libraries: libgip_raster.so (include/gip_raster.h), libgip_knn.so (include/gip_knn.h),
-libgip_model.so (include/gip_model.h: scene, loss, mesh, field, tet, hash-grid and volume kernels) and libgip_nn.so (include/gip_nn.h: the
+libgip_model.so (include/gip_model.h: scene, loss, mesh, field, tet, hash-grid, volume and SDF-volume kernels) and libgip_nn.so (include/gip_nn.h: the
 denoiser / VAE kernels and the guidance glue).
 
 Host code launches through `call_model`, `call_nn` and `call_knn` (pointers from `ptr`, the device's current stream appended, a
@@ -358,6 +358,15 @@ def model_lib():
         lib.gip_volume_accumulate_forward.argtypes = [_vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp]
         lib.gip_volume_accumulate_backward.restype = ctypes.c_int
         lib.gip_volume_accumulate_backward.argtypes = [_vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp]
+        lib.gip_volume_alpha_weights_forward.restype = ctypes.c_int
+        lib.gip_volume_alpha_weights_forward.argtypes = [_vp, _vp, _i64, _i64, _vp, _vp, _vp]
+        lib.gip_volume_alpha_weights_backward.restype = ctypes.c_int
+        lib.gip_volume_alpha_weights_backward.argtypes = [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp]
+        _sdf = [_vp] * 8 + [_f32]                             # sdf, normals, rays_d, t_starts, t_ends, values, offsets, inv_std, then rho
+        lib.gip_volume_sdf_render_forward.restype = ctypes.c_int
+        lib.gip_volume_sdf_render_forward.argtypes = _sdf + [_i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp]
+        lib.gip_volume_sdf_render_backward.restype = ctypes.c_int
+        lib.gip_volume_sdf_render_backward.argtypes = _sdf + [_vp] * 5 + [_i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp]
         _model = _Counted(lib)
     return _model
 
@@ -572,3 +581,5 @@ MESH_TET_SYMBOLS = ["gip_tet_workspace_size", "gip_tet_mark", "gip_tet_emit", "g
 HASHGRID_SYMBOLS = ["gip_hashgrid_forward", "gip_hashgrid_backward_input", "gip_hashgrid_backward_table"]
 VOLUME_SYMBOLS = ["gip_volume_march_count", "gip_volume_march_emit", "gip_volume_weights_forward", "gip_volume_weights_backward",
                   "gip_volume_accumulate_forward", "gip_volume_accumulate_backward"]
+VOLUME_SDF_SYMBOLS = ["gip_volume_alpha_weights_forward", "gip_volume_alpha_weights_backward", "gip_volume_sdf_render_forward",
+                      "gip_volume_sdf_render_backward"]

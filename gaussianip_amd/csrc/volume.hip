@@ -49,20 +49,15 @@
 #include <stdint.h>
 
 #include "../../include/gip_model.h"
-#include "mesh_common.h"
+#include "volume_common.h"
 
-#define VOL_RAYS_PER_BLOCK (MESH_THREADS / 64)
 #define VOL_MAX_GRID 256
-#define VOL_MAX_CHANNELS 16
 
 // the box and the grid, by value in the kernel arguments: uniform, so these are scalar loads
 struct VolGrid {
   float lo[3], hi[3], scale[3];
   int G;
 };
-
-__device__ __forceinline__ float vol_min(float a, float b) { return b < a ? b : a; }
-__device__ __forceinline__ float vol_max(float a, float b) { return b > a ? b : a; }
 
 // [t_near, t_far) of a ray in the box; false when the ray has no samples
 __device__ __forceinline__ bool vol_span(const float o[3], const float d[3], const VolGrid& g, float near, float far, float* t_near, float* t_far) {
@@ -158,17 +153,6 @@ volume_march_emit_kernel(const float* __restrict__ rays_o, const float* __restri
   vol_march<true>(rays_o, rays_d, occ, jitter, g, dt, near, far, K_cap, r, lane, offsets[r], M, ray_indices, t_starts, t_ends);
 }
 
-// the doubling scan of the definition over the 64 lanes, towards higher lanes (UP) or towards lower ones
-template <bool UP>
-__device__ __forceinline__ float vol_scan(float s, int lane) {
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const float y = UP ? __shfl_up(s, d, 64) : __shfl_down(s, d, 64);
-    if (UP ? lane >= d : lane + d < 64) s += y;
-  }
-  return s;
-}
-
 __global__ void __launch_bounds__(MESH_THREADS)
 volume_weights_forward_kernel(const float* __restrict__ t_starts, const float* __restrict__ t_ends, const float* __restrict__ sigmas,
                               const int32_t* __restrict__ offsets, int64_t R, int64_t M, float* __restrict__ weights,
@@ -243,9 +227,7 @@ volume_accumulate_forward_kernel(const float* __restrict__ weights, const float*
 #pragma unroll
   for (int c = 0; c < VOL_MAX_CHANNELS; c++) {
     if (c < C) {
-      float v = acc[c];
-#pragma unroll
-      for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+      const float v = vol_wave_sum(acc[c]);
       if (lane == 0) out[r * C + c] = v;
     }
   }
@@ -270,12 +252,6 @@ volume_accumulate_backward_kernel(const float* __restrict__ weights, const float
 }
 
 // ------------------------------------------------------------------------------------------------------------------------ host
-// workgroups of one wave per ray; 0 when the count is not launchable
-static int64_t vol_ray_blocks(int64_t R) {
-  if (R < 1 || R > INT32_MAX / 64) return 0;
-  return (R + VOL_RAYS_PER_BLOCK - 1) / VOL_RAYS_PER_BLOCK;
-}
-
 // The march's arguments; fills *g.  false: the caller returns the bad-argument status.
 static bool vol_march_config(int64_t R, int32_t G, const float box[9], float dt, float near, float far, int32_t K_cap, VolGrid* g) {
   if (R < 0 || R > INT32_MAX / 64 || G < 1 || G > VOL_MAX_GRID || K_cap < 1) return false;
@@ -316,8 +292,6 @@ extern "C" int gip_volume_march_emit(const float* rays_o, const float* rays_d, c
               ray_indices, t_starts, t_ends);
   return mesh_done();
 }
-
-static bool vol_rows_ok(int64_t R, int64_t M) { return R >= 0 && R <= INT32_MAX / 64 && mesh_count_ok(M); }
 
 extern "C" int gip_volume_weights_forward(const float* t_starts, const float* t_ends, const float* sigmas, const int32_t* offsets, int64_t R,
                                           int64_t M, float* weights, float* trans, float* alphas, void* stream) {

@@ -6,7 +6,8 @@ project's own, and has not been compared with nerfacc's output.
   march_rays(rays_o, rays_d, occ, aabb, render_step_size, ...)    (ray_indices, t_starts, t_ends, offsets): the samples of every ray
   render_weight_from_density(t_starts, t_ends, sigmas, ...)       (weights, trans, alphas); gradient to sigmas.  First order only.
   accumulate_along_rays(weights, values, ray_indices, n_rays)     [n_rays, C]; gradients to weights and values.  First order only.
-  OccupancyGrid                    stands in for nerfacc.OccGridEstimator(levels=1): update_every_n_steps, sampling
+  OccupancyGrid                    stands in for nerfacc.OccGridEstimator(levels=1): update_every_n_steps, sampling (pruning by a
+                                   sigma_fn, or by an alpha_fn for utils/sdf_volume.py's signed-distance fields)
   ImplicitVolume                   the reference's implicit-volume geometry over get_encoding / get_mlp
   NeRFVolumeRenderer               the reference's nerf-volume-renderer with the no-material and a solid background
   get_ray_directions, get_rays     the reference's threestudio/utils/ops.py:179-260 without the camera noise
@@ -246,17 +247,26 @@ class OccupancyGrid(nn.Module):
 
     @torch.no_grad()
     def sampling(self, rays_o, rays_d, sigma_fn=None, render_step_size=1e-3, alpha_thre=0.0, stratified=False, early_stop_eps=1e-4,
-                 near_plane=0.0, far_plane=1e10, max_samples_per_ray=1024):
+                 near_plane=0.0, far_plane=1e10, max_samples_per_ray=1024, alpha_fn=None):
         """(ray_indices, t_starts, t_ends) of march_rays through binaries; stratified draws jitter = torch.rand(R).  With sigma_fn
         (t_starts, t_ends, ray_indices -> sigmas [M]) and alpha_thre > 0 or early_stop_eps > 0, only the samples with
         alphas >= alpha_thre and trans >= early_stop_eps are kept, trans and alphas being render_weight_from_density's on the marched
-        samples; the mask and the compaction are PyTorch."""
+        samples; the mask and the compaction are PyTorch.  With alpha_fn (the same arguments -> alphas [M]) instead, the alphas are
+        the given ones and trans is utils.sdf_volume.render_weight_from_alpha's.  Both functions together: ValueError."""
+        if sigma_fn is not None and alpha_fn is not None:
+            raise ValueError("OccupancyGrid.sampling: give sigma_fn or alpha_fn, not both")
         jitter = torch.rand(rays_o.shape[0], device=rays_o.device) if stratified and isinstance(rays_o, torch.Tensor) else None
         ray_indices, t_starts, t_ends, _ = march_rays(rays_o, rays_d, self.binaries, self._lo_hi, render_step_size, near_plane, far_plane,
                                                       jitter, max_samples_per_ray)
         if sigma_fn is not None and (alpha_thre > 0 or early_stop_eps > 0) and ray_indices.shape[0]:
             sigmas = sigma_fn(t_starts, t_ends, ray_indices).reshape(-1).float().contiguous()
             _, trans, alphas = _kernel_weights(t_starts, t_ends, sigmas, ray_indices, int(rays_o.shape[0]))
+            keep = prune_mask(trans, alphas, alpha_thre, early_stop_eps)
+            ray_indices, t_starts, t_ends = ray_indices[keep], t_starts[keep], t_ends[keep]
+        elif alpha_fn is not None and (alpha_thre > 0 or early_stop_eps > 0) and ray_indices.shape[0]:
+            from .sdf_volume import render_weight_from_alpha
+            alphas = alpha_fn(t_starts, t_ends, ray_indices).reshape(-1).float().contiguous()
+            _, trans = render_weight_from_alpha(alphas, ray_indices, int(rays_o.shape[0]))
             keep = prune_mask(trans, alphas, alpha_thre, early_stop_eps)
             ray_indices, t_starts, t_ends = ray_indices[keep], t_starts[keep], t_ends[keep]
         return ray_indices, t_starts, t_ends
@@ -360,6 +370,21 @@ def _chunked(fn, chunk, points, **kwargs):
     return torch.cat(parts, dim=0)
 
 
+def _background(what, bg_color, B, H, W, C, dev):
+    """bg [B H W, C] of a renderer's bg_color: [C], [B, C] or [B, H, W, C]; black when absent."""
+    n_rays = B * H * W
+    if bg_color is None:
+        return torch.zeros((n_rays, C), dtype=torch.float32, device=dev)
+    bg = torch.as_tensor(bg_color, dtype=torch.float32, device=dev)
+    if bg.dim() == 1:
+        return bg.expand(n_rays, C)
+    if tuple(bg.shape[:-1]) == (B,):
+        return bg[:, None, None, :].expand(B, H, W, bg.shape[-1]).reshape(n_rays, -1)
+    if tuple(bg.shape[:-1]) == (B, H, W):
+        return bg.reshape(n_rays, -1)
+    raise ValueError("%s: bg_color must be [3], [B, 3] or [B, H, W, 3]" % what)
+
+
 class NeRFVolumeRenderer(nn.Module):
     """The reference's nerf-volume-renderer over a geometry with `bbox`, `radius`, forward and forward_density (ImplicitVolume): an
     OccupancyGrid of 32^3 cells, steps of 1.732 * 2 * radius / num_samples_per_ray, the colour sigmoid(features) (the reference's
@@ -430,19 +455,7 @@ class NeRFVolumeRenderer(nn.Module):
         # the second moment about the ray's own depth, not E[t^2] - depth^2, which cancels
         z_variance = accumulate_along_rays(weights, ((t_positions - depth[index]) ** 2).contiguous(), ray_indices, n_rays)
 
-        C = comp_rgb_fg.shape[-1]
-        if bg_color is None:
-            bg = torch.zeros((n_rays, C), dtype=torch.float32, device=o.device)
-        else:
-            bg = torch.as_tensor(bg_color, dtype=torch.float32, device=o.device)
-            if bg.dim() == 1:
-                bg = bg.expand(n_rays, C)
-            elif tuple(bg.shape[:-1]) == (B,):
-                bg = bg[:, None, None, :].expand(B, H, W, bg.shape[-1]).reshape(n_rays, -1)
-            elif tuple(bg.shape[:-1]) == (B, H, W):
-                bg = bg.reshape(n_rays, -1)
-            else:
-                raise ValueError("NeRFVolumeRenderer: bg_color must be [3], [B, 3] or [B, H, W, 3]")
+        bg = _background("NeRFVolumeRenderer", bg_color, B, H, W, comp_rgb_fg.shape[-1], o.device)
         comp_rgb = comp_rgb_fg + bg * (1.0 - opacity)
         out = {"comp_rgb": comp_rgb.view(B, H, W, -1), "comp_rgb_fg": comp_rgb_fg.view(B, H, W, -1), "comp_rgb_bg": bg.reshape(B, H, W, -1),
                "opacity": opacity.view(B, H, W, 1), "depth": depth.view(B, H, W, 1), "z_variance": z_variance.view(B, H, W, 1)}

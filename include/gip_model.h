@@ -494,6 +494,36 @@ int gip_volume_accumulate_forward(const float* weights, const float* values, con
                                   float* out, void* stream);
 int gip_volume_accumulate_backward(const float* weights, const float* values, const int32_t* ray_indices, const float* g_out, int64_t R,
                                    int64_t M, int32_t C, float* g_weights, float* g_values, void* stream);
+/* NeuS volume rendering of a signed-distance field (csrc/volume_sdf.hip, whose header states the definition;
+ * gaussianip_amd/utils/sdf_volume.py).  They stand in for what the reference's neus-volume-renderer
+ * (threestudio/models/renderers/neus_volume_renderer.py) computes with PyTorch ops and nerfacc.  All arrays are on the device and
+ * float32 but offsets [R + 1] int32 (CSR, as above): sdf, t_starts, t_ends, alphas, trans, weights [M], normals [M, 3] or NULL (then
+ * iter_cos = -1, the alpha_fn form), rays_d [R, 3] (indexed by the ray), values [M, C] or NULL (then C = 0), inv_std one float read on
+ * the device, cos_anneal_ratio by value, out and g_out [R, 2 + C] (opacity, depth, the C channels).  No entry point uses an atomic:
+ * every output is bitwise reproducible.
+ *   gip_volume_alpha_weights_forward / _backward    nerfacc.render_weight_from_alpha (neus_volume_renderer.py:216): weights and trans [M]
+ *       of alphas [M]; backward g_alphas [M] of g_weights [M] by the division-free reverse recurrence, finite at alpha == 1.
+ *   gip_volume_sdf_render_forward                   get_alpha with use_volsdf off (:72-96; normals NULL: alpha_fn :135-141 and occ_eval_fn
+ *       :295-301), render_weight_from_alpha (:216) and the accumulate_along_rays calls (:222, :225, :228, :262) in one launch: alphas,
+ *       trans, weights [M] and out [R, 2 + C].
+ *   gip_volume_sdf_render_backward                  their backward in one launch: g_sdf [M], g_normals [M, 3] (NULL allowed; needs normals),
+ *       g_values [M, C] (NULL allowed) and g_inv_std_rays [R], the per-ray parts of inv_std's gradient, which the caller adds; of g_out
+ *       [R, 2 + C] and g_weights [M] (NULL allowed).  No gradient to the rays or the samples.
+ * Status 1, launching nothing: a NULL required pointer, R < 0 or R above (2^31 - 1) / 64, M outside 0 .. 2^31 - 1, C outside 0 .. 16,
+ * values NULL with C != 0 or given with C == 0, M max(C, 1) >= 2^31, cos_anneal_ratio not finite or outside [0, 1].  R == 0 or M == 0
+ * is a success that launches nothing.  Status 3: a launch error. */
+int gip_volume_alpha_weights_forward(const float* alphas, const int32_t* offsets, int64_t R, int64_t M, float* weights, float* trans,
+                                     void* stream);
+int gip_volume_alpha_weights_backward(const float* alphas, const float* trans, const float* g_weights, const int32_t* offsets, int64_t R,
+                                      int64_t M, float* g_alphas, void* stream);
+int gip_volume_sdf_render_forward(const float* sdf, const float* normals, const float* rays_d, const float* t_starts, const float* t_ends,
+                                  const float* values, const int32_t* offsets, const float* inv_std, float cos_anneal_ratio, int64_t R,
+                                  int64_t M, int32_t C, float* alphas, float* trans, float* weights, float* out, void* stream);
+int gip_volume_sdf_render_backward(const float* sdf, const float* normals, const float* rays_d, const float* t_starts, const float* t_ends,
+                                   const float* values, const int32_t* offsets, const float* inv_std, float cos_anneal_ratio,
+                                   const float* alphas, const float* trans, const float* weights, const float* g_out, const float* g_weights,
+                                   int64_t R, int64_t M, int32_t C, float* g_sdf, float* g_normals, float* g_values, float* g_inv_std_rays,
+                                   void* stream);
 #ifdef __cplusplus
 }
 #endif
