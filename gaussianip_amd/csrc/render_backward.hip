@@ -17,8 +17,8 @@
 //     workgroup barrier, no cross-wave LDS traffic, four-way ILP in the per-pixel math.
 //   * NO float atomics.  The ten per-pixel terms of an entry are first added over a lane's four pixels
 //     in registers; the live entries are taken TWO at a time and the twenty accumulators of a pair are
-//     reduced across the 64 lanes by one fold network (fold_two_entries: 15 v_permlane32/16_swap and 9 DPP
-//     adds per pair, where two lone entries took 14 and 26) that keeps every sum's summation tree, after
+//     reduced across the 64 lanes by one fold network (fold_two_entries in bwd_fold.h: 15 half-wave exchanges
+//     over the LDS crossbar and 9 DPP adds per pair) that keeps every sum's summation tree, after
 //     which every sum sits in a lane known at compile time and one predicated dword store
 //     writes both rows.  ONE row per (tile, Gaussian) instance, at row inst_offset[g] + (tile's position
 //     in g's rectangle).  An entry's summation tree is the same in either slot of a pair and with any
@@ -30,83 +30,11 @@
 // Row layout (floats): 0,1 M1,M2  2,3,4 M3,M4,M5  5 M0   (moments of Q = dL/dG * G over the pixel offsets dx, dy)
 //                      6,7,8 dL/dcolour  9 dL/ddepth  10..15 unused
 #include "gip_internal.h"
+#include "bwd_fold.h"   // BwdAcc, fold_two_entries
 
 #ifndef BWD_GRID
 #define BWD_GRID 16384 // persistent single-wave workgroups (grid-stride over the segment list)
 #endif
-
-// Cross-lane fold of TWO entries' ten terms at once (20 accumulators of 64 lanes -> 20 sums): 15 swaps, 9 DPP adds, 14 plain
-// adds and 8 selects, where two lone folds took 14 swaps and 26 DPP adds.  Every sum keeps the summation tree of the
-// one-entry fold this replaces, so the rows are bit-identical to its rows:
-//     terms 0-7   T(q), q[i] = (x[i] + x[i+32]) + (x[i+16] + x[i+48]),
-//     terms 8, 9  T(h[16..31]) + T(h[0..15]), h[i] = x[i] + x[i+32],
-// with T the 16-lane tree over neighbours, pairs of neighbours, quads and halves (float addition commutes, so only the
-// pairing matters, not which lane holds a sum).  What the fold costs is its DPP and swap instructions, not its instruction
-// count (profiles/bwd_pair_fold.txt), so the network spends plain selects to halve the registers BEFORE each DPP level:
-//   level 32  v_permlane32_swap(a_t, b_t): a_t = [a_lo | b_lo], b_t = [a_hi | b_hi], so a_t + b_t holds entry A's half sums
-//             in lanes 0-31 and entry B's in lanes 32-63                                          10 swaps + 10 adds
-//   level 16  v_permlane16_swap (odd rows of x <-> even rows of y) on the term pairs (0,1) (2,3) (4,5) (6,7), then x + y:
-//             rows [A_t, A_t+1, B_t, B_t+1]; on (8,9) the swap alone: x = first rows [A_8, A_9, B_8, B_9] of the half
-//             sums, y = their second rows                                                           5 swaps +  4 adds
-//   level 1   per register pair (x, y): u = even lanes of x | odd lanes of y, v = the other lanes; quad_perm:[1,0,3,2](v) + u
-//             holds x's neighbour sums in the even lanes and y's in the odd ones: 6 -> 3 registers   6 selects + 3 DPP adds
-//   level 2   the same on bit 1 of the lane with quad_perm:[2,3,0,1]: 3 -> 2 registers              2 selects + 2 DPP adds
-//   level 4   bank-masked DPP adds (banks 0, 2 with row_shl:4, banks 1, 3 from the other register with row_shr:4; the
-//             unwritten banks keep the destination): 2 -> 1 register                                2 DPP adds
-//   level 8   row_ror:8                                                                             1 DPP add
-//   terms 8, 9: odd lane (second row's tree) + even lane (first row's), banks 1, 3 only             1 DPP add
-// Result: b8, lanes 16 r + j (j = 0..3): entry r >> 1, term 2 j + (r & 1); lanes 16 r + 4: entry r >> 1, term 8 + (r & 1).
-// Entry A's term t and entry B's term t go through the SAME tree (the same lanes of another row at every level), so an
-// entry's row does not depend on its slot in the pair nor on its partner.
-// One asm statement: the compiler pads no hazard inside one, so the order below keeps at least two wait states between
-// every vector write and the v_permlane / DPP read of that register (s_nop where no independent work is left).
-// Inline asm for the swaps because the clang builtin mis-selects its second result for float operands on ROCm 7.2
-// (both extracts return the first register); the whole wave must be active (wave-uniform control flow only).
-struct BwdAcc { float v0, v1, v2, v3, v4, v5, v6, v7, v8, v9; };
-
-__device__ __forceinline__ void fold_two_entries(BwdAcc& a, BwdAcc& b) {
-#define GIP_DPP(d, s, ctrl, bank) "v_add_f32_dpp " d ", " s ", " s " " ctrl " row_mask:0xf bank_mask:" bank "\n\t"
-#define GIP_QP1 "quad_perm:[1,0,3,2]"
-#define GIP_QP2 "quad_perm:[2,3,0,1]"
-  asm volatile(
-      "s_nop 1\n\t"
-      "v_permlane32_swap_b32 %0, %10\n\tv_permlane32_swap_b32 %1, %11\n\tv_permlane32_swap_b32 %2, %12\n\t"
-      "v_permlane32_swap_b32 %3, %13\n\tv_permlane32_swap_b32 %4, %14\n\tv_permlane32_swap_b32 %5, %15\n\t"
-      "v_permlane32_swap_b32 %6, %16\n\tv_permlane32_swap_b32 %7, %17\n\tv_permlane32_swap_b32 %8, %18\n\t"
-      "v_permlane32_swap_b32 %9, %19\n\t"
-      "v_add_f32 %0, %0, %10\n\tv_add_f32 %1, %1, %11\n\tv_add_f32 %2, %2, %12\n\tv_add_f32 %3, %3, %13\n\t"
-      "v_add_f32 %4, %4, %14\n\tv_add_f32 %5, %5, %15\n\tv_add_f32 %6, %6, %16\n\tv_add_f32 %7, %7, %17\n\t"
-      "v_add_f32 %8, %8, %18\n\tv_add_f32 %9, %9, %19\n\t"
-      "v_permlane16_swap_b32 %0, %1\n\tv_permlane16_swap_b32 %2, %3\n\tv_permlane16_swap_b32 %4, %5\n\t"
-      "v_permlane16_swap_b32 %6, %7\n\tv_permlane16_swap_b32 %8, %9\n\t"
-      "v_add_f32 %0, %0, %1\n\tv_add_f32 %2, %2, %3\n\tv_add_f32 %4, %4, %5\n\tv_add_f32 %6, %6, %7\n\t"
-      // level 1, two registers per DPP add: u = even lanes of x | odd lanes of y, v = the other lanes; dpp(v) + u leaves x's
-      // neighbour sums in the even lanes and y's in the odd ones     %10 <- %0 | %2   %12 <- %4 | %6   %14 <- %8 | %9
-      "v_cndmask_b32_e64 %10, %0, %2, %20\n\tv_cndmask_b32_e64 %11, %2, %0, %20\n\t"
-      "v_cndmask_b32_e64 %12, %4, %6, %20\n\tv_cndmask_b32_e64 %13, %6, %4, %20\n\t"
-      "v_cndmask_b32_e64 %14, %8, %9, %20\n\tv_cndmask_b32_e64 %15, %9, %8, %20\n\t"
-      "v_add_f32_dpp %10, %11, %10 " GIP_QP1 " row_mask:0xf bank_mask:0xf\n\t"
-      "v_add_f32_dpp %12, %13, %12 " GIP_QP1 " row_mask:0xf bank_mask:0xf\n\t"
-      "v_add_f32_dpp %14, %15, %14 " GIP_QP1 " row_mask:0xf bank_mask:0xf\n\t"
-      // level 2, the same on bit 1 of the lane: %16 <- %10 (lanes 0, 1 of a quad) | %12 (lanes 2, 3); %14 on its own
-      "v_cndmask_b32_e64 %17, %12, %10, %21\n\tv_cndmask_b32_e64 %16, %10, %12, %21\n\t"
-      "v_add_f32_dpp %14, %14, %14 " GIP_QP2 " row_mask:0xf bank_mask:0xf\n\t"
-      "v_add_f32_dpp %16, %17, %16 " GIP_QP2 " row_mask:0xf bank_mask:0xf\n\t"
-      "s_nop 0\n\t"
-      // level 4: banks 0, 2 <- %16, banks 1, 3 <- %14;  level 8;  terms 8, 9: odd lane (second row's tree) + even lane
-      GIP_DPP("%18", "%14", "row_shr:4", "0xa") GIP_DPP("%18", "%16", "row_shl:4", "0x5")
-      "s_nop 1\n\t"
-      GIP_DPP("%18", "%18", "row_ror:8", "0xf")
-      "s_nop 1\n\t"
-      "v_add_f32_dpp %18, %18, %18 " GIP_QP1 " row_mask:0xf bank_mask:0xa"
-      : "+v"(a.v0), "+v"(a.v1), "+v"(a.v2), "+v"(a.v3), "+v"(a.v4), "+v"(a.v5), "+v"(a.v6), "+v"(a.v7), "+v"(a.v8),
-        "+v"(a.v9), "+v"(b.v0), "+v"(b.v1), "+v"(b.v2), "+v"(b.v3), "+v"(b.v4), "+v"(b.v5), "+v"(b.v6), "+v"(b.v7),
-        "+v"(b.v8), "+v"(b.v9)
-      : "s"(0xaaaaaaaaaaaaaaaaull), "s"(0xccccccccccccccccull));
-#undef GIP_DPP
-#undef GIP_QP1
-#undef GIP_QP2
-}
 
 struct BwdPix {
   float T, Sp, Kc, g0, g1, g2, gd;
@@ -165,6 +93,7 @@ gip_render_backward_kernel(GipKernelParams kp, const GipRasterHeader* __restrict
   // where this lane stores what fold_two_entries leaves in it: lanes 16 r + j (j = 0..3) hold term 2 j + (r & 1), lanes
   // 16 r + 4 hold term 8 + (r & 1)
   float* const row_term = partial + (((lane & 15) < 4 ? 2 * (lane & 3) : 8) + ((lane >> 4) & 1));
+  const int xaddr = (lane ^ 32) << 2;   // the fold's ds_bpermute address: lane ^ 32
   const size_t HW = (size_t)kp.H * kp.W;
   const float bg0 = bg[0], bg1 = bg[1], bg2 = bg[2];
   // an overflowed forward left truncated buckets behind: nothing downstream is meaningful (the host raises when it
@@ -355,7 +284,7 @@ gip_render_backward_kernel(GipKernelParams kp, const GipRasterHeader* __restrict
           continue;
         }
         // an entry no pixel took folds exact +0 (every one of its terms is +0 in every lane)
-        fold_two_entries(a, bb);
+        fold_two_entries(a, bb, xaddr);
         if (rsel != 0xffffffffu) {
           float* dst = row_term + (size_t)rsel * GIP_PARTIAL_FLOATS;
           if ((lane & 15) <= 4) dst[0] = bb.v8;
